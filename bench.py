@@ -19,8 +19,15 @@ gradient all-reduce over RCCL (N > 1) -> Adam step -> weight re-pack.  fp32 thro
 every rank renders its own 4096 rays per step.
 
 Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel, from HIP events recorded on the launch stream
-inside the timed region; `cpu_baseline` is the oracle (CPU port of the reference path, oracle/nerf_oracle.py) timed on
-this box's host cores on a bounded sample (N=1 only).
+inside the timed region.  A plain run does only that: set up, warm up, time the --steps steps, print the line.
+    --full              also everything that takes runs of its own: the same steps again without the HIP events
+                        (`unprofiled_rerun`), per-net all-reduce times (N > 1), and at N = 1 `cpu_baseline` (the oracle,
+                        oracle/nerf_oracle.py, the CPU port of the reference path, timed on the host's cores on a bounded
+                        sample), `pytorch_rocm_reference`, `dropin_route` and the `labelled_lines` (other precisions,
+                        workloads, sizes and the trained regime, each measured in a child process)
+    --dump-outputs DIR  after the timed steps, what the last timed step computed as DIR/<name>.npy (float32): train --
+                        the loss, both nets' rendered colours, the gradient and the updated weights; eval -- the rendered
+                        maps and the 8-bit image rows.  Inputs are seeded: the same arguments give the same inputs.
 """
 import argparse
 import json
@@ -29,6 +36,7 @@ import os
 import socket
 import subprocess
 import sys
+import tempfile
 import time
 
 import torch
@@ -250,6 +258,26 @@ def cpu_baseline_eval(sample_rays=8192):
                        "oracle/nerf_oracle.py on torch %s CPU ops" % (sample_rays, torch.__version__))
 
 
+def dump_outputs(dirname, arrays, limit_bytes=64 << 20):
+    """arrays {name: tensor} -> dirname/<name>.npy in float32 (float64 stays float64).  Above `limit_bytes` in all, every array
+    of more than one row keeps the same fixed, seeded sample of its rows (numpy default_rng(0), sorted)."""
+    import numpy as np
+    out = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+        out[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in out.values())
+    if total > limit_bytes:
+        frac = limit_bytes / float(total)
+        for name, a in out.items():
+            if a.ndim > 0 and a.shape[0] > 1:
+                keep = max(1, int(a.shape[0] * frac))
+                out[name] = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -412,6 +440,10 @@ def main():
                     "per-kernel times, no roofline object): what the events cost a short step")
     ap.add_argument("--dry-run", action="store_true", help="launcher / rendezvous / timing plumbing only, on the CPU with "
                     "gloo: no kernel runs and no number is reported (the CPU test-suite uses it)")
+    ap.add_argument("--full", action="store_true", help="also the measurements that take runs of their own: the unprofiled rerun, "
+                    "all-reduce times, CPU baseline, PyTorch-ROCm reference, drop-in route and the labelled lines (off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy "
+                    "(float32, at most 64 MB in all)")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 20 if args.mode == "train" else 3
@@ -540,7 +572,7 @@ def main():
                 rgb8 = N.eval_utils._cast_to_image_device(out[3])           # eval_nerf.py:178-184 (8-bit cast on the device)
                 if args.gather:
                     rgb8 = N.parallel.gather_image_rows(rgb8)
-            return rgb8
+            return rgb8, out
         samples_per_step = (n * nc, n * (nc + nf))
 
     for i in range(args.warmup):
@@ -568,10 +600,19 @@ def main():
         gathered = [torch.zeros_like(tt) for _ in range(world)]
         torch.distributed.all_gather(gathered, tt)
         per_rank = [float(t) for t in gathered]
-        if args.mode == "train":
+        if args.mode == "train" and args.full:
             allreduce_ms = eng.collective_times_ms()
     dt = max(per_rank)
     loss_host = [float(v) for v in last.cpu()] if args.mode == "train" else None
+    if args.dump_outputs and rank == 0:   # (before anything below runs another step)
+        if args.mode == "train":
+            b = eng._bufs
+            arrays = dict(loss=last, rgb_coarse=b["rgb_c"], rgb_fine=b["rgb_f"], grad=eng.grad, params_coarse=mc.flat_params,
+                          params_fine=mf.flat_params)
+        else:
+            rgb8, out = last
+            arrays = dict(rgb_coarse=out[0], acc_coarse=out[2], rgb_fine=out[3], acc_fine=out[5], rgb8=rgb8)
+        dump_outputs(args.dump_outputs, arrays)
     # compacted backward: the sample points the LAST timed step's backward kept, per net (two words per net of its workspace)
     kept = eng.backward_sample_counts() if (args.mode == "train" and args.compact not in (None, "dense")) else None
     # (the mode the accounting below assumes: `auto` -> what the last timed step's nets ran in; per-net / per-step mixes make the auto
@@ -584,7 +625,7 @@ def main():
     # What the per-launch HIP events of the timed region cost: the same K steps once more WITHOUT them (N = 1 only).  Nothing at
     # 27 ms per step; 0.28 ms of a 2.0-ms fern step (a step is ~40 launches, each with two event records on the host's path).
     unprofiled = None
-    if world == 1 and not args.no_kernel_profile:
+    if world == 1 and not args.no_kernel_profile and args.full:
         fence()
         t1 = time.perf_counter()
         for i in range(args.warmup + args.steps, args.warmup + 2 * args.steps):
@@ -799,7 +840,7 @@ def main():
                                     note="allreduce_ms_per_step: one all-reduce of each net's flat gradient by itself, after the timed region "
                                          "(HIP events, mean of 20: TrainEngine.collective_times_ms) -- in the step the fine net's overlaps the "
                                          "coarse backward; SURVEY 5.8 expects ~55 us for 4.77 MB over xGMI.  ms_per_step_per_rank is compute + exchange")
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             if args.mode == "train":
                 res["cpu_baseline"] = cpu_baseline(wl=wl, cfg=cfg)
                 if args.workload == "lego" and cfg == MODEL:
@@ -820,7 +861,7 @@ def main():
                     # (scripts/bench_trained.py: 2000 iterations on the teacher scene first -- where most cotangent rows are zero)
                     ref = res["pytorch_rocm_reference"].get("value")
                     res["labelled_lines"] = {}
-                    short = ["--no-cpu-baseline", "--no-labelled-lines", "--steps", str(min(args.steps, 10)), "--warmup", "2"]
+                    short = ["--full", "--no-cpu-baseline", "--no-labelled-lines", "--steps", str(min(args.steps, 10)), "--warmup", "2"]
                     # (fp16-piece plans run the two-stream step by default -- +1.4 % dense, +7 % in the trained regime --, which makes a
                     # kernel's event-to-event time that of a GPU it shares: the f16x3_train line keeps ONE stream, so that its per-kernel
                     # times are the kernels' own, and the engine's default is the line next to it)
@@ -868,11 +909,11 @@ def main():
                         except Exception as e:
                             res["labelled_lines"][label] = dict(error=repr(e)[:200])
                     try:
-                        tmp = os.path.join(ROOT, "gpurun_out", "bench_trained_regime.json")
-                        os.makedirs(os.path.dirname(tmp), exist_ok=True)
-                        subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "bench_trained.py"), tmp, "--iters", "2000", "--steps",
-                                        str(min(args.steps, 10)), "--warmup", "2"], capture_output=True, text=True, timeout=600)
-                        t = json.load(open(tmp))
+                        with tempfile.TemporaryDirectory() as tmpdir:
+                            tmp = os.path.join(tmpdir, "bench_trained_regime.json")
+                            subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "bench_trained.py"), tmp, "--iters", "2000", "--steps",
+                                            str(min(args.steps, 10)), "--warmup", "2"], capture_output=True, text=True, timeout=600)
+                            t = json.load(open(tmp))
                         tr = dict(what="%s; students %s, %s samples, %d rays/step; trained %d iterations (%s) before the timed steps; full iterations "
                                        "(selection from resident views, forward, loss, backward, Adam, re-pack)"
                                        % (t["scene"], t["student"], t["samples"], t["rays_per_step"], t["pretrain_iters"], t["pretrain"]["arm"]),

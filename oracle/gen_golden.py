@@ -255,6 +255,35 @@ def pretrained_lego(nerf):
     npz("lego_lowres_render.npz", **d)
 
 
+def pretrained_lego_checkpoint(nerf):
+    """The reference's pretrained/lego-lowres checkpoint (2 MB) cut down to a fixture of ~50 KB: every tensor -- both nets' weights
+    and the optimizer's exp_avg / exp_avg_sq -- is its leading block in the shape of a 4 x 16 net with one encoding frequency; every
+    other entry is unchanged (iter, loss, psnr, param_groups, the id() keys of the optimizer state, the integer `step`), and the file
+    is written in the legacy (pre-zip) serialization the original uses.  tests/test_io_formats.py reads it."""
+    from collections import OrderedDict
+    ck_path = os.path.join(R.REFERENCE_ROOT, "pretrained", "lego-lowres", "checkpoint199999.ckpt")
+    ck = torch.load(ck_path, map_location="cpu", weights_only=False)
+    cfg = dict(num_layers=4, hidden_size=16, skip_connect_every=4, num_encoding_fn_xyz=1, num_encoding_fn_dir=1)
+    shapes = {k: tuple(v.shape) for k, v in R.make_reference_model(nerf, cfg).state_dict().items()}
+
+    def cut(t, shape):  # (a copy: a view would carry its whole storage into the file)
+        return t[tuple(slice(0, n) for n in shape)].clone()
+    out = dict(ck)
+    for key in ("model_coarse_state_dict", "model_fine_state_dict"):
+        out[key] = OrderedDict((k, cut(v, shapes[k])) for k, v in ck[key].items())
+    osd = ck["optimizer_state_dict"]
+    ids = osd["param_groups"][0]["params"]
+    names = list(ck["model_coarse_state_dict"]) + list(ck["model_fine_state_dict"])  # (the reference's Adam: coarse, then fine)
+    state = {}
+    for pid, st in osd["state"].items():
+        shape = shapes[names[ids.index(pid)]]
+        state[pid] = {k: cut(v, shape) if isinstance(v, torch.Tensor) else v for k, v in st.items()}
+    out["optimizer_state_dict"] = dict(state=state, param_groups=osd["param_groups"])
+    path = os.path.join(GOLD, "lego_lowres_checkpoint_cut.ckpt")
+    torch.save(out, path, _use_new_zipfile_serialization=False)
+    print("wrote %-28s %8.1f KB" % (os.path.basename(path), os.path.getsize(path) / 1024))
+
+
 def reference_script_function(script, name, namespace):
     """Execute ONE function definition of a reference script (the scripts themselves cannot be imported here:
     torchvision / tensorboard / imageio are absent) and return it."""
@@ -319,6 +348,8 @@ def main():
     nerf = R.import_reference()
     if sys.argv[1:] == ["dataio"]:
         return dataio(nerf)
+    if sys.argv[1:] == ["checkpoint"]:
+        return pretrained_lego_checkpoint(nerf)
     north = dict(num_layers=8, hidden_size=256, skip_connect_every=4, num_encoding_fn_xyz=10, num_encoding_fn_dir=4)
     if sys.argv[1:] == ["northstar"]:
         return e2e_sampled(nerf, "e2e_northstar.npz", north, 5, 64, 128, seed=6)
@@ -334,6 +365,7 @@ def main():
     e2e_case(nerf, "e2e_c.npz", fern, fern, 4, 32, 32, False, False, False, 0.0, seed=3, ndc=True)
     e2e_case(nerf, "e2e_d.npz", novw, novw, 5, 8, 8, True, True, True, 1.0, seed=4)
     pretrained_lego(nerf)
+    pretrained_lego_checkpoint(nerf)
     dataio(nerf)
     e2e_sampled(nerf, "e2e_northstar.npz", north, 5, 64, 128, seed=6)
 

@@ -33,7 +33,7 @@ mocks)
     timeout 120 scripts/f16w_loop_mock; timeout 120 scripts/ws_loop_mock; timeout 120 scripts/ws_loop_mock; } > $R/mocks.txt 2>&1
   cat $R/mocks.txt ;;
 bench)
-  timeout 400 python bench.py > $R/bench.log 2>&1
+  timeout 400 python bench.py --full > $R/bench.log 2>&1
   timeout 100 python bench.py --no-cpu-baseline --precision f16x3_train > $R/bench_f16x3_train.log 2>&1
   timeout 100 python bench.py --no-cpu-baseline --hidden 128 --layers 4 > $R/bench_4x128.log 2>&1
   timeout 100 python bench.py --no-cpu-baseline --hidden 128 --layers 4 --precision f16x3_train > $R/bench_f16x3_train_4x128.log 2>&1

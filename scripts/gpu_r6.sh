@@ -48,7 +48,7 @@ tests)
   cp gpurun_out/parity_small_cases.json $R/ 2>/dev/null; for f in gpurun_out/parity_fullsize_*.json; do cp $f $R/ 2>/dev/null; done
   grep -E "passed|failed|rc=" $R/pytest_gpu.log | tail -3; grep -E "^FAILED|^ERROR" $R/pytest_gpu.log | head -20; tail -2 $R/smoke.log ;;
 bench)
-  timeout 900 python bench.py > $R/bench.log 2>&1; echo "bench rc=$?"; line $R/bench.log ;;
+  timeout 900 python bench.py --full > $R/bench.log 2>&1; echo "bench rc=$?"; line $R/bench.log ;;
 trained)
   timeout 500 python scripts/bench_trained.py $R/bench_trained.json --iters 2000 --save-weights $W > $R/bench_trained.log 2>&1; echo "trained rc=$?"; tail -8 $R/bench_trained.log ;;
 trained_more)   # the two-stream step in the compacted modes; the 4x128 nets train_nerf.py really builds

@@ -482,3 +482,30 @@ def test_models_in_auto_mode_pick_their_backward_through_the_reference_loop(hidd
         (((out[0] - 0.5) ** 2).mean() + ((out[3] - 0.5) ** 2).mean()).backward()
         grads.append(torch.cat([p.grad.reshape(-1) for p in list(a.parameters()) + list(b.parameters())]))
     assert float((grads[0] - grads[1]).abs().max()) <= 1e-5 * float(grads[1].abs().max()) + 1e-12
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` (no --full): the headline line with exactly K timed steps and none of
+    the --full measurements; DIR holds the last timed step's loss, colours, gradient and updated weights, float32, finite."""
+    import json
+    _dev()
+    root = os.path.dirname(HERE)
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    assert p.returncode == 0, p.stderr.decode()[-3000:]
+    lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, lines
+    j = json.loads(lines[0])
+    assert j["metric"] == "train rays/sec" and j["unit"] == "rays/s" and j["higher_is_better"] is True and j["steps"] == 3
+    assert j["ms_per_step"] > 0 and abs(j["value"] - 4096 * 1e3 / j["ms_per_step"]) <= 1e-2 * j["value"]
+    assert j["unprofiled_rerun"] is None and j["cpu_baseline"] is None and "labelled_lines" not in j and "pytorch_rocm_reference" not in j
+    import nerf_pytorch_amd as N
+    nparams = N.FlexibleNeRFModel(num_layers=8, hidden_size=256, skip_connect_every=4, num_encoding_fn_xyz=10, num_encoding_fn_dir=4).num_flat_params
+    shapes = dict(loss=(3,), rgb_coarse=(4096, 3), rgb_fine=(4096, 3), grad=(2 * nparams,), params_coarse=(nparams,), params_fine=(nparams,))
+    assert sorted(os.listdir(out)) == sorted(k + ".npy" for k in shapes)
+    for name, shape in shapes.items():
+        a = np.load(out / (name + ".npy"))
+        assert a.dtype == np.float32 and a.shape == shape and np.isfinite(a).all(), name
+    loss = np.load(out / "loss.npy")
+    assert abs(float(loss[2]) - float(loss[0] + loss[1])) <= 1e-6 and np.allclose(loss, j["final_loss"], rtol=1e-6, atol=0)

@@ -374,3 +374,32 @@ def test_bench_launches_its_own_ranks_when_started_plainly():
     bad = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run"],
                          env=dict(env, WORLD_SIZE="1", RANK="0"), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
     assert bad.returncode != 0 and b"WORLD_SIZE=1" in bad.stderr
+
+
+def test_bench_dump_outputs_writes_float32_and_samples_above_the_cap(tmp_path):
+    """bench.py --dump-outputs: one DIR/<name>.npy per array, float32 (float64 kept); above the byte cap every multi-row array
+    keeps the same seeded rows, so that two runs (two builds) can be compared output for output."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    B = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(B)
+    g = torch.Generator().manual_seed(0)
+    arrays = dict(loss=torch.rand(3, generator=g), rgb=torch.rand(1000, 3, generator=g), img=torch.randint(0, 256, (40, 5, 3), dtype=torch.uint8),
+                  wide=np.random.RandomState(1).rand(500).astype(np.float64))
+    B.dump_outputs(str(tmp_path / "all"), arrays)
+    for name, t in arrays.items():
+        a = np.load(tmp_path / "all" / (name + ".npy"))
+        ref = t.numpy() if isinstance(t, torch.Tensor) else t
+        assert a.dtype == (np.float64 if ref.dtype == np.float64 else np.float32) and np.array_equal(a, ref.astype(a.dtype)), name
+    cap = 8 * 1024
+    for run in ("s1", "s2"):
+        B.dump_outputs(str(tmp_path / run), arrays, limit_bytes=cap)
+    total = 0
+    for name in arrays:
+        a1, a2 = np.load(tmp_path / "s1" / (name + ".npy")), np.load(tmp_path / "s2" / (name + ".npy"))
+        assert np.array_equal(a1, a2), name
+        total += a1.nbytes
+    assert total <= cap
+    rgb = np.load(tmp_path / "s1" / "rgb.npy")
+    rows = {tuple(r) for r in arrays["rgb"].numpy()}
+    assert 0 < rgb.shape[0] < 1000 and all(tuple(r) in rows for r in rgb)

@@ -12,7 +12,10 @@ import nerf_pytorch_amd as N
 from nerf_pytorch_amd import io_utils as IO
 from nerf_pytorch_amd.eval_utils import png_bytes
 
-REF_CKPT = "/root/reference/pretrained/lego-lowres/checkpoint199999.ckpt"
+# the reference's pretrained/lego-lowres/checkpoint199999.ckpt as torch 1.x wrote it, every tensor cut to the leading block of
+# REF_CKPT_CFG's nets (oracle/gen_golden.py pretrained_lego_checkpoint)
+REF_CKPT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "lego_lowres_checkpoint_cut.ckpt")
+REF_CKPT_CFG = dict(num_layers=4, hidden_size=16, skip_connect_every=4, num_encoding_fn_xyz=1, num_encoding_fn_dir=1)
 CFG = dict(num_layers=4, hidden_size=128, skip_connect_every=4, num_encoding_fn_xyz=10, num_encoding_fn_dir=4)
 
 
@@ -65,10 +68,9 @@ def test_checkpoint_round_trip(tmp_path):
     IO.load_checkpoint(path, mc2, None)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CKPT), reason="reference tree not present (build container only)")
 def test_reads_the_references_own_checkpoint():
-    """The reference's pretrained file (torch 1.x optimizer layout: id() keys, integer step)."""
-    mc, mf = N.FlexibleNeRFModel(**CFG), N.FlexibleNeRFModel(**CFG)
+    """The reference's pretrained file (torch 1.x legacy serialization; optimizer layout: id() keys, integer step)."""
+    mc, mf = N.FlexibleNeRFModel(**REF_CKPT_CFG), N.FlexibleNeRFModel(**REF_CKPT_CFG)
     eng = fake_engine(mc, mf)
     ck = IO.load_checkpoint(REF_CKPT, mc, mf, engine=eng, map_location="cpu")
     assert ck["iter"] == 199999 and eng.step_count == 200000
@@ -80,6 +82,11 @@ def test_reads_the_references_own_checkpoint():
     assert torch.equal(eng.exp_avg[:first["exp_avg"].numel()], first["exp_avg"].reshape(-1))
     assert torch.equal(eng.exp_avg_sq[-last["exp_avg_sq"].numel():], last["exp_avg_sq"].reshape(-1))
     assert float(eng.exp_avg_sq.min()) >= 0
+    # the fixture's weights are the leading blocks of the reference's trained nets (tests/golden/lego_lowres_weights.npz: the whole file's)
+    full = np.load(os.path.join(os.path.dirname(REF_CKPT), "lego_lowres_weights.npz"))
+    for tag, m in (("c_", mc), ("f_", mf)):
+        for name, p in m.named_parameters():
+            assert np.array_equal(p.detach().numpy(), full[tag + name][tuple(slice(0, n) for n in p.shape)]), tag + name
 
 
 def test_cached_example_round_trip(tmp_path):
