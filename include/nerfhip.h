@@ -446,6 +446,28 @@ int nerfhip_select_cached_rays(const nerfhip_select_cfg* cfg, const float* ray_o
                                const float* targets, int64_t population, const int64_t* select_inds, int64_t n,
                                float* rays, float* target, int64_t* inds_out, nerfhip_stream_t stream);
 
+/* ---- pose gradient (pose refinement: NeRF--, BARF, noisy COLMAP poses) --------------------------------------------------
+ * The reference's get_ray_bundle is torch arithmetic on tform_cam2world, so autograd carries d(loss)/d(rays) back to a pose
+ * that requires grad.  These are the vector-Jacobian products of nerfhip_ray_bundle and nerfhip_select_rays w.r.t. c2w:
+ * g_c2w: dev float[3, 4] (row-major, overwritten) = d(loss)/d(c2w[:3, :4]) summed over the n rays (the rows of c2w below the
+ * third carry no gradient).  The sum is a fixed-order reduction without atomics (per-workgroup partials in tmp, then one
+ * workgroup sums them): its order depends on n only, so the result is bit-reproducible from run to run and machine to
+ * machine.  tmp: dev scratch of nerfhip_pose_grad_tmp_bytes(n) bytes (-1 for n < 0).  Two launches on `stream`. */
+int64_t nerfhip_pose_grad_tmp_bytes(int64_t n);
+/* VJP of nerfhip_ray_bundle: pixels as there (NULL = all height*width pixels in row order, then n must be height*width);
+ * g_ray_origins / g_ray_directions: dev [n,3] cotangents of its two outputs (either may be NULL = zero, not both unless
+ * n == 0). */
+int nerfhip_ray_bundle_bwd(int height, int width, float focal, const int64_t* pixels, int64_t n, const float* g_ray_origins,
+                           const float* g_ray_directions, void* tmp, int64_t tmp_bytes, float* g_c2w, nerfhip_stream_t stream);
+/* VJP of nerfhip_select_rays (image branch: pin-hole rays -> optional ndc_rays -> [o d near far viewdirs] rows).  cfg / c2w /
+ * c2w_ld: those of the forward; inds: dev int64 [n], the inds_out of the forward (the select indices it used); g_rays: dev
+ * rows [n, g_rays_stride >= 8|11] of d(loss)/d(rays); g_rays_2: a second set of rows of the same layout that is added to the
+ * first one row by row before anything else (the coarse and the fine net's parts of the ray gradient), or NULL.  Columns
+ * 6 / 7 (near / far) carry no gradient; 8..10 go through the normalisation of the pre-NDC direction. */
+int nerfhip_select_rays_bwd(const nerfhip_select_cfg* cfg, const float* c2w, int c2w_ld, const int64_t* inds, int64_t n,
+                            const float* g_rays, const float* g_rays_2, int g_rays_stride, void* tmp, int64_t tmp_bytes,
+                            float* g_c2w, nerfhip_stream_t stream);
+
 /* cast_to_image (eval_nerf.py:23-29): ToPILImage of a float image = mul(255) then byte conversion (truncation).
  * rgb: dev [pixels, in_channels >= 3] (first three used); out: dev uint8 [pixels, 3] (H, W, 3 byte order). */
 int nerfhip_cast_to_image(const float* rgb, int in_channels, int64_t pixels, uint8_t* out, nerfhip_stream_t stream);

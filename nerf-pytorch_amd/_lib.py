@@ -131,6 +131,10 @@ _PROTOS = {
     "nerfhip_select_rays": (C.c_int, [C.POINTER(SelectCfg), c_f, C.c_int, c_f, c_f, c_i64, c_f, c_f, c_f, c_f]),
     "nerfhip_select_cached_rays": (C.c_int, [C.POINTER(SelectCfg), c_f, c_f, c_f, c_i64, c_f, c_i64, c_f, c_f, c_f,
                                              c_f]),
+    "nerfhip_pose_grad_tmp_bytes": (c_i64, [c_i64]),
+    "nerfhip_ray_bundle_bwd": (C.c_int, [C.c_int, C.c_int, C.c_float, c_f, c_i64, c_f, c_f, c_f, c_i64, c_f, c_f]),
+    "nerfhip_select_rays_bwd": (C.c_int, [C.POINTER(SelectCfg), c_f, C.c_int, c_f, c_i64, c_f, c_f, C.c_int, c_f, c_i64, c_f,
+                                          c_f]),
     "nerfhip_cast_to_image": (C.c_int, [c_f, C.c_int, c_i64, c_f, c_f]),
     "nerfhip_cast_to_disparity_image": (C.c_int, [c_f, c_i64, c_f, c_f, c_f]),
 }

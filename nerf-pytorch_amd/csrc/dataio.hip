@@ -2,6 +2,7 @@
 //   * training-ray selection: draw N distinct pixels, generate ONLY those rays, pack them, gather their target
 //     colours (train_nerf.py:210-227, cached branch :175-194) -- one launch instead of a host permutation of the
 //     whole image, a full-image get_ray_bundle and three fancy-index gathers;
+//   * its backward to the pose (pose refinement): d(loss)/d(rays) -> d(loss)/d(c2w[:3, :4]), a fixed-order reduction;
 //   * 8-bit output: cast_to_image / cast_to_disparity_image (eval_nerf.py:23-36).
 // Everything here is HBM/latency-bound byte and index work: one thread per ray / pixel, coalesced rows.
 #include "nh_host.h"
@@ -140,6 +141,166 @@ extern "C" int nerfhip_select_cached_rays(const nerfhip_select_cfg* cfg, const f
     NH_REQUIRE(cfg && ray_origins && ray_directions, "select_cached_rays: bad arguments");
     return select_launch(cfg, nullptr, 0, ray_origins, ray_directions, targets, population, select_inds, n, rays, target,
                          inds_out, stream, "select_cached_rays");
+}
+
+// ---- pose VJP: d(loss)/d(c2w[:3, :4]) from d(loss)/d(rays) (what autograd gives the reference's pose) --------------------
+// get_ray_bundle is linear in the pose: d = c2w[:3, :3] dc, o = c2w[:3, 3] (nh_pinhole_ray), so ray r contributes
+// g_c2w[c][k] += g_d[c] dc[k] (k < 3) and g_c2w[c][3] += g_o[c].  The select form first runs the packing and NDC backward of
+// the ray's row in registers (viewdir normalisation, nh_ndc_ray_vjp), recomputing the pre-NDC ray from the pose.
+// Reduction without atomics, in an order that depends on n only (bit-reproducible run to run and machine to machine):
+// k_pose_vjp_part -- G(n) = min(ceil(n / 256), 1024) workgroups of 256 threads; thread t of workgroup b sums rays
+// i = b * 256 + t + q * 256 G (q = 0, 1, ...) in q order, each wave combines its lanes by an xor butterfly, lane 0 of each wave
+// hands its 12 sums to LDS and the workgroup's sums of its 4 waves (in wave order) go to tmp[b][12]; k_pose_vjp_sum -- one
+// workgroup, wave j sums tmp[p][j] over p = lane, lane + 64, ... in p order, then an xor butterfly.
+namespace {
+
+constexpr int PV_THREADS = 256, PV_MAX_WGS = 1024;
+
+int64_t pv_wgs(int64_t n) { return n <= 0 ? 0 : (nh_ceil_div(n, PV_THREADS) < PV_MAX_WGS ? nh_ceil_div(n, PV_THREADS) : PV_MAX_WGS); }
+
+struct PoseVjpArgs {
+    nerfhip_select_cfg s;
+    NhNdc ndc;
+    int select;               // 1: select form (row k % height, col k / height; packing / NDC backward); 0: bundle form
+    const float* c2w;         // select form only (the pre-NDC ray)
+    int ld;
+    const int64_t* inds;      // select indices / linear pixel ids (row * width + col), or NULL: ray i is pixel i
+    int64_t n;
+    const float* g_a;         // select form: d(loss)/d(rays) rows; bundle form: d(loss)/d(origins) [n, 3] or NULL
+    const float* g_b;         // select form: a second set of rows, added (may be NULL); bundle form: d/d(directions) or NULL
+    int g_stride;
+    float* tmp;               // [G][12] workgroup partials
+};
+
+// this ray's 12 terms: t[c * 4 + k] = g_d[c] dc[k] (k < 3), t[c * 4 + 3] = g_o[c]
+NH_DEVICE void pose_vjp_ray(const PoseVjpArgs& a, int64_t i, float* t) {
+    const int64_t k = a.inds ? a.inds[i] : i;
+    int64_t row, col;
+    if (a.select) {
+        row = k % a.s.height, col = k / a.s.height;  // (k_select_rays)
+    } else {
+        row = k / a.s.width, col = k % a.s.width;    // (k_ray_bundle)
+    }
+    float dc[3], go[3] = {0.f, 0.f, 0.f}, gd[3] = {0.f, 0.f, 0.f};
+    nh_pinhole_cam(a.s.height, a.s.width, a.s.focal, row, col, dc);
+    if (a.select) {
+        const float* ga = a.g_a + i * a.g_stride;
+        const float* gb = a.g_b ? a.g_b + i * a.g_stride : nullptr;
+        float gr[11];
+        const int cols = a.s.use_viewdirs ? 11 : 8;
+        for (int c = 0; c < cols; ++c) gr[c] = gb ? ga[c] + gb[c] : ga[c];  // (columns 6, 7: near / far carry no gradient)
+        float o[3], d[3];
+        nh_pinhole_ray(a.s.height, a.s.width, a.s.focal, a.c2w, a.ld, row, col, o, d);
+        if (a.s.ndc) {
+            nh_ndc_ray_vjp(a.ndc, o, d, gr, gr + 3, go, gd);
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) go[c] = gr[c], gd[c] = gr[3 + c];
+        }
+        if (a.s.use_viewdirs) {  // v / ||v|| of the pre-NDC direction (nh_write_ray_row): (g_v - u (u . g_v)) / ||v||, u = v / ||v||
+            const float nrm = sqrtf(fmaf(d[2], d[2], fmaf(d[1], d[1], d[0] * d[0])));
+            const float u0 = d[0] / nrm, u1 = d[1] / nrm, u2 = d[2] / nrm;
+            const float dot = u0 * gr[8] + u1 * gr[9] + u2 * gr[10];
+            gd[0] = gd[0] + (gr[8] - u0 * dot) / nrm;
+            gd[1] = gd[1] + (gr[9] - u1 * dot) / nrm;
+            gd[2] = gd[2] + (gr[10] - u2 * dot) / nrm;
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (a.g_a) go[c] = a.g_a[i * 3 + c];
+            if (a.g_b) gd[c] = a.g_b[i * 3 + c];
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        t[c * 4 + 0] = gd[c] * dc[0];
+        t[c * 4 + 1] = gd[c] * dc[1];
+        t[c * 4 + 2] = gd[c] * dc[2];
+        t[c * 4 + 3] = go[c];
+    }
+}
+
+NH_KERNEL void k_pose_vjp_part(PoseVjpArgs a) {
+    NH_SHARED float s_part[PV_THREADS / 64][12];
+    float acc[12];
+#pragma unroll
+    for (int j = 0; j < 12; ++j) acc[j] = 0.0f;
+    const int64_t step = (int64_t)gridDim.x * PV_THREADS;
+    for (int64_t i = (int64_t)blockIdx.x * PV_THREADS + threadIdx.x; i < a.n; i += step) {
+        float t[12];
+        pose_vjp_ray(a, i, t);
+#pragma unroll
+        for (int j = 0; j < 12; ++j) acc[j] += t[j];
+    }
+#pragma unroll
+    for (int j = 0; j < 12; ++j) acc[j] = nh_wave_sum(acc[j]);
+    const int wave = nh_wave_in_block();
+    if (nh_lane() == 0) {
+#pragma unroll
+        for (int j = 0; j < 12; ++j) s_part[wave][j] = acc[j];
+    }
+    nh_block_sync();
+    if (threadIdx.x < 12) {
+        float v = s_part[0][threadIdx.x];
+        for (int w = 1; w < PV_THREADS / 64; ++w) v += s_part[w][threadIdx.x];
+        a.tmp[(int64_t)blockIdx.x * 12 + threadIdx.x] = v;
+    }
+}
+
+NH_KERNEL void k_pose_vjp_sum(const float* __restrict__ tmp, int wgs, float* __restrict__ g_c2w) {
+    const int j = nh_wave_in_block(), lane = nh_lane();
+    float v = 0.0f;
+    for (int p = lane; p < wgs; p += 64) v += tmp[(int64_t)p * 12 + j];
+    v = nh_wave_sum(v);
+    if (lane == 0) g_c2w[j] = v;
+}
+
+int pose_vjp_launch(const PoseVjpArgs& a, int64_t tmp_bytes, float* g_c2w, nerfhip_stream_t stream, const char* what) {
+    const int64_t wgs = pv_wgs(a.n);
+    NH_REQUIRE(tmp_bytes >= wgs * 12 * (int64_t)sizeof(float) && (wgs == 0 || a.tmp),
+               "%s: tmp must hold nerfhip_pose_grad_tmp_bytes(n) = %lld bytes", what, (long long)(wgs * 12 * sizeof(float)));
+    if (wgs > 0) {
+        NH_LAUNCH(k_pose_vjp_part, wgs, PV_THREADS, 0, stream, a);
+        int rc = nh_launch_status(what);
+        if (rc) return rc;
+    }
+    NH_LAUNCH(k_pose_vjp_sum, 1, 12 * 64, 0, stream, (const float*)a.tmp, (int)wgs, g_c2w);  // (n == 0: zeros)
+    return nh_launch_status(what);
+}
+
+}  // namespace
+
+extern "C" int64_t nerfhip_pose_grad_tmp_bytes(int64_t n) { return n < 0 ? -1 : pv_wgs(n) * 12 * (int64_t)sizeof(float); }
+
+extern "C" int nerfhip_ray_bundle_bwd(int height, int width, float focal, const int64_t* pixels, int64_t n,
+                                      const float* g_ray_origins, const float* g_ray_directions, void* tmp, int64_t tmp_bytes,
+                                      float* g_c2w, nerfhip_stream_t stream) {
+    NH_REQUIRE(height > 0 && width > 0 && n >= 0 && g_c2w && (n == 0 || g_ray_origins || g_ray_directions),
+               "ray_bundle_bwd: bad arguments");
+    NH_REQUIRE(pixels || n == (int64_t)height * width, "ray_bundle_bwd: n must be height*width when pixels is NULL");
+    PoseVjpArgs a;
+    memset(&a, 0, sizeof(a));
+    a.s.height = height, a.s.width = width, a.s.focal = focal;
+    a.select = 0, a.inds = pixels, a.n = n, a.g_a = g_ray_origins, a.g_b = g_ray_directions, a.g_stride = 3;
+    a.tmp = (float*)tmp;
+    return pose_vjp_launch(a, tmp_bytes, g_c2w, stream, "ray_bundle_bwd");
+}
+
+extern "C" int nerfhip_select_rays_bwd(const nerfhip_select_cfg* cfg, const float* c2w, int c2w_ld, const int64_t* inds,
+                                       int64_t n, const float* g_rays, const float* g_rays_2, int g_rays_stride, void* tmp,
+                                       int64_t tmp_bytes, float* g_c2w, nerfhip_stream_t stream) {
+    NH_REQUIRE(cfg && c2w && c2w_ld >= 4 && cfg->height > 0 && cfg->width > 0 && n >= 0 && g_c2w && (n == 0 || (inds && g_rays)),
+               "select_rays_bwd: bad arguments");
+    NH_REQUIRE(g_rays_stride >= (cfg->use_viewdirs ? 11 : 8), "select_rays_bwd: g_rays_stride must cover the %d columns of a ray row",
+               cfg->use_viewdirs ? 11 : 8);
+    PoseVjpArgs a;
+    memset(&a, 0, sizeof(a));
+    a.s = *cfg;
+    a.ndc = NhNdc{cfg->ndc_near, cfg->ndc_cw, cfg->ndc_ch, cfg->ndc_two_near, cfg->ndc_neg_two_near};
+    a.select = 1, a.c2w = c2w, a.ld = c2w_ld, a.inds = inds, a.n = n, a.g_a = g_rays, a.g_b = g_rays_2;
+    a.g_stride = g_rays_stride, a.tmp = (float*)tmp;
+    return pose_vjp_launch(a, tmp_bytes, g_c2w, stream, "select_rays_bwd");
 }
 
 // ---- 8-bit output stage (eval_nerf.py:23-36) ---------------------------------------------------------------------------

@@ -19,9 +19,10 @@ void nh_set_error(const char* fmt, ...) {
 extern "C" const char* nerfhip_last_error(void) { return g_err; }
 extern "C" int nerfhip_version(void) {
 #ifdef NH_DIAG  // (make variant: an A/B or diagnostic build -- nh_diag.h; the Python package refuses it)
-    return 104 + NH_DIAG_VERSION_FLAG;
+    return 105 + NH_DIAG_VERSION_FLAG;
 #else
-    return 104;  // (102: round 6 -- the compacted backward's three entry points; 103: + the fused backward modes 3 / 4 of 64-wide nets; 104: + mode 5)
+    return 105;  // (102: round 6 -- the compacted backward's three entry points; 103: + the fused backward modes 3 / 4 of 64-wide nets; 104: + mode 5;
+                 // 105: + the pose VJP, nerfhip_pose_grad_tmp_bytes / nerfhip_ray_bundle_bwd / nerfhip_select_rays_bwd)
 #endif
 }
 extern "C" int nerfhip_is_emulated(void) {
@@ -212,40 +213,23 @@ extern "C" int nerfhip_ndc_rays(float near, float cw, float ch, float two_near, 
     return nh_launch_status("ndc_rays");
 }
 
-// Vector-Jacobian product of ndc_rays: the chain rule through the statements of nh_ndc_ray in reverse order, which is what
-// autograd does to nerf/nerf_helpers.py:170-197 (t = -(near + oz)/dz; p = o + t d; the six outputs are rational in p, d).
+// Vector-Jacobian product of ndc_rays (nh_ndc_ray_vjp, nh_rays.h).
 NH_KERNEL void k_ndc_rays_bwd(NhNdc k, const float* __restrict__ ro, const float* __restrict__ rd,
                               const float* __restrict__ g_oo, const float* __restrict__ g_od, int64_t n,
                               float* __restrict__ g_ro, float* __restrict__ g_rd) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float ox = ro[i * 3], oy = ro[i * 3 + 1], oz = ro[i * 3 + 2];
-    const float dx = rd[i * 3], dy = rd[i * 3 + 1], dz = rd[i * 3 + 2];
-    const float gO0 = g_oo[i * 3], gO1 = g_oo[i * 3 + 1], gO2 = g_oo[i * 3 + 2];
-    const float gD0 = g_od[i * 3], gD1 = g_od[i * 3 + 1], gD2 = g_od[i * 3 + 2];
-    const float t = -(k.near + oz) / dz;
-    const float px = ox + t * dx, py = oy + t * dy, pz = oz + t * dz;
-    const float ipz = 1.0f / pz, idz = 1.0f / dz;
-    // outputs -> p, d
-    const float ax = k.cw * (gO0 - gD0), ay = k.ch * (gO1 - gD1);  // d/d(px/pz), d/d(py/pz)
-    float gpx = ax * ipz, gpy = ay * ipz;
-    float gpz = -(ax * px + ay * py + k.two_near * gO2 + k.neg_two_near * gD2) * ipz * ipz;
-    float gdx = k.cw * gD0 * idz, gdy = k.ch * gD1 * idz;
-    float gdz = -(k.cw * gD0 * dx + k.ch * gD1 * dy) * idz * idz;
-    // p = o + t d
-    const float gt = gpx * dx + gpy * dy + gpz * dz;
-    gdx += t * gpx;
-    gdy += t * gpy;
-    gdz += t * gpz;
-    // t = -(near + oz) / dz
-    gpz += -gt * idz;                         // (g wrt oz: through p and through t)
-    gdz += gt * (k.near + oz) * idz * idz;
-    g_ro[i * 3] = gpx;
-    g_ro[i * 3 + 1] = gpy;
-    g_ro[i * 3 + 2] = gpz;
-    g_rd[i * 3] = gdx;
-    g_rd[i * 3 + 1] = gdy;
-    g_rd[i * 3 + 2] = gdz;
+    const float o[3] = {ro[i * 3], ro[i * 3 + 1], ro[i * 3 + 2]};
+    const float d[3] = {rd[i * 3], rd[i * 3 + 1], rd[i * 3 + 2]};
+    const float gO[3] = {g_oo[i * 3], g_oo[i * 3 + 1], g_oo[i * 3 + 2]};
+    const float gD[3] = {g_od[i * 3], g_od[i * 3 + 1], g_od[i * 3 + 2]};
+    float go[3], gd[3];
+    nh_ndc_ray_vjp(k, o, d, gO, gD, go, gd);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        g_ro[i * 3 + c] = go[c];
+        g_rd[i * 3 + c] = gd[c];
+    }
 }
 
 extern "C" int nerfhip_ndc_rays_bwd(float near, float cw, float ch, float two_near, float neg_two_near, const float* rays_o,

@@ -75,6 +75,7 @@ class TrainEngine:
         self._ws = None
         self._ws_n = -1
         self._bufs = None
+        self.ray_grad_coarse = None   # the coarse net's part of d(loss)/d(rays) of a step with ray_grad (forward_backward)
         # backward mode of the step: None -- whatever each model's set_backward_compaction says (default: dense); "dense" / "compact" /
         # "recompute" -- set on both models; "auto" -- chosen per net and per step from the zero-cotangent fraction the previous
         # compacted steps reported (read back asynchronously: no host synchronisation), see _choose_backward_modes
@@ -141,7 +142,26 @@ class TrainEngine:
             self._ev = (torch.cuda.Event(), torch.cuda.Event())
         return main, self._side
 
-    def forward_backward(self, rays, target, ray_offset=0, global_rays=None, draws=None):
+    def _ray_grad_bufs(self, n):
+        """Engine-owned buffers of a step with a ray gradient: the coarse net's part of d(loss)/d(rays) and one tmp per net (the two
+        nets' backward chains may run at the same time on two streams)."""
+        if getattr(self, "_rg_n", -1) != n:
+            plan_f = self.mf._plan if self.mf is not None else None
+            tb = self.lib.render_bwd_rays_tmp_bytes(self.mc._plan, plan_f, C.byref(self.cfg), n)
+            if tb < 0:
+                raise L.NerfHipError(self.lib.last_error().decode())
+            mk = lambda *s: torch.empty(s, dtype=torch.float32, device=self.dev)  # noqa: E731
+            self.ray_grad_coarse = mk(n, self.stride) if self.mf is not None else None
+            self._rg_tmp = (mk(tb // 4 + 1), mk(tb // 4 + 1) if self.mf is not None else None, tb)
+            self._rg_n = n
+        return self.ray_grad_coarse, self._rg_tmp
+
+    def _no_pose_grad_across_ranks(self, what):
+        if self.world > 1:
+            raise NotImplementedError("TrainEngine: %s with world size %d is not implemented (the pose / ray gradient of a "
+                                      "data-parallel step would need its own all-reduce); run it with one rank" % (what, self.world))
+
+    def forward_backward(self, rays, target, ray_offset=0, global_rays=None, draws=None, ray_grad=None):
         """rays: (n, 8|11) packed rows on the device; target: (n, >=3), row stride free (an RGBA image's [..., :3] view
         works).  Leaves the summed-over-this-rank gradient in self.grad and {coarse_mse, fine_mse, sum} in self.loss
         (device); with world > 1 the gradient all-reduces are in flight when this returns (optimizer_step waits).
@@ -150,8 +170,19 @@ class TrainEngine:
         draws: None (production: in-kernel Philox draws keyed by (seed, step, global ray index)) or the reference's four
         draws as device tensors (t_rand (n, nc), noise_coarse (n, nc), u (n, nf), noise_fine (n, nc + nf); any may be
         None) -- e.g. made with torch.rand / torch.randn in the reference's order, to run the engine on exactly the random
-        numbers another implementation consumed."""
+        numbers another implementation consumed.
+        ray_grad: None, or a contiguous float32 (n, 8|11) device tensor: the step then also computes d(loss)/d(rays) (the
+        render backward with the ray gradient, nerfhip_render_bwd_rays; fused 64-wide backward modes run as mode 2 there).
+        Its two parts land in two buffers: the fine net's in `ray_grad`, the coarse net's in the engine-owned
+        `self.ray_grad_coarse` (a net with num_fine == 0: the whole of it in `ray_grad`); d(loss)/d(rays) is their sum, and
+        train_utils.select_training_rays_bwd / step_on_image(pose_grad=...) add them row by row.  One rank only."""
         self._check_inputs(rays, target)
+        if ray_grad is not None:
+            self._no_pose_grad_across_ranks("ray_grad")
+            if (not isinstance(ray_grad, torch.Tensor) or ray_grad.device != self.dev or ray_grad.dtype != torch.float32
+                    or tuple(ray_grad.shape) != tuple(rays.shape) or not ray_grad.is_contiguous()):
+                raise RuntimeError("TrainEngine: ray_grad must be a contiguous float32 tensor of the rays' shape %s on %s"
+                                   % (tuple(rays.shape), self.dev))
         lib, n = self.lib, rays.shape[0]
         gscale = 1.0 if global_rays is None else float(n) * self.world / float(global_rays)
         if self.backward == "auto":
@@ -184,6 +215,12 @@ class TrainEngine:
         bwd_head = (self.mc._plan, plan_f, C.byref(self.cfg), rays.data_ptr(), n, self.packed_c.data_ptr(), pf, rr, seed,
                     ray_offset)
         bwd_tail = (self._ws.data_ptr(), self._wsb, gc.data_ptr(), gf.data_ptr() if gf is not None else None)
+        if ray_grad is not None:
+            g_rays_c, (tmp_c, tmp_f, tmpb) = self._ray_grad_bufs(n)
+            if g_rays_c is None:
+                g_rays_c = ray_grad
+            pc_flat = self.mc.flat_params.data_ptr()
+            pf_flat = self.mf.flat_params.data_ptr() if nf > 0 else None
         self._pending = []
         with torch.cuda.device(self.dev):
             main, side = self._streams()
@@ -194,7 +231,11 @@ class TrainEngine:
             def coarse_backward(stream_handle):
                 lib.mse_loss_fwd_bwd(b["rgb_c"].data_ptr(), None, target.data_ptr(), tstride, n, gscale, b["g_c"].data_ptr(),
                                      None, self._loss_c.data_ptr(), stream_handle)
-                lib.render_bwd_parts(*bwd_head, C.byref(cot_c), *bwd_tail, L.PART_COARSE, stream_handle)
+                if ray_grad is None:
+                    lib.render_bwd_parts(*bwd_head, C.byref(cot_c), *bwd_tail, L.PART_COARSE, stream_handle)
+                else:
+                    lib.render_bwd_rays(*bwd_head, C.byref(cot_c), *bwd_tail, L.PART_COARSE, pc_flat, pf_flat, tmp_c.data_ptr(),
+                                        tmpb, g_rays_c.data_ptr(), stream_handle)
 
             if two:
                 e1, e2 = self._ev
@@ -206,7 +247,11 @@ class TrainEngine:
                 lib.render_fwd_parts(*fwd_args, L.PART_FINE, st)
                 lib.mse_loss_fwd_bwd(b["rgb_f"].data_ptr(), None, target.data_ptr(), tstride, n, gscale, b["g_f"].data_ptr(),
                                      None, self._loss_f.data_ptr(), st)
-                lib.render_bwd_parts(*bwd_head, C.byref(cot_f), *bwd_tail, L.PART_FINE, st)
+                if ray_grad is None:
+                    lib.render_bwd_parts(*bwd_head, C.byref(cot_f), *bwd_tail, L.PART_FINE, st)
+                else:
+                    lib.render_bwd_rays(*bwd_head, C.byref(cot_f), *bwd_tail, L.PART_FINE, pc_flat, pf_flat, tmp_f.data_ptr(), tmpb,
+                                        ray_grad.data_ptr(), st)
                 if self._reduce:  # in flight while the coarse backward computes
                     self._pending.append(allreduce_gradients(gf, self.pg, async_op=True, single_rank=True))
             if two:
@@ -375,30 +420,53 @@ class TrainEngine:
                               st)
         self.repack()
 
-    def step(self, rays, target, ray_offset=0, lr=None, global_rays=None, draws=None):
+    def step(self, rays, target, ray_offset=0, lr=None, global_rays=None, draws=None, ray_grad=None):
         """One full training iteration.  Returns the device tensor {coarse_mse, fine_mse, sum} (no host sync)."""
-        self.forward_backward(rays, target, ray_offset, global_rays, draws)
+        self.forward_backward(rays, target, ray_offset, global_rays, draws, ray_grad)
         self.optimizer_step(lr)
         return self.loss
 
-    def step_on_image(self, image, pose, height, width, focal_length, options, num_random_rays, lr=None, global_rays=None):
+    def step_on_image(self, image, pose, height, width, focal_length, options, num_random_rays, lr=None, global_rays=None,
+                      pose_grad=None):
         """One whole iteration of the reference's loop body (train_nerf.py:210-270) on a resident training image:
         on-device selection of this rank's distinct pixels (ranks take disjoint slices of one permutation keyed by
         (seed, iteration)), their rays and targets, then `step`.  No host work besides launches.
         Weak scaling (default): every rank draws `num_random_rays` rays, the step covers world * num_random_rays.
         Strong scaling (`global_rays` = the step's total, BASELINE config 3: 8192 over 8 ranks): this rank takes its
-        parallel.shard_bounds slice of the first `global_rays` positions; unequal shards are weighted (forward_backward)."""
+        parallel.shard_bounds slice of the first `global_rays` positions; unequal shards are weighted (forward_backward).
+        pose_grad: None, or a contiguous float32 (3, 4) tensor on the engine's device: the step also writes d(loss)/d(pose[:3, :4])
+        into it (pose refinement: the render backward with the ray gradient, then the pose VJP of the selection on the main
+        stream after the two streams joined, nerfhip_select_rays_bwd; still no host synchronisation).  The engine's Adam
+        updates the nets as usual (lr=0 freezes them); a pose parametrisation of one's own takes the gradient with
+        torch.autograd.backward(pose_expr[:3, :4], pose_grad).  One rank only."""
         from .parallel import shard_bounds
-        from .train_utils import select_training_rays
+        from .train_utils import select_training_rays, select_training_rays_bwd
         if global_rays is None:
             n = int(num_random_rays)
             first = self.rank * n
         else:
             first, hi = shard_bounds(int(global_rays), self.rank, self.world)
             n = hi - first
-        rays, target, _ = select_training_rays(height, width, focal_length, pose, image, n, options, seed=self.seed,
-                                               step=self.step_count, first=first)
-        return self.step(rays, target, ray_offset=first, lr=lr, global_rays=global_rays)
+        if pose_grad is None:
+            rays, target, _ = select_training_rays(height, width, focal_length, pose, image, n, options, seed=self.seed,
+                                                   step=self.step_count, first=first)
+            return self.step(rays, target, ray_offset=first, lr=lr, global_rays=global_rays)
+        self._no_pose_grad_across_ranks("pose_grad")
+        if (not isinstance(pose_grad, torch.Tensor) or pose_grad.device != self.dev or pose_grad.dtype != torch.float32
+                or tuple(pose_grad.shape) != (3, 4) or not pose_grad.is_contiguous()):
+            raise RuntimeError("TrainEngine: pose_grad must be a contiguous float32 (3, 4) tensor on %s" % self.dev)
+        with torch.no_grad():
+            rays, target, used = select_training_rays(height, width, focal_length, pose, image, n, options, seed=self.seed,
+                                                      step=self.step_count, first=first)
+        if getattr(self, "_ray_grad_n", -1) != n:
+            self._ray_grad = torch.empty((n, self.stride), dtype=torch.float32, device=self.dev)
+            self._ray_grad_n = n
+        self.forward_backward(rays, target, first, global_rays, None, self._ray_grad)
+        with torch.cuda.device(self.dev):
+            select_training_rays_bwd(height, width, focal_length, pose, used, self._ray_grad, options, self.ray_grad_coarse,
+                                     out=pose_grad)
+        self.optimizer_step(lr)
+        return self.loss
 
     @staticmethod
     def lr_at(iteration, lr0=5e-3, lr_decay=250, lr_decay_factor=0.1):

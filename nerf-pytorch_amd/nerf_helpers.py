@@ -2,9 +2,11 @@
 function runs a hand-written HIP kernel of libnerfhip.so on the tensors' device (MI355X).  CPU tensors are rejected:
 this package has no CPU path.
 
-Functions here are *not* differentiable w.r.t. their tensor inputs (the hot path never needs that: the encodings,
-depths and samples carry no gradient -- SURVEY A.8); the differentiable pieces are
-``volume_rendering_utils.volume_render_radiance_field`` and ``models.FlexibleNeRFModel``.
+Differentiable, as the reference's torch arithmetic is: ``get_ray_bundle`` and ``get_rays_at_pixels`` w.r.t. the pose
+(pose refinement: with a ``tform_cam2world`` that requires grad the rays carry a ``grad_fn`` and the backward runs the
+pose VJP kernel, nerfhip_ray_bundle_bwd), ``ndc_rays`` w.r.t. the rays, ``cumprod_exclusive``; further
+``volume_rendering_utils.volume_render_radiance_field`` and ``models.FlexibleNeRFModel``.  The rest (encodings, depth
+samples) is not differentiable w.r.t. its tensor inputs: on the hot path they carry no gradient.
 """
 import math
 from typing import Optional
@@ -108,33 +110,82 @@ def cumprod_exclusive(tensor: torch.Tensor) -> torch.Tensor:
     return _CumprodExclusive.apply(tensor.float().contiguous()).to(tensor.dtype)
 
 
+def _pose_grad_like(pose, g34):
+    """d(loss)/d(pose) of the input's shape and dtype from the 3 x 4 VJP: zero outside [:3, :4], the entries the rays read."""
+    g = torch.zeros(pose.shape, dtype=pose.dtype, device=pose.device)
+    g[:3, :4] = g34.to(pose.dtype)
+    return g
+
+
+class _RayBundle(torch.autograd.Function):
+    """get_ray_bundle / get_rays_at_pixels with the pose VJP (nerfhip_ray_bundle_bwd): the forward issues exactly the launch of
+    the non-differentiable call."""
+
+    @staticmethod
+    def forward(ctx, pose, height, width, focal, pix, shape):
+        c2w = _dev32(pose, "tform_cam2world")
+        ro, rd = _ray_bundle_launch(height, width, focal, c2w, pix, shape)
+        ctx.args = (height, width, focal, pix)
+        ctx.pose = pose.detach()
+        ctx.set_materialize_grads(False)
+        return ro, rd
+
+    @staticmethod
+    def backward(ctx, g_ro, g_rd):
+        height, width, focal, pix = ctx.args
+        pose = ctx.pose
+        if g_ro is None and g_rd is None:
+            return (None,) * 6
+        g_ro = None if g_ro is None else g_ro.reshape(-1, 3).contiguous().float()
+        g_rd = None if g_rd is None else g_rd.reshape(-1, 3).contiguous().float()
+        n = height * width if pix is None else pix.numel()
+        lib = get_lib()
+        tb = lib.pose_grad_tmp_bytes(n)
+        tmp = torch.empty(tb // 4 + 1, dtype=torch.float32, device=pose.device)
+        g34 = torch.empty((3, 4), dtype=torch.float32, device=pose.device)
+        with launch_on(pose, pix, g_ro, g_rd, tmp, g34) as st:
+            lib.ray_bundle_bwd(height, width, focal, pix.data_ptr() if pix is not None else None, n,
+                               g_ro.data_ptr() if g_ro is not None else None, g_rd.data_ptr() if g_rd is not None else None,
+                               tmp.data_ptr(), tb, g34.data_ptr(), st)
+        return (_pose_grad_like(pose, g34),) + (None,) * 5
+
+
+def _ray_bundle_launch(height, width, focal, c2w, pix, shape):
+    n = height * width if pix is None else pix.numel()
+    ro = torch.empty(shape, dtype=torch.float32, device=c2w.device)
+    rd = torch.empty_like(ro)
+    with launch_on(c2w, pix, ro, rd) as st:
+        get_lib().ray_bundle(height, width, focal, c2w.data_ptr(), c2w.stride(0), pix.data_ptr() if pix is not None else None,
+                             n, ro.data_ptr(), rd.data_ptr(), st)
+    return ro, rd
+
+
+def _wants_pose_grad(pose):
+    return torch.is_grad_enabled() and isinstance(pose, torch.Tensor) and pose.requires_grad
+
+
 def get_ray_bundle(height: int, width: int, focal_length, tform_cam2world: torch.Tensor):
     """nerf/nerf_helpers.py:67-110.  Returns (ray_origins, ray_directions), each (height, width, 3); directions are
-    not normalised."""
+    not normalised.  Differentiable w.r.t. tform_cam2world (its [:3, :4] entries), as the reference is."""
     c2w = _dev32(tform_cam2world, "tform_cam2world")
     if c2w.dim() != 2 or c2w.shape[0] < 3 or c2w.shape[1] < 4:
         raise RuntimeError("tform_cam2world must be at least 3x4")
     focal = float(focal_length)
-    n = height * width
-    ro = torch.empty((height, width, 3), dtype=torch.float32, device=c2w.device)
-    rd = torch.empty_like(ro)
-    with launch_on(c2w, ro, rd) as st:
-        get_lib().ray_bundle(height, width, focal, c2w.data_ptr(), c2w.stride(0), None, n, ro.data_ptr(), rd.data_ptr(), st)
-    return ro, rd
+    if _wants_pose_grad(tform_cam2world):
+        return _RayBundle.apply(tform_cam2world, height, width, focal, None, (height, width, 3))
+    return _ray_bundle_launch(height, width, focal, c2w, None, (height, width, 3))
 
 
 def get_rays_at_pixels(height: int, width: int, focal_length, tform_cam2world: torch.Tensor, pixels: torch.Tensor):
     """Rays of selected pixels only: `pixels` are int64 linear ids row*width+col.  Equivalent to
-    get_ray_bundle(...)[...].reshape(-1, 3)[pixels] without generating the whole image."""
+    get_ray_bundle(...)[...].reshape(-1, 3)[pixels] without generating the whole image (differentiable w.r.t. the pose
+    in the same way)."""
     c2w = _dev32(tform_cam2world, "tform_cam2world")
     pix = pixels.to(device=c2w.device, dtype=torch.int64).contiguous()
     n = pix.numel()
-    ro = torch.empty((n, 3), dtype=torch.float32, device=c2w.device)
-    rd = torch.empty_like(ro)
-    with launch_on(c2w, pix, ro, rd) as st:
-        get_lib().ray_bundle(height, width, float(focal_length), c2w.data_ptr(), c2w.stride(0), pix.data_ptr(), n,
-                             ro.data_ptr(), rd.data_ptr(), st)
-    return ro, rd
+    if _wants_pose_grad(tform_cam2world):
+        return _RayBundle.apply(tform_cam2world, height, width, float(focal_length), pix, (n, 3))
+    return _ray_bundle_launch(height, width, float(focal_length), c2w, pix, (n, 3))
 
 
 def positional_encoding(tensor, num_encoding_functions=6, include_input=True, log_sampling=True) -> torch.Tensor:

@@ -328,33 +328,104 @@ def _select_cfg(height, width, focal_length, options, channels, seed, step, firs
                        channels=int(channels), seed=int(seed) & 0xFFFFFFFFFFFFFFFF, step=int(step), first=int(first))
 
 
+def _select_pose(pose):
+    p = pose.detach().float()
+    return p if p.stride(-1) == 1 else p.contiguous()
+
+
+def _select_launch(cfg, pose, image, select_inds, n):
+    dev = pose.device
+    rays = torch.empty((n, 11 if cfg.use_viewdirs else 8), dtype=torch.float32, device=dev)
+    target = torch.empty((n, cfg.channels), dtype=torch.float32, device=dev) if image is not None else None
+    used = torch.empty((n,), dtype=torch.int64, device=dev)
+    with L.launch_on(pose, image, select_inds, rays) as st:
+        L.get_lib().select_rays(C.byref(cfg), pose.data_ptr(), pose.stride(-2), image.data_ptr() if image is not None else None,
+                                select_inds.data_ptr() if select_inds is not None else None, n, rays.data_ptr(),
+                                target.data_ptr() if target is not None else None, used.data_ptr(), st)
+    return rays, target, used
+
+
+class _SelectRays(torch.autograd.Function):
+    """select_training_rays with the pose VJP (nerfhip_select_rays_bwd): the gradient flows from the rays to the pose (its
+    [:3, :4] entries); target and select indices carry none.  The forward issues exactly the launch of the plain call."""
+
+    @staticmethod
+    def forward(ctx, pose, cfg, image, select_inds, n):
+        p = _select_pose(pose)
+        rays, target, used = _select_launch(cfg, p, image, select_inds, n)
+        ctx.keep = (cfg, p, used)
+        ctx.pose_shape = (pose.shape, pose.dtype)
+        ctx.mark_non_differentiable(*[t for t in (target, used) if t is not None])
+        ctx.set_materialize_grads(False)
+        return rays, target, used
+
+    @staticmethod
+    def backward(ctx, g_rays, _g_target, _g_used):
+        if g_rays is None:
+            return (None,) * 5
+        cfg, p, used = ctx.keep
+        g34 = _pose_vjp(cfg, p, used, g_rays.contiguous().float(), None)
+        shape, dtype = ctx.pose_shape
+        g = torch.zeros(shape, dtype=dtype, device=p.device)
+        g[:3, :4] = g34.to(dtype)
+        return g, None, None, None, None
+
+
+def _pose_vjp(cfg, pose, used, g_rays, g_rays_2, out=None):
+    """nerfhip_select_rays_bwd on the current stream: d(loss)/d(pose[:3, :4]) (3 x 4 float32) of the rays the select call with
+    `cfg` / `pose` made at the select indices `used`, from d(loss)/d(rays) rows g_rays (+ g_rays_2, added row by row)."""
+    lib = L.get_lib()
+    n = used.numel()
+    tb = lib.pose_grad_tmp_bytes(n)
+    tmp = torch.empty(tb // 4 + 1, dtype=torch.float32, device=pose.device)
+    if out is None:
+        out = torch.empty((3, 4), dtype=torch.float32, device=pose.device)
+    with L.launch_on(pose, used, g_rays, g_rays_2, tmp, out) as st:
+        lib.select_rays_bwd(C.byref(cfg), pose.data_ptr(), pose.stride(-2), used.data_ptr(), n, g_rays.data_ptr(),
+                            g_rays_2.data_ptr() if g_rays_2 is not None else None, g_rays.stride(0), tmp.data_ptr(), tb,
+                            out.data_ptr(), st)
+    return out
+
+
 def select_training_rays(height, width, focal_length, pose, image, num_random_rays, options, select_inds=None, seed=0,
                          step=0, first=0):
     """The image branch of the training loop (train_nerf.py:210-227) fused with run_one_iter_of_nerf's ray packing
     (train_utils.py:143-168), in ONE launch: draws `num_random_rays` distinct pixels on the device (or takes the
     reference's `select_inds`, the flat indices it draws with np.random.choice), generates only those rays from `pose`
     (>= 3x4, device), and gathers their targets from `image` (H, W, 3|4).  Returns (rays (N, 8|11) -- feed them to
-    predict_and_render_radiance or TrainEngine.step --, target (N, C), select_inds (N,))."""
-    lib = L.get_lib()
-    pose = pose.detach().float()
-    if pose.stride(-1) != 1:
-        pose = pose.contiguous()
-    dev = pose.device
+    predict_and_render_radiance or TrainEngine.step --, target (N, C), select_inds (N,)).
+    With a `pose` that requires grad the rays are differentiable w.r.t. it (pose refinement, as the reference's torch
+    arithmetic is): the backward runs the pose VJP kernel (select_training_rays_bwd)."""
     n = int(num_random_rays)
     channels = 3 if image is None else image.shape[-1]
     cfg = _select_cfg(height, width, focal_length, options, channels, seed, step, first)
     if image is not None:
         image = image.detach().float().contiguous()
+    dev = pose.device
     if select_inds is not None:
         select_inds = torch.as_tensor(select_inds, dtype=torch.int64, device=dev).contiguous()
-    rays = torch.empty((n, 11 if cfg.use_viewdirs else 8), dtype=torch.float32, device=dev)
-    target = torch.empty((n, channels), dtype=torch.float32, device=dev) if image is not None else None
-    used = torch.empty((n,), dtype=torch.int64, device=dev)
-    with L.launch_on(pose, image, select_inds, rays) as st:
-        lib.select_rays(C.byref(cfg), pose.data_ptr(), pose.stride(-2), image.data_ptr() if image is not None else None,
-                        select_inds.data_ptr() if select_inds is not None else None, n, rays.data_ptr(),
-                        target.data_ptr() if target is not None else None, used.data_ptr(), st)
-    return rays, target, used
+    if torch.is_grad_enabled() and pose.requires_grad:
+        return _SelectRays.apply(pose, cfg, image, select_inds, n)
+    return _select_launch(cfg, _select_pose(pose), image, select_inds, n)
+
+
+def select_training_rays_bwd(height, width, focal_length, pose, select_inds, g_rays, options, g_rays_2=None, out=None):
+    """The pose VJP of select_training_rays without autograd: d(loss)/d(pose[:3, :4]) (3 x 4 float32 device tensor; written
+    into `out` when given) of the rays select_training_rays(height, width, focal_length, pose, ..., options) made at
+    `select_inds` (its third output), from d(loss)/d(rays) rows `g_rays` (+ `g_rays_2`, added row by row: e.g. the coarse and
+    the fine net's parts that TrainEngine.forward_backward(ray_grad=...) leaves).  Enqueued on the current stream."""
+    cfg = _select_cfg(height, width, focal_length, options, 3, 0, 0, 0)
+    for name, g in (("g_rays", g_rays), ("g_rays_2", g_rays_2)):
+        if g is not None and (g.dtype != torch.float32 or g.dim() != 2 or g.stride(1) != 1
+                              or g.shape[1] < (11 if cfg.use_viewdirs else 8)):
+            raise RuntimeError("select_training_rays_bwd: %s must be float32 rows of the ray layout (got %s, shape %s)"
+                               % (name, g.dtype, tuple(g.shape)))
+    if g_rays_2 is not None and (g_rays_2.shape != g_rays.shape or g_rays_2.stride() != g_rays.stride()):
+        raise RuntimeError("select_training_rays_bwd: g_rays_2 must have the layout of g_rays")
+    if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != (3, 4) or not out.is_contiguous()):
+        raise RuntimeError("select_training_rays_bwd: out must be a contiguous float32 (3, 4) tensor")
+    used = torch.as_tensor(select_inds, dtype=torch.int64, device=pose.device).contiguous()
+    return _pose_vjp(cfg, _select_pose(pose), used, g_rays, g_rays_2, out)
 
 
 def select_cached_training_rays(cache_dict, num_random_rays, options, select_inds=None, seed=0, step=0, first=0):
