@@ -23,6 +23,7 @@ import math
 import torch
 
 from . import _lib as L
+from . import backward_mode as BM
 from .nerf_helpers import linspace01
 from .parallel import allreduce_gradients
 
@@ -79,20 +80,16 @@ class TrainEngine:
         # backward mode of the step: None -- whatever each model's set_backward_compaction says (default: dense); "dense" / "compact" /
         # "recompute" -- set on both models; "auto" -- chosen per net and per step from the zero-cotangent fraction the previous
         # compacted steps reported (read back asynchronously: no host synchronisation), see _choose_backward_modes
-        if backward not in (None, "dense", "compact", "recompute", "fused", "fused_compact", "fused_stash", "auto"):
-            raise ValueError("backward must be None, 'dense', 'compact', 'recompute', 'fused', 'fused_compact', 'fused_stash' or 'auto' (got %r)" % (backward,))
         self.backward = backward
-        self._zero_frac = {"coarse": None, "fine": None}   # last known fraction of all-zero d(loss)/d(raw) rows per net
-        self._stats_host = None
-        self._stats_event = None
-        self._stats_pending = None
-        self._probe_every = 50
+        self._nets = tuple((name, m) for name, m in (("coarse", self.mc), ("fine", self.mf)) if m is not None)
+        if backward not in (None, "auto"):
+            mode = BM.parse(backward)   # (ValueError for anything that is not a mode)
+            for _, m in self._nets:
+                m.set_backward_compaction(mode)
+        self._stats = BM.StatsReader(("coarse", "fine"))
+        self._zero_frac = self._stats.frac   # last known fraction of all-zero d(loss)/d(raw) rows per net (updated in place)
         # steps run dense / compacted / recomputed / fused / fused over the list / fused over the stash, per net ("auto")
         self.backward_modes_used = {"coarse": [0, 0, 0, 0, 0, 0], "fine": [0, 0, 0, 0, 0, 0]}
-        if backward in ("dense", "compact", "recompute", "fused", "fused_compact", "fused_stash"):
-            for m in (self.mc, self.mf):
-                if m is not None:
-                    m.set_backward_compaction({"dense": False, "compact": True}.get(backward, backward))
         self.t_vals = linspace01(num_coarse, self.dev)
         self.u_det = linspace01(num_fine, self.dev) if num_fine > 0 else None
         self.repack()
@@ -264,74 +261,29 @@ class TrainEngine:
                 torch.stack((self._loss_c[0], self._loss_f[0], self._loss_c[0] + self._loss_f[0]), out=self.loss)
             else:
                 self.loss.copy_(self._loss_c)
-            if self.backward == "auto":
-                self._request_backward_stats(n)
+            if self.backward == "auto":   # ({kept, total} of every net that ran over a list in the step just issued)
+                self._stats.request(((name, self._stats_words(name)) for name, m in self._nets if m.backward_compaction in BM.BUILDS_LIST), main)
 
-    # ---- backward="auto" ---------------------------------------------------------------------------------------------------------
-    # A compacted step costs what its gather costs when nothing is dropped (fp32: k_wgrad + 19 %, fp16 pieces + 1 %) and saves the
-    # dropped fraction of the data and weight gradient; the recomputing mode additionally trades the stash stream of the forward for a
-    # second forward over the kept samples (pays above ~2/3 dropped rows for the fp16-piece plans, never for fp32): DESIGN.md 3.3-3.4.
-    # Nets with a fused backward (fp32, 64 wide: csrc/mlp64r.hip) always run it -- over every sample (from the register-image stash,
-    # mode 5, where the plan has it: 0.70 of the recomputing kernel's time) until the list is known to drop enough of them: 5 % against
-    # the recomputing mode 3 (the list costs two small launches), 30 % against mode 5 (the list walk recomputes its forward) --, over
-    # the list from there on.
+    # ---- backward="auto" (the policy and its thresholds: backward_mode.choose) ----------------------------------------------------
     @staticmethod
     def _mode_for(frac, f16, fused=0):
-        if fused:
-            dense_mode = 5 if fused == 5 else 3
-            return 4 if (frac is not None and frac >= (0.30 if dense_mode == 5 else 0.05)) else dense_mode
-        if frac is None:
-            return 0
-        if f16:
-            return 2 if frac >= 0.72 else (1 if frac >= 0.05 else 0)
-        return 1 if frac >= 0.15 else 0
+        return BM.choose(frac, f16, fused)
 
     def _choose_backward_modes(self):
         """Sets each net's plan option for the step about to run.  The fractions come from the last compacted step whose two statistics
         words per net have arrived on the host (an asynchronous copy behind that step's backward; polled, never waited for); a net that
-        runs dense produces none, so every `_probe_every`-th step runs compacted to look again."""
-        if self._stats_event is not None and self._stats_event.query():
-            h = self._stats_host.tolist()
-            for k, name in enumerate(self._stats_pending):
-                kept, total = h[2 * k], h[2 * k + 1]
-                if total > 0:
-                    self._zero_frac[name] = 1.0 - kept / float(total)
-            self._stats_event = None
-        probe = self.step_count % self._probe_every == 0
-        for name, m in (("coarse", self.mc), ("fine", self.mf)):
-            if m is None:
-                continue
-            mode = self._mode_for(self._zero_frac[name], m.training_precision != "fp32", m.fused_backward_available())
-            if probe and mode == 0:
-                mode = 1
-            if probe and mode in (3, 5):
-                mode = 4
+        runs dense produces none, so every backward_mode.PROBE_EVERY-th step runs compacted to look again."""
+        self._stats.poll()
+        probe = self.step_count % BM.PROBE_EVERY == 0
+        for name, m in self._nets:
+            mode = BM.choose(self._zero_frac[name], m.training_precision != "fp32", m.fused_backward_available(), probe)
             if m.backward_compaction != mode:
-                m.set_backward_compaction({0: False, 1: True, 2: "recompute", 3: "fused", 4: "fused_compact", 5: "fused_stash"}[mode])
+                m._apply_backward(mode)
             self.backward_modes_used[name][mode] += 1
 
-    def _request_backward_stats(self, n):
-        """Enqueues the copy of {kept, total} of every net that ran compacted in the step just issued (current stream)."""
-        if self._stats_event is not None:
-            return  # (the previous request is still in flight)
-        names = [nm for nm, m in (("coarse", self.mc), ("fine", self.mf)) if m is not None and m.backward_compaction in (1, 2, 4)]
-        if not names:
-            return
-        if self._stats_host is None:
-            self._stats_host = torch.zeros(4, dtype=torch.int32).pin_memory()
-        lib = self.lib
-        plan_f = self.mf._plan if self.mf is not None else None
-        words = self._ws.view(torch.int32)
-        for k, name in enumerate(names):
-            model = self.mc if name == "coarse" else self.mf
-            samples = self.cfg.num_coarse if name == "coarse" else self.cfg.num_coarse + self.cfg.num_fine
-            off, nb = C.c_int64(), C.c_int64()
-            lib.render_workspace_region(self.mc._plan, plan_f, C.byref(self.cfg), n, 1, ("bwd_scratch_" + name).encode(), C.byref(off), C.byref(nb))
-            so = (off.value + lib.plan_bwd_stats_offset(model._plan, n * samples)) // 4
-            self._stats_host[2 * k:2 * k + 2].copy_(words[so:so + 2], non_blocking=True)
-        self._stats_pending = names
-        self._stats_event = torch.cuda.Event()
-        self._stats_event.record(torch.cuda.current_stream(self.dev))
+    def _stats_words(self, name):
+        """The two statistics words of net `name` in the workspace of the last step."""
+        return BM.stats_words(self.lib, self.mc._plan, self.mf._plan if self.mf is not None else None, self.cfg, self._ws_n, 1, name, self._ws)
 
     def backward_sample_counts(self):
         """{"coarse": (kept, total), "fine": (kept, total)}: the sample points the last step's COMPACTED backward of each net kept
@@ -340,18 +292,10 @@ class TrainEngine:
         out = {"coarse": None, "fine": None}
         if self._ws is None:
             return out
-        lib, n = self.lib, self._ws_n
-        plan_f = self.mf._plan if self.mf is not None else None
         torch.cuda.synchronize(self.dev)
-        words = self._ws.view(torch.int32)
-        for name, model, samples in (("coarse", self.mc, self.cfg.num_coarse), ("fine", self.mf, self.cfg.num_coarse + self.cfg.num_fine)):
-            if model is None or model.backward_compaction not in (1, 2, 4):  # (3: the fused backward over every sample builds no list)
-                continue
-            off, nb = C.c_int64(), C.c_int64()
-            lib.render_workspace_region(self.mc._plan, plan_f, C.byref(self.cfg), n, 1, ("bwd_scratch_" + name).encode(), C.byref(off), C.byref(nb))
-            so = lib.plan_bwd_stats_offset(model._plan, n * samples)
-            w = words[(off.value + so) // 4:(off.value + so) // 4 + 2].cpu()
-            out[name] = (int(w[0]), int(w[1]))
+        for name, m in self._nets:
+            if m.backward_compaction in BM.BUILDS_LIST:   # (the fused backward over every sample builds no list)
+                out[name] = tuple(self._stats_words(name).tolist())
         return out
 
     def wait_gradients(self):

@@ -13,6 +13,7 @@ import ctypes as C
 import torch
 
 from . import _lib as L
+from . import backward_mode as BM
 from .nerf_helpers import frequency_bands_cpu
 
 
@@ -162,13 +163,8 @@ class FlexibleNeRFModel(torch.nn.Module):
         self._inf_packed = None
         if getattr(self, "inference_precision", "fp32") != "fp32":
             self._inf_owner = _PlanHandle(self.cfg, PRECISIONS[self.inference_precision])
-        # the backward's data flow: what set_backward_compaction last asked for; by default the fused one-kernel backward where the plan
-        # has it (fp32 nets of hidden_size <= 64 with view directions, <= 4 layers, no skip layer: csrc/mlp64r.hip) -- over the
-        # register-image stash (5; measured on MI355X, fern workload: 1.43 -> 1.15 ms per step against the recomputing mode 3) --, else dense
-        if getattr(self, "_backward_choice", None) is None:
-            self._fused_ok = None
-            self.backward_compaction = self.fused_backward_available() or 0
-        lib.plan_set_bwd_compaction(self._plan, int(self.backward_compaction))
+        self._fused_ok = None
+        self._apply_backward(self._backward_choice)
         self._flatten()
 
     @property
@@ -190,12 +186,16 @@ class FlexibleNeRFModel(torch.nn.Module):
         precisions (plans are per net)."""
         if precision not in TRAINING_PRECISIONS:
             raise ValueError("training precision must be one of %s (got %r)" % (TRAINING_PRECISIONS, precision))
-        _PlanHandle(self.cfg, PRECISIONS[precision])  # (raises for a geometry the split-precision kernels do not cover, before anything changes)
+        probe = _PlanHandle(self.cfg, PRECISIONS[precision])  # (raises for a geometry the split-precision kernels do not cover, before anything changes)
+        if isinstance(self._backward_choice, int):  # (... and for an explicitly chosen backward the new plan does not have: the fused ones)
+            L.get_lib().plan_set_bwd_compaction(probe.ptr, self._backward_choice)
         self.training_precision = precision
         self._native_init()
         return self
 
-    backward_compaction = 0
+    backward_compaction = 0    # the plan's mode (backward_mode.NAMES)
+    _backward_choice = None    # what set_backward_compaction was asked: None (never called), "auto" or a mode
+    _stats = None              # "auto": the reader of this net's zero-row fraction
 
     def set_backward_compaction(self, on=True):
         """Compacted backward (nerfhip_plan_set_bwd_compaction; off by default): this model's backward passes drop the sample points
@@ -218,47 +218,38 @@ class FlexibleNeRFModel(torch.nn.Module):
         the mode of every training forward is chosen from the zero-row fraction this model's last compacted backward reported -- what
         TrainEngine(backward="auto") does for the engine's step: dense (64-wide nets: fused over the stash) while too little is dropped
         to pay for the list, compacted / recomputed / fused over the list from there on; a dense net is probed with one compacted
-        pass every 50 forwards.  The two statistics words come back by an asynchronous copy that is polled, never waited for."""
-        self._backward_choice = on
-        if on == "auto":
-            self._auto_frac, self._auto_calls, self._auto_event, self._auto_host = None, 0, None, None
-            self.backward_compaction = self.fused_backward_available() or 0
-        else:
-            self.backward_compaction = {"recompute": 2, "fused": 3, "fused_compact": 4, "fused_stash": 5}.get(on, int(bool(on)))
-        L.get_lib().plan_set_bwd_compaction(self._plan, self.backward_compaction)
+        pass every 50 forwards.  The two statistics words come back by an asynchronous copy that is polled, never waited for.
+        Accepted: False / True, the codes 0..5, their names "dense" / "compact" / "recompute" / "fused" / "fused_compact" / "fused_stash"
+        (backward_mode.NAMES) and "auto"; ValueError for anything else; a fused mode on a plan without one raises and changes nothing."""
+        choice = on if on == "auto" else BM.parse(on)
+        self._apply_backward(choice)
+        self._backward_choice = choice
+        self._stats, self._auto_calls = (BM.StatsReader(("net",)) if choice == "auto" else None), 0
         return self
+
+    def _apply_backward(self, choice):
+        """Puts the CURRENT plan into the mode `choice` stands for, whatever set_backward_compaction was asked (TrainEngine(backward=
+        "auto") sets its steps' modes here).  None (never asked) and "auto" start from the fused one-kernel backward where the plan has
+        it (fp32 nets of hidden_size <= 64 with view directions, <= 4 layers, no skip layer: csrc/mlp64r.hip) -- over the register-image
+        stash (5; measured on MI355X, fern workload: 1.43 -> 1.15 ms per step against the recomputing mode 3) --, else dense."""
+        mode = (self.fused_backward_available() or 0) if choice in (None, "auto") else choice
+        L.get_lib().plan_set_bwd_compaction(self._plan, mode)   # (raises for a fused mode the plan does not have: nothing has changed)
+        self.backward_compaction = mode
+
+    @property
+    def _auto_frac(self):
+        return self._stats.frac["net"] if self._stats is not None else None
 
     def _auto_choose_backward(self):
         """set_backward_compaction("auto"): sets the plan's mode for the training forward about to run (train_utils._FusedRender)."""
-        if getattr(self, "_backward_choice", None) != "auto":
+        if self._backward_choice != "auto":
             return
-        from .engine import TrainEngine
-        if self._auto_event is not None and self._auto_event.query():
-            kept, total = self._auto_host.tolist()
-            if total > 0:
-                self._auto_frac = 1.0 - kept / float(total)
-            self._auto_event = None
-        mode = TrainEngine._mode_for(self._auto_frac, self.training_precision != "fp32", self.fused_backward_available())
-        probe = self._auto_calls % 50 == 0
+        self._stats.poll()
+        mode = BM.choose(self._auto_frac, self.training_precision != "fp32", self.fused_backward_available(),
+                         probe=self._auto_calls % BM.PROBE_EVERY == 0)
         self._auto_calls += 1
-        if probe and mode == 0:
-            mode = 1
-        if probe and mode in (3, 5):
-            mode = 4
         if mode != self.backward_compaction:
-            self.backward_compaction = mode
-            L.get_lib().plan_set_bwd_compaction(self._plan, mode)
-
-    def _auto_note_stats(self, words):
-        """... and, behind a backward that ran over the list, asks for its {kept, total} (words: two int32 on the device; the copy is
-        ordered behind the backward on the current stream and lands in pinned memory)."""
-        if getattr(self, "_backward_choice", None) != "auto" or self._auto_event is not None:
-            return
-        if self._auto_host is None:
-            self._auto_host = torch.zeros(2, dtype=torch.int32).pin_memory()
-        self._auto_host.copy_(words, non_blocking=True)
-        self._auto_event = torch.cuda.Event()
-        self._auto_event.record(torch.cuda.current_stream(words.device))
+            self._apply_backward(mode)
 
     def fused_backward_available(self):
         """Truthy where set_backward_compaction("fused") works -- the plan has an LDS-resident image (csrc/nh_r64.h nh_r64_eligible):
@@ -322,10 +313,7 @@ class FlexibleNeRFModel(torch.nn.Module):
         state = self.__dict__.copy()
         for k in ("_plan_owner", "_flat", "_flat_grad", "_pack_table", "_packed_buf", "_inf_owner", "_inf_table", "_inf_packed"):
             state[k] = None
-        for k in ("_auto_event", "_auto_host"):   # (set_backward_compaction("auto"): the copy in flight stays behind)
-            if k in state:
-                state[k] = None
-        return state
+        return state   # (set_backward_compaction("auto"): _stats travels without its copy in flight, StatsReader.__getstate__)
 
     def __setstate__(self, state):
         super().__setstate__(state)

@@ -18,6 +18,7 @@ import ctypes as C
 import torch
 
 from . import _lib as L
+from . import backward_mode as BM
 from .models import FlexibleNeRFModel
 from .nerf_helpers import EmbeddingFunction, get_minibatches, linspace01, ndc_rays, sample_pdf_2 as sample_pdf
 from .volume_rendering_utils import volume_render_radiance_field
@@ -151,25 +152,17 @@ class _FusedRender(torch.autograd.Function):
             if g_rays is not None:
                 tmpb = lib.render_bwd_rays_tmp_bytes(model_c._plan, plan_f, C.byref(cfg), n)
                 tmp = torch.empty(tmpb // 4 + 1, dtype=torch.float32, device=dev)
-            now = (lib.plan_bwd_compaction(model_c._plan), lib.plan_bwd_compaction(plan_f) if plan_f is not None else 0)
-            for plan, was, cur in ((model_c._plan, ctx.bwd_modes[0], now[0]), (plan_f, ctx.bwd_modes[1], now[1])):
-                if plan is not None and was != cur:
-                    lib.plan_set_bwd_compaction(plan, was)
             # "auto" models read the {kept, total} words of their compacted backward; the two nets share one set of backward buffers
             # here (the fine pass runs first), so the passes are issued one by one with the copy in between -- the same launches in
             # the same order as the single call (not with a ray gradient: its second pass accumulates into the first one's)
-            auto = [m for m in (model_c, model_f) if m is not None and getattr(m, "_backward_choice", None) == "auto"]
+            auto = [m for m in (model_c, model_f) if m is not None and m._backward_choice == "auto"]
             passes = [parts]
             if auto and g_rays is None and parts == (L.PART_COARSE | L.PART_FINE):
                 passes = [L.PART_FINE, L.PART_COARSE]
-
-            def note(model, name, samples):
-                if model in auto and lib.plan_bwd_compaction(model._plan) in (1, 2, 4):
-                    off, nb = C.c_int64(), C.c_int64()
-                    lib.render_workspace_region(model_c._plan, plan_f, C.byref(cfg), n, 2, name, C.byref(off), C.byref(nb))
-                    so = (off.value + lib.plan_bwd_stats_offset(model._plan, n * samples)) // 4
-                    model._auto_note_stats(ws.view(torch.int32)[so:so + 2])
-
+            pins = [(p, was, lib.plan_bwd_compaction(p)) for p, was in zip((model_c._plan, plan_f), ctx.bwd_modes) if p is not None]
+            for plan, was, cur in pins:
+                if was != cur:
+                    lib.plan_set_bwd_compaction(plan, was)
             try:
                 with L.launch_on(rays, ws, gpc, gpf, tmp, *[k for k in keep if k is not None]) as st:
                     for part in passes:
@@ -181,13 +174,14 @@ class _FusedRender(torch.autograd.Function):
                                             flats[1].data_ptr() if (flats is not None and flats[1] is not None) else None,
                                             tmp.data_ptr() if tmp is not None else None, tmpb,
                                             g_rays.data_ptr() if g_rays is not None else None, st)
-                        if part & L.PART_FINE and len(passes) == 2:
-                            note(model_f, b"bwd_scratch_fine", cfg.num_coarse + nf)
-                    if parts & L.PART_COARSE:   # (the coarse pass ran last: its words are the ones in the shared buffers)
-                        note(model_c, b"bwd_scratch_coarse", cfg.num_coarse)
+                        # (the words in the shared buffers: the coarse net's behind a pass that ran it -- it runs last --, the fine net's
+                        # only between the two passes)
+                        model, net, mode = (model_c, "coarse", ctx.bwd_modes[0]) if part & L.PART_COARSE else (model_f, "fine", ctx.bwd_modes[1])
+                        if (part & L.PART_COARSE or len(passes) == 2) and model in auto and mode in BM.BUILDS_LIST:
+                            model._stats.request([("net", BM.stats_words(lib, model_c._plan, plan_f, cfg, n, 2, net, ws))], torch.cuda.current_stream(dev))
             finally:
-                for plan, was, cur in ((model_c._plan, ctx.bwd_modes[0], now[0]), (plan_f, ctx.bwd_modes[1], now[1])):
-                    if plan is not None and was != cur:
+                for plan, was, cur in pins:
+                    if was != cur:
                         lib.plan_set_bwd_compaction(plan, cur)
         grads = model_c._split_flat(gpc) + (model_f._split_flat(gpf) if nf > 0 else ())
         return (g_rays,) + (None,) * 6 + grads
