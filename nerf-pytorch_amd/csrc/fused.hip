@@ -6,12 +6,17 @@
 
 namespace {
 
-struct Workspace {
-    int64_t z_c, raw_c, w_c, z_f, raw_f, stash_c, stash_f, total;
+// one net's regions of the workspace (byte offsets)
+struct NetSpace {
+    int64_t z, raw, weights, stash;  // (weights: the coarse net's only -- the fine depths are drawn from them)
     // backward buffers, one set per net: the coarse and the fine backward chains are independent and may run on
     // different streams (nerfhip_render_bwd_parts)
-    int64_t g_raw_c, scratch_c, scratch_c_bytes, g_raw_f, scratch_f, scratch_f_bytes;
-    int64_t gnorm_c, gnorm_f;  // dL/d||rd|| per ray of the two compositing backwards (read by the ray-gradient pass)
+    int64_t g_raw, scratch, scratch_bytes;
+    int64_t gnorm;  // dL/d||rd|| per ray of the net's compositing backward (read by the ray-gradient pass)
+};
+struct Workspace {
+    NetSpace c, f;
+    int64_t total;
 };
 
 int64_t align_up(int64_t v) { return (v + 255) & ~(int64_t)255; }
@@ -30,29 +35,29 @@ Workspace layout(nerfhip_plan* pc, nerfhip_plan* pf, const nerfhip_render_cfg* c
         off = align_up(off + bytes);
         return o;
     };
-    w.z_c = take(n * nc * 4);
-    w.raw_c = take(n * nc * 16);
-    w.w_c = take(n * nc * 4);
+    w.c.z = take(n * nc * 4);
+    w.c.raw = take(n * nc * 16);
+    w.c.weights = take(n * nc * 4);
     if (nf > 0) {
-        w.z_f = take(n * sf * 4);
-        w.raw_f = take(n * sf * 16);
+        w.f.z = take(n * sf * 4);
+        w.f.raw = take(n * sf * 16);
     }
     if (training) {
-        w.gnorm_c = take(n * 4);
-        if (nf > 0) w.gnorm_f = take(n * 4);
-        w.stash_c = take(nerfhip_plan_stash_bytes(pc, n * nc));
-        if (nf > 0) w.stash_f = take(nerfhip_plan_stash_bytes(pf, n * sf));
-        w.scratch_c_bytes = nh_mlp_bwd_scratch_bytes(pc, n * nc);
-        if (nf > 0) w.scratch_f_bytes = nh_mlp_bwd_scratch_bytes(pf, n * sf);
+        w.c.gnorm = take(n * 4);
+        if (nf > 0) w.f.gnorm = take(n * 4);
+        w.c.stash = take(nerfhip_plan_stash_bytes(pc, n * nc));
+        if (nf > 0) w.f.stash = take(nerfhip_plan_stash_bytes(pf, n * sf));
+        w.c.scratch_bytes = nh_mlp_bwd_scratch_bytes(pc, n * nc);
+        if (nf > 0) w.f.scratch_bytes = nh_mlp_bwd_scratch_bytes(pf, n * sf);
         if (training == 2 && nf > 0) {
-            w.g_raw_c = w.g_raw_f = take(n * sf * 16);
-            w.scratch_c = w.scratch_f = take(w.scratch_c_bytes > w.scratch_f_bytes ? w.scratch_c_bytes : w.scratch_f_bytes);
+            w.c.g_raw = w.f.g_raw = take(n * sf * 16);
+            w.c.scratch = w.f.scratch = take(w.c.scratch_bytes > w.f.scratch_bytes ? w.c.scratch_bytes : w.f.scratch_bytes);
         } else {
-            w.g_raw_c = take(n * nc * 16);
-            w.scratch_c = take(w.scratch_c_bytes);
+            w.c.g_raw = take(n * nc * 16);
+            w.c.scratch = take(w.c.scratch_bytes);
             if (nf > 0) {
-                w.g_raw_f = take(n * sf * 16);
-                w.scratch_f = take(w.scratch_f_bytes);
+                w.f.g_raw = take(n * sf * 16);
+                w.f.scratch = take(w.f.scratch_bytes);
             }
         }
     }
@@ -70,6 +75,85 @@ int check_cfg(nerfhip_plan* pc, nerfhip_plan* pf, const nerfhip_render_cfg* cfg)
     return NERFHIP_OK;
 }
 
+// what the passes of one call share
+struct Call {
+    const nerfhip_render_cfg* cfg;
+    const float* rays;
+    int64_t n;
+    uint64_t seed, ray_offset;
+    char* ws;
+    nerfhip_stream_t stream;
+};
+
+// one net's pass through the pipeline: the coarse and the fine net take the same steps (forward_pass, backward_pass) with these
+struct Pass {
+    nerfhip_plan* plan;
+    const float* packed;
+    NhMlpInput in;        // the rays and the net's depths (the caller of forward_pass has put them into the z region); in.S per ray
+    uint32_t rng_stream;  // of the compositing noise
+    const float* noise;   // ... or the caller's
+    NetSpace w;
+    // the backward's: the net's cotangents, its gradient buffer, its flat parameters (the ray gradient reads them)
+    const float *g_rgb, *g_depth, *g_acc;
+    float* g_params;
+    const float* params;
+};
+
+Pass net_pass(const Call& c, bool fine, nerfhip_plan* plan, const float* packed, const nerfhip_render_rand* rnd, const Workspace& w) {
+    Pass p;
+    memset(&p, 0, sizeof(p));
+    p.plan = plan;
+    p.packed = packed;
+    p.rng_stream = fine ? 3u : 1u;
+    if (rnd) p.noise = fine ? rnd->noise_fine : rnd->noise_coarse;
+    p.w = fine ? w.f : w.c;
+    p.in.mode = 1;
+    p.in.rays = c.rays;
+    p.in.ray_stride = c.cfg->ray_stride;
+    p.in.z = (const float*)(c.ws + p.w.z);
+    p.in.S = c.cfg->num_coarse + (fine ? c.cfg->num_fine : 0);
+    return p;
+}
+
+// MLP over the pass's depths -> compositing.  (a training forward leaves in the stash what the plan's backward will read there:
+// nh_mlp_forward_training)
+int forward_pass(const Call& c, const Pass& p, int training, float* rgb, float* disp, float* acc, float* weights, float* depth) {
+    const int64_t M = c.n * p.in.S;
+    float* raw = (float*)(c.ws + p.w.raw);
+    const int rc = training ? nh_mlp_forward_training(p.plan, p.packed, p.in, M, raw, (float*)(c.ws + p.w.stash), c.stream)
+                            : nh_mlp_forward(p.plan, p.packed, p.in, M, raw, nullptr, c.stream);
+    if (rc) return rc;
+    return nerfhip_volume_render_fwd(raw, p.in.z, c.rays + 3, c.cfg->ray_stride, c.n, p.in.S, c.cfg->noise_std, p.noise, c.seed,
+                                     p.rng_stream, c.ray_offset, c.cfg->white_background, rgb, disp, acc, weights, depth, c.stream);
+}
+
+// compositing backward -> MLP backward (by the plan's data flow, nh_bwd_flow: it is told whether its d(pre-activation) images will
+// be read) -> with g_rays: d(loss)/d(rays) of the pass, overwriting g_rays or accumulating into it: dL/d(encoded input) from the
+// images the MLP backward just left in the scratch (nerfhip_mlp_bwd_input), then the positional encoding's backward and
+// pts = ro + rd * z (nh_ray_grad)
+int backward_pass(const Call& c, const Pass& q, void* tmp, int64_t tmp_bytes, float* g_rays, int accumulate) {
+    nerfhip_plan* p = q.plan;
+    const int64_t M = c.n * q.in.S;
+    float* g_raw = (float*)(c.ws + q.w.g_raw);
+    float* scratch = (float*)(c.ws + q.w.scratch);
+    float* g_norm = g_rays ? (float*)(c.ws + q.w.gnorm) : nullptr;
+    int rc = nh_volume_render_bwd((const float*)(c.ws + q.w.raw), q.in.z, c.rays + 3, c.cfg->ray_stride, c.n, q.in.S, c.cfg->noise_std,
+                                  q.noise, c.seed, q.rng_stream, c.ray_offset, c.cfg->white_background, q.g_rgb, q.g_depth, q.g_acc, nullptr,
+                                  g_raw, g_norm, c.stream);
+    if (rc) return rc;
+    rc = nh_mlp_backward(p, q.packed, &q.in, g_raw, M, (float*)(c.ws + q.w.stash), scratch, q.w.scratch_bytes, q.g_params,
+                         g_rays != nullptr, c.stream);
+    if (rc || !g_rays) return rc;
+    const int64_t need = M * (int64_t)(p->Dx + p->Dd) * 4;
+    NH_REQUIRE(q.params && tmp && tmp_bytes >= need, "render_bwd: the ray gradient needs the flat parameters and %lld bytes of tmp",
+               (long long)need);
+    rc = nerfhip_mlp_bwd_input(p, q.params, M, scratch, (float*)tmp, c.stream);
+    if (rc) return rc;
+    return nh_ray_grad(c.rays, c.cfg->ray_stride, c.n, q.in.z, q.in.S, (const float*)tmp, p->Dx, p->Dd, p->cfg.include_input_xyz ? 1 : 0,
+                       (p->view && p->cfg.include_input_dir) ? 1 : 0, p->cfg.num_encoding_fn_xyz, p->view ? p->cfg.num_encoding_fn_dir : 0,
+                       p->freqs_xyz, p->freqs_dir, g_norm, g_rays, accumulate, c.stream);
+}
+
 }  // namespace
 
 extern "C" int64_t nerfhip_render_workspace_bytes(nerfhip_plan_t plan_coarse, nerfhip_plan_t plan_fine,
@@ -85,25 +169,22 @@ extern "C" int nerfhip_render_workspace_region(nerfhip_plan_t plan_coarse, nerfh
     if (rc) return rc;
     NH_REQUIRE(name && offset && bytes && n_rays >= 0, "render_workspace_region: bad arguments");
     const Workspace w = layout(plan_coarse, plan_fine, cfg, n_rays, training);
-    const int64_t nc = cfg->num_coarse, sf = nc + cfg->num_fine;
-    struct {
-        const char* name;
-        int64_t off, bytes;
-        bool fine;
-    } regions[] = {{"z_coarse", w.z_c, n_rays * nc * 4, false},      {"raw_coarse", w.raw_c, n_rays * nc * 16, false},
-                   {"weights_coarse", w.w_c, n_rays * nc * 4, false}, {"z_fine", w.z_f, n_rays * sf * 4, true},
-                   {"raw_fine", w.raw_f, n_rays * sf * 16, true},
-                   // (training layouts: each net's backward scratch -- nerfhip_plan_bwd_stats_offset points into it)
-                   {"bwd_scratch_coarse", w.scratch_c, w.scratch_c_bytes, false},
-                   {"bwd_scratch_fine", w.scratch_f, w.scratch_f_bytes, true}};
-    for (const auto& r : regions)
-        if (strcmp(name, r.name) == 0) {
-            NH_REQUIRE(!r.fine || cfg->num_fine > 0, "render_workspace_region: %s needs num_fine > 0", name);
-            NH_REQUIRE(training || strncmp(name, "bwd_", 4) != 0, "render_workspace_region: %s exists in a training layout only", name);
-            *offset = r.off;
-            *bytes = r.bytes;
-            return NERFHIP_OK;
-        }
+    // (training layouts: each net's backward scratch -- nerfhip_plan_bwd_stats_offset points into it)
+    static const char* const names[2][4] = {{"z_coarse", "raw_coarse", "weights_coarse", "bwd_scratch_coarse"},
+                                            {"z_fine", "raw_fine", nullptr, "bwd_scratch_fine"}};
+    for (int fine = 0; fine < 2; ++fine) {
+        const NetSpace& s = fine ? w.f : w.c;
+        const int64_t M = n_rays * (cfg->num_coarse + (fine ? cfg->num_fine : 0));
+        const int64_t off[4] = {s.z, s.raw, s.weights, s.scratch}, size[4] = {M * 4, M * 16, M * 4, s.scratch_bytes};
+        for (int i = 0; i < 4; ++i)
+            if (names[fine][i] && strcmp(name, names[fine][i]) == 0) {
+                NH_REQUIRE(!fine || cfg->num_fine > 0, "render_workspace_region: %s needs num_fine > 0", name);
+                NH_REQUIRE(training || strncmp(name, "bwd_", 4) != 0, "render_workspace_region: %s exists in a training layout only", name);
+                *offset = off[i];
+                *bytes = size[i];
+                return NERFHIP_OK;
+            }
+    }
     NH_REQUIRE(false, "render_workspace_region: unknown region '%s'", name);
 }
 
@@ -125,50 +206,27 @@ extern "C" int nerfhip_render_fwd_parts(nerfhip_plan_t pc, nerfhip_plan_t pf, co
     const Workspace w = layout(pc, pf, cfg, n, training);
     NH_REQUIRE(workspace_bytes >= w.total, "render_fwd: workspace too small (%lld < %lld)", (long long)workspace_bytes,
                (long long)w.total);
-    char* ws = (char*)workspace;
-    const int nc = cfg->num_coarse, nf = cfg->num_fine, sf = nc + nf, stride = cfg->ray_stride;
-    nerfhip_render_rand none = {nullptr, nullptr, nullptr, nullptr};
-    const nerfhip_render_rand* r = rnd ? rnd : &none;
-    float* z_c = (float*)(ws + w.z_c);
-    float* raw_c = (float*)(ws + w.raw_c);
-    float* w_c = (float*)(ws + w.w_c);
-
-    NhMlpInput in;
-    memset(&in, 0, sizeof(in));
-    in.mode = 1;
-    in.rays = rays;
-    in.ray_stride = stride;
+    const Call c = {cfg, rays, n, seed, ray_offset, (char*)workspace, stream};
+    float* z_c = (float*)(c.ws + w.c.z);
+    float* w_c = (float*)(c.ws + w.c.weights);
     if (parts & NERFHIP_PART_COARSE) {
-        rc = nerfhip_stratified_z(rays, stride, n, t_vals, nc, cfg->lindisp, cfg->perturb, r->t_rand, seed, ray_offset, z_c,
-                                  stream);
+        rc = nerfhip_stratified_z(rays, cfg->ray_stride, n, t_vals, cfg->num_coarse, cfg->lindisp, cfg->perturb, rnd ? rnd->t_rand : nullptr,
+                                  seed, ray_offset, z_c, stream);
         if (rc) return rc;
-        in.z = z_c;
-        in.S = nc;
-        // (a plan whose backward recomputes the stash for the samples it keeps -- nerfhip_plan_set_bwd_compaction(plan, 2) -- runs the
-        // stash-free forward here)
-        rc = training ? nh_mlp_forward_training(pc, packed_c, in, n * nc, raw_c, (float*)(ws + w.stash_c), stream)
-                      : nh_mlp_forward(pc, packed_c, in, n * nc, raw_c, nullptr, stream);
-        if (rc) return rc;
-        rc = nerfhip_volume_render_fwd(raw_c, z_c, rays + 3, stride, n, nc, cfg->noise_std, r->noise_coarse, seed, 1u,
-                                       ray_offset, cfg->white_background, out->rgb_coarse, out->disp_coarse,
-                                       out->acc_coarse, w_c, out->depth_coarse, stream);
+        rc = forward_pass(c, net_pass(c, false, pc, packed_c, rnd, w), training, out->rgb_coarse, out->disp_coarse, out->acc_coarse, w_c,
+                          out->depth_coarse);
         if (rc) return rc;
     }
-    if (nf > 0 && (parts & NERFHIP_PART_FINE)) {
-        float* z_f = (float*)(ws + w.z_f);
-        float* raw_f = (float*)(ws + w.raw_f);
+    if (cfg->num_fine > 0 && (parts & NERFHIP_PART_FINE)) {
         const int det = cfg->perturb ? 0 : 1;  // det = (perturb == 0.0), nerf/train_utils.py:101
-        NH_REQUIRE(!det || r->u || u_det, "render_fwd: perturb == 0 needs u_det");
-        rc = nerfhip_hierarchical_z(z_c, w_c, n, nc, r->u, det, u_det, nf, seed, ray_offset, nullptr, z_f, stream);
+        const float* u = rnd ? rnd->u : nullptr;
+        NH_REQUIRE(!det || u || u_det, "render_fwd: perturb == 0 needs u_det");
+        rc = nerfhip_hierarchical_z(z_c, w_c, n, cfg->num_coarse, u, det, u_det, cfg->num_fine, seed, ray_offset, nullptr,
+                                    (float*)(c.ws + w.f.z), stream);
         if (rc) return rc;
-        in.z = z_f;
-        in.S = sf;
-        rc = training ? nh_mlp_forward_training(pf, packed_f, in, n * sf, raw_f, (float*)(ws + w.stash_f), stream)
-                      : nh_mlp_forward(pf, packed_f, in, n * sf, raw_f, nullptr, stream);
-        if (rc) return rc;
-        rc = nerfhip_volume_render_fwd(raw_f, z_f, rays + 3, stride, n, sf, cfg->noise_std, r->noise_fine, seed, 3u,
-                                       ray_offset, cfg->white_background, out->rgb_fine, out->disp_fine, out->acc_fine,
-                                       nullptr, out->depth_fine, stream);
+        // (only the coarse compositing writes its weights: the fine depths were drawn from them)
+        rc = forward_pass(c, net_pass(c, true, pf, packed_f, rnd, w), training, out->rgb_fine, out->disp_fine, out->acc_fine, nullptr,
+                          out->depth_fine);
         if (rc) return rc;
     }
     return NERFHIP_OK;
@@ -182,25 +240,6 @@ extern "C" int nerfhip_render_fwd(nerfhip_plan_t pc, nerfhip_plan_t pf, const ne
     return nerfhip_render_fwd_parts(pc, pf, cfg, rays, n, packed_c, packed_f, t_vals, u_det, rnd, seed, ray_offset, out,
                                     workspace, workspace_bytes, training, NERFHIP_PART_COARSE | NERFHIP_PART_FINE, stream);
 }
-
-namespace {
-
-// d(loss)/d(rays) of one net's pass: dL/d(encoded input) from the d(pre-activation) images its backward just left in the
-// scratch (nerfhip_mlp_bwd_input), then the positional encoding's backward and pts = ro + rd * z (nh_ray_grad).
-int ray_grad_of_pass(nerfhip_plan* p, const float* params, const float* rays, int stride, int64_t n, const float* z, int S,
-                     const float* scratch, const float* g_norm, void* tmp, int64_t tmp_bytes, float* g_rays, int accumulate,
-                     nerfhip_stream_t stream) {
-    const int64_t M = n * S, need = M * (int64_t)(p->Dx + p->Dd) * 4;
-    NH_REQUIRE(params && tmp && tmp_bytes >= need, "render_bwd: the ray gradient needs the flat parameters and %lld bytes of tmp",
-               (long long)need);
-    int rc = nerfhip_mlp_bwd_input(p, params, M, scratch, (float*)tmp, stream);
-    if (rc) return rc;
-    return nh_ray_grad(rays, stride, n, z, S, (const float*)tmp, p->Dx, p->Dd, p->cfg.include_input_xyz ? 1 : 0,
-                       (p->view && p->cfg.include_input_dir) ? 1 : 0, p->cfg.num_encoding_fn_xyz,
-                       p->view ? p->cfg.num_encoding_fn_dir : 0, p->freqs_xyz, p->freqs_dir, g_norm, g_rays, accumulate, stream);
-}
-
-}  // namespace
 
 extern "C" int64_t nerfhip_render_bwd_rays_tmp_bytes(nerfhip_plan_t pc, nerfhip_plan_t pf, const nerfhip_render_cfg* cfg,
                                                      int64_t n) {
@@ -228,63 +267,26 @@ extern "C" int nerfhip_render_bwd_rays(nerfhip_plan_t pc, nerfhip_plan_t pf, con
     const Workspace w = layout(pc, pf, cfg, n, shared ? 2 : 1);
     NH_REQUIRE(workspace_bytes >= w.total, "render_bwd: workspace too small (%lld < %lld)", (long long)workspace_bytes,
                (long long)w.total);
-    char* ws = (char*)workspace;
-    const int nc = cfg->num_coarse, nf = cfg->num_fine, sf = nc + nf, stride = cfg->ray_stride;
-    nerfhip_render_rand none = {nullptr, nullptr, nullptr, nullptr};
-    const nerfhip_render_rand* r = rnd ? rnd : &none;
+    const Call c = {cfg, rays, n, seed, ray_offset, (char*)workspace, stream};
     int wrote_rays = 0;  // the first pass that runs overwrites g_rays, the second accumulates
-    if (nf > 0 && (parts & NERFHIP_PART_FINE)) {
+    if (cfg->num_fine > 0 && (parts & NERFHIP_PART_FINE)) {
         NH_REQUIRE(packed_f && g_params_f && (g->g_rgb_fine || g->g_acc_fine || g->g_depth_fine),
                    "render_bwd: fine arguments missing");
-        float* g_raw = (float*)(ws + w.g_raw_f);
-        rc = nh_volume_render_bwd((const float*)(ws + w.raw_f), (const float*)(ws + w.z_f), rays + 3, stride, n, sf,
-                                  cfg->noise_std, r->noise_fine, seed, 3u, ray_offset, cfg->white_background, g->g_rgb_fine,
-                                  g->g_depth_fine, g->g_acc_fine, nullptr, g_raw, g_rays ? (float*)(ws + w.gnorm_f) : nullptr, stream);
+        Pass fine = net_pass(c, true, pf, packed_f, rnd, w);
+        fine.g_rgb = g->g_rgb_fine, fine.g_depth = g->g_depth_fine, fine.g_acc = g->g_acc_fine;
+        fine.g_params = g_params_f, fine.params = params_f;
+        rc = backward_pass(c, fine, tmp, tmp_bytes, g_rays, wrote_rays);
         if (rc) return rc;
-        if (nh_mlp_recomputes(pf, n * sf)) {
-            NhMlpInput in;
-            memset(&in, 0, sizeof(in));
-            in.mode = 1, in.rays = rays, in.ray_stride = stride, in.z = (const float*)(ws + w.z_f), in.S = sf;
-            rc = nh_mlp_backward_recompute(pf, packed_f, in, g_raw, n * sf, (float*)(ws + w.stash_f), (float*)(ws + w.scratch_f),
-                                           w.scratch_f_bytes, g_params_f, g_rays != nullptr, stream);
-        } else {
-            rc = nh_mlp_backward(pf, packed_f, g_raw, n * sf, (const float*)(ws + w.stash_f), (float*)(ws + w.scratch_f),
-                                 w.scratch_f_bytes, g_params_f, stream);
-        }
-        if (rc) return rc;
-        if (g_rays) {
-            rc = ray_grad_of_pass(pf, params_f, rays, stride, n, (const float*)(ws + w.z_f), sf, (const float*)(ws + w.scratch_f),
-                                  (const float*)(ws + w.gnorm_f), tmp, tmp_bytes, g_rays, wrote_rays, stream);
-            if (rc) return rc;
-            wrote_rays = 1;
-        }
+        wrote_rays = g_rays != nullptr;
     }
     if (parts & NERFHIP_PART_COARSE) {
         NH_REQUIRE(g_params_c && (g->g_rgb_coarse || g->g_acc_coarse || g->g_depth_coarse),
                    "render_bwd: coarse arguments missing");
-        float* g_raw = (float*)(ws + w.g_raw_c);
-        rc = nh_volume_render_bwd((const float*)(ws + w.raw_c), (const float*)(ws + w.z_c), rays + 3, stride, n, nc,
-                                  cfg->noise_std, r->noise_coarse, seed, 1u, ray_offset, cfg->white_background, g->g_rgb_coarse,
-                                  g->g_depth_coarse, g->g_acc_coarse, nullptr, g_raw, g_rays ? (float*)(ws + w.gnorm_c) : nullptr,
-                                  stream);
+        Pass coarse = net_pass(c, false, pc, packed_c, rnd, w);
+        coarse.g_rgb = g->g_rgb_coarse, coarse.g_depth = g->g_depth_coarse, coarse.g_acc = g->g_acc_coarse;
+        coarse.g_params = g_params_c, coarse.params = params_c;
+        rc = backward_pass(c, coarse, tmp, tmp_bytes, g_rays, wrote_rays);
         if (rc) return rc;
-        if (nh_mlp_recomputes(pc, n * nc)) {
-            NhMlpInput in;
-            memset(&in, 0, sizeof(in));
-            in.mode = 1, in.rays = rays, in.ray_stride = stride, in.z = (const float*)(ws + w.z_c), in.S = nc;
-            rc = nh_mlp_backward_recompute(pc, packed_c, in, g_raw, n * nc, (float*)(ws + w.stash_c), (float*)(ws + w.scratch_c),
-                                           w.scratch_c_bytes, g_params_c, g_rays != nullptr, stream);
-        } else {
-            rc = nh_mlp_backward(pc, packed_c, g_raw, n * nc, (const float*)(ws + w.stash_c), (float*)(ws + w.scratch_c),
-                                 w.scratch_c_bytes, g_params_c, stream);
-        }
-        if (rc) return rc;
-        if (g_rays) {
-            rc = ray_grad_of_pass(pc, params_c, rays, stride, n, (const float*)(ws + w.z_c), nc, (const float*)(ws + w.scratch_c),
-                                  (const float*)(ws + w.gnorm_c), tmp, tmp_bytes, g_rays, wrote_rays, stream);
-            if (rc) return rc;
-            wrote_rays = 1;
-        }
     }
     return NERFHIP_OK;
 }

@@ -2,6 +2,8 @@
 // sequences  forward = k_mlp_fwd16 (mlp16.hip),  backward = k_mlp_dgrad16 (mlp16.hip) -> k_wgrad -> k_wgrad_reduce
 // (wgrad.hip), and the C-ABI entry points nerfhip_mlp_fwd / nerfhip_mlp_bwd; plus the gradient w.r.t. the encoded input
 // (nerfhip_mlp_bwd_input: off the hot path -- the render path never differentiates its encodings).
+// Which of those sequences a plan's backward is (compacted, recomputing, the fused kernel of mlp64r.hip) and what its training forward
+// leaves in the stash for it: nh_bwd_flow, below -- the training forward, the backward and the input gradient all ask it.
 #include <stdlib.h>
 
 #include "nh_mlp.h"
@@ -82,13 +84,37 @@ int64_t nh_mlp_bwd_scratch_bytes(nerfhip_plan* p, int64_t M) {
     const int64_t nt = nh_ceil_div(M, 128) * 4;
     return (fused_partial_offset(p, nt) + nh_mlp64r_partial_floats(p, M)) * (int64_t)sizeof(float);
 }
-// A backward over M sample points runs compacted when the plan asks for it and a gathered row's byte offset inside a region (at most
-// 256 rows of 4 bytes per sample) fits the 32-bit offset of a buffer instruction; otherwise it runs dense.
-// (the fused modes 3 / 4 leave no d(pre-activation) images: whoever needs them -- the ray gradient, nerfhip_mlp_bwd with a stash of its
-// caller -- gets mode 2's data flow)
-static int image_mode(const nerfhip_plan* p) { return p->bwd_compact >= 3 ? 2 : p->bwd_compact; }
-static bool compacts(const nerfhip_plan* p, int64_t M) { return image_mode(p) != 0 && nh_ceil_div(M, 128) * 128 * 1024 < ((int64_t)1 << 32); }
-bool nh_mlp_recomputes(const nerfhip_plan* p, int64_t M) { return image_mode(p) == 2 && compacts(p, M) && nh_prec_level(p->precision) != 1; }
+// THE data flow of a backward over M sample points of this plan, and with it what the training forward must leave in the stash: the
+// one reader of the plan's option (nerfhip_plan_set_bwd_compaction) besides its setter and getter.
+//
+//   mode | training forward leaves in `stash` | backward                                            | ... if the images are needed
+//   -----+------------------------------------+-----------------------------------------------------+-----------------------------
+//    0   | the general stash                  | three kernels (dgrad, wgrad, reduce), every sample  | the same
+//    1   | the general stash                  | sample list; three kernels over the list            | the same
+//    2   | nothing                            | sample list; forward over the list -> `stash` in    | the same
+//        |                                    | list order; three kernels over the list             |
+//    3   | nothing                            | the fused kernel (mlp64r.hip), every sample,        | as mode 2
+//        |                                    | recomputing the forward                             |
+//    4   | nothing                            | sample list; the fused kernel over the list         | as mode 2
+//    5   | the register-image stash (nh_r64.h)| the fused kernel over that stash, every sample      | as mode 2
+//
+// "the images": the d(pre-activation) images in the scratch, which the fused kernel does not write; the ray gradient
+// (nerfhip_mlp_bwd_input) reads them afterwards.  Rows 2 .. 5 hold inside the fused render only (in_render: the backward is handed the
+// forward's input again and owns the stash); a backward over a stash of its caller (nerfhip_mlp_bwd) runs them as row 1.
+// Every row falls back to row 0 when a gathered row's byte offset inside a region (at most 256 rows of 4 bytes per sample) does not
+// fit the 32-bit offset of a buffer instruction; rows 2 .. 5 to row 1 for an inference-only plan (which has no backward at all);
+// rows 3 .. 5 need the resident image (the setter sees to it), row 5 a register-image stash that fits (else it runs as row 3).
+NhBwdFlow nh_bwd_flow(const nerfhip_plan* p, int64_t M, bool in_render, bool need_images) {
+    const int m = p->bwd_compact;
+    const bool fits = nh_ceil_div(M, 128) * 128 * 1024 < ((int64_t)1 << 32);
+    const bool resident = p->r64_off >= 0;
+    NhBwdFlow f;
+    f.recompute = in_render && m >= 2 && fits && nh_prec_level(p->precision) != 1;
+    f.reg_image = f.recompute && m == 5 && resident && nh_r64_stash_fits(p);
+    f.fused = f.recompute && m >= 3 && resident && !need_images;
+    f.list = f.fused ? m == 4 : m != 0 && fits;
+    return f;
+}
 
 static int mlp_forward_any(nerfhip_plan* p, const float* packed, const NhMlpInput& in, int64_t M, float* out, float* stash,
                            nerfhip_stream_t stream, const NhCompact* list);
@@ -119,56 +145,43 @@ static int mlp_forward_any(nerfhip_plan* p, const float* packed, const NhMlpInpu
     return nh_mlp16_forward(p, packed, in, M, out, stash, stream, list);
 }
 
-// mode 5 inside the fused render: fp32 plan with a resident image whose register-image stash fits the plan's stash region
-static bool fused_stashed(const nerfhip_plan* p, int64_t M) {
-    return p->bwd_compact == 5 && p->r64_off >= 0 && nh_r64_stash_fits(p) && nh_mlp_recomputes(p, M);
-}
-
 int nh_mlp_forward_training(nerfhip_plan* p, const float* packed, const NhMlpInput& in, int64_t M, float* out, float* stash,
                             nerfhip_stream_t stream) {
     NH_REQUIRE(p && out && stash, "mlp_fwd: bad arguments");
-    if (M > 0 && fused_stashed(p, M)) return nh_mlp64r_forward(p, packed, in, M, out, stash, stream);
-    return mlp_forward_any(p, packed, in, M, out, nh_mlp_recomputes(p, M) ? nullptr : stash, stream, nullptr);
+    const NhBwdFlow f = nh_bwd_flow(p, M, true, false);  // (what it leaves does not depend on need_images)
+    if (M > 0 && f.reg_image) return nh_mlp64r_forward(p, packed, in, M, out, stash, stream);
+    return mlp_forward_any(p, packed, in, M, out, f.recompute ? nullptr : stash, stream, nullptr);
 }
 
-// `recompute`: the forward of this launch wrote no stash (nh_mlp_recomputes); `in` names its input again
-static int mlp_backward_any(nerfhip_plan* p, const float* packed, const NhMlpInput* recompute, const float* g_out, int64_t M, float* stash,
-                            float* scratch, int64_t scratch_bytes, float* g_params, bool need_images, nerfhip_stream_t stream) {
+int nh_mlp_backward(nerfhip_plan* p, const float* packed, const NhMlpInput* in, const float* g_out, int64_t M, float* stash,
+                    float* scratch, int64_t scratch_bytes, float* g_params, bool need_images, nerfhip_stream_t stream) {
     NH_REQUIRE(p && packed && g_out && stash && scratch && g_params && M > 0, "mlp_bwd: bad arguments");
     NH_REQUIRE(nh_prec_level(p->precision) != 1, "mlp_bwd: an f16x3 plan is inference-only");
     NH_REQUIRE(scratch_bytes >= nh_mlp_bwd_scratch_bytes(p, M), "mlp_bwd: scratch too small (%lld < %lld)",
                (long long)scratch_bytes, (long long)nh_mlp_bwd_scratch_bytes(p, M));
+    const NhBwdFlow f = nh_bwd_flow(p, M, in != nullptr, need_images);
     const int64_t nt = nh_ceil_div(M, 128) * 4;
     const bool bdg = nh_prec_level(p->precision) >= 3;
     int rc = NERFHIP_OK;
-    if (recompute && p->bwd_compact >= 3 && p->r64_off >= 0 && !need_images) {
-        // the fused backward (mlp64r.hip): forward recomputed, data gradient and weight gradient in one kernel; mode 4 walks the list
-        if (fused_stashed(p, M))  // mode 5: the forward left the register-image stash; nothing is recomputed, every sample is walked
-            return nh_mlp64r_backward(p, packed, *recompute, g_out, M, scratch + fused_partial_offset(p, nt), g_params, nullptr, stash, stream);
-        NhCompact lview;
-        const NhCompact* lx = nullptr;
-        if (p->bwd_compact == 4) {
-            lview = nh_compact_view((int*)(scratch + compact_word_offset(p, nt)), nt * 32);
-            rc = nh_compact_build(g_out, M, lview, stream);
-            if (rc) return rc;
-            lx = &lview;
-        }
-        return nh_mlp64r_backward(p, packed, *recompute, g_out, M, scratch + fused_partial_offset(p, nt), g_params, lx, nullptr, stream);
-    }
     // compacted backward: list the samples whose d(raw output) row is not all zero; every kernel below then walks that list
     NhCompact cview;
     const NhCompact* cx = nullptr;
-    if (compacts(p, M)) {
+    if (f.list) {
         cview = nh_compact_view((int*)(scratch + compact_word_offset(p, nt)), nt * 32);
         rc = nh_compact_build(g_out, M, cview, stream);
         if (rc) return rc;
         cx = &cview;
     }
-    if (recompute) {
+    // the fused backward (mlp64r.hip): data gradient and weight gradient in one kernel, over the forward's register-image stash or
+    // recomputing the forward
+    if (f.fused)
+        return nh_mlp64r_backward(p, packed, *in, g_out, M, scratch + fused_partial_offset(p, nt), g_params, cx,
+                                  f.reg_image ? stash : nullptr, stream);
+    if (f.recompute) {
         // ... and the forward is run again for the listed samples only: their activation rows and ReLU masks, in list order (the
         // fp16-piece forward also records the stash's region maxima again, behind the stash as every training forward does)
         NH_REQUIRE(cx, "mlp_bwd: a recomputing backward needs the compacted list");
-        rc = mlp_forward_any(p, packed, *recompute, M, nullptr, stash, stream, cx);
+        rc = mlp_forward_any(p, packed, *in, M, nullptr, stash, stream, cx);
         if (rc) return rc;
         cview.stash_in_list_order = true;
     }
@@ -193,16 +206,6 @@ static int mlp_backward_any(nerfhip_plan* p, const float* packed, const NhMlpInp
     // (level 4: the large blocks, behind the fp32 kernel's partials)
     float* const partial_b = partial + nh_wgrad_partial_floats(p, nt);
     return nh_wgrad_f16(p, nt, stash, scratch, partial_b, g_params, amax, bmax, cx, stream);
-}
-
-int nh_mlp_backward(nerfhip_plan* p, const float* packed, const float* g_out, int64_t M, const float* stash,
-                    float* scratch, int64_t scratch_bytes, float* g_params, nerfhip_stream_t stream) {
-    return mlp_backward_any(p, packed, nullptr, g_out, M, (float*)stash, scratch, scratch_bytes, g_params, true, stream);
-}
-
-int nh_mlp_backward_recompute(nerfhip_plan* p, const float* packed, const NhMlpInput& in, const float* g_out, int64_t M, float* stash,
-                              float* scratch, int64_t scratch_bytes, float* g_params, bool need_images, nerfhip_stream_t stream) {
-    return mlp_backward_any(p, packed, &in, g_out, M, stash, scratch, scratch_bytes, g_params, need_images, stream);
 }
 
 extern "C" int nerfhip_plan_set_bwd_compaction(nerfhip_plan_t plan, int on) {
@@ -244,7 +247,8 @@ extern "C" int nerfhip_mlp_fwd(nerfhip_plan_t plan, const float* packed, const f
 extern "C" int nerfhip_mlp_bwd(nerfhip_plan_t plan, const float* packed, const float* g_out, int64_t m,
                                const void* stash, void* scratch, int64_t scratch_bytes, float* g_params,
                                nerfhip_stream_t stream) {
-    return nh_mlp_backward(plan, packed, g_out, m, (const float*)stash, (float*)scratch, scratch_bytes, g_params, stream);
+    // (the stash is its caller's: no input to recompute from; the d(pre-activation) images are part of what it returns)
+    return nh_mlp_backward(plan, packed, nullptr, g_out, m, (float*)const_cast<void*>(stash), (float*)scratch, scratch_bytes, g_params, true, stream);
 }
 
 extern "C" int nerfhip_mlp_bwd_input(nerfhip_plan_t p, const float* params, int64_t m, const void* scratch, float* g_x,
@@ -278,7 +282,7 @@ extern "C" int nerfhip_mlp_bwd_input(nerfhip_plan_t p, const float* params, int6
     a.D = p->Dx + p->Dd;
     a.g_x = g_x;
     a.gscale = nullptr;  // (the d(pre-activation) images are plain values in every precision)
-    if (compacts(p, m)) {  // (the backward that filled `scratch` ran compacted: its images are in list order)
+    if (nh_bwd_flow(p, m, false, true).list) {  // (the backward that filled `scratch` ran compacted: its images are in list order)
         const NhCompact c = nh_compact_view((int*)const_cast<void*>(scratch) + compact_word_offset(p, a.nt), a.nt * 32);
         a.cidx = c.idx;
         a.cstats = c.stats;

@@ -415,7 +415,7 @@ struct Fwd16Args {
     float* stash;
     NhStashLayout sl;
     unsigned long long* clk;  // shader-clock probe counters, or NULL (nh_prof_clock_slot)
-    // a forward over a compaction list (the recomputing backward, mlp.hip nh_mlp_backward_recompute), or NULLs: slot c of the launch
+    // a forward over a compaction list (the recomputing backward, mlp.hip nh_mlp_backward), or NULLs: slot c of the launch
     // computes sample cidx[c] and writes that sample's stash rows and ReLU masks AT SLOT c; cstats[NH_CSTAT_ACTIVE] slots carry a
     // sample; `out` may be NULL
     const int* cidx;
@@ -754,21 +754,6 @@ NH_KERNEL void NH_LB(64 * Shape<W>::NW, Shape<W>::WAVES_PER_SIMD) k_mlp_dgrad16(
 #endif
 }
 
-template <class K>
-int lds_limit(K kern, int bytes) {
-#ifndef NERFHIP_EMU
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) {
-        nh_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize=%d): %s", bytes, hipGetErrorString(e));
-        return NERFHIP_ERR_LAUNCH;
-    }
-#else
-    (void)kern;
-    (void)bytes;
-#endif
-    return NERFHIP_OK;
-}
-
 }  // namespace
 
 #if defined(NH_PHASE_TIMING) && !defined(NH16_W512_TU) && !defined(NH16_EXT_TU)
@@ -848,7 +833,7 @@ void fill_dgrad_args(nerfhip_plan* p, const float* packed, const float* g_out, i
 // whole 128-sample groups are launched: every stash tile is written
 #define NH_FWD16_T(WW, VV, TT, EE)                                                                                    \
     {                                                                                                                 \
-        rc = lds_limit(k_mlp_fwd16<WW, VV, TT, EE>, Lds<WW>::BYTES_ALL);                                              \
+        rc = nh_lds_limit(k_mlp_fwd16<WW, VV, TT, EE>, Lds<WW>::BYTES_ALL);                                           \
         if (rc) return rc;                                                                                            \
         NH_LAUNCH((k_mlp_fwd16<WW, VV, TT, EE>), groups * (8 / Shape<WW>::NW), 64 * Shape<WW>::NW, Lds<WW>::BYTES_ALL, stream, a); \
     }
@@ -862,7 +847,7 @@ void fill_dgrad_args(nerfhip_plan* p, const float* packed, const float* g_out, i
 #define NH_FWD16(WW, VV) NH_FWD16_E(WW, VV, false)
 #define NH_BWD16(WW, VV)                                                                                              \
     {                                                                                                                 \
-        rc = lds_limit(k_mlp_dgrad16<WW, VV>, Lds<WW>::BYTES_ALL);                                                    \
+        rc = nh_lds_limit(k_mlp_dgrad16<WW, VV>, Lds<WW>::BYTES_ALL);                                                 \
         if (rc) return rc;                                                                                            \
         NH_LAUNCH((k_mlp_dgrad16<WW, VV>), groups * (8 / Shape<WW>::NW), 64 * Shape<WW>::NW, Lds<WW>::BYTES_ALL, stream, d); \
     }

@@ -856,47 +856,16 @@ NH_KERNEL void k_bwd64r_reduce(Red64rArgs a) {
     if (dst >= 0) a.g_params[dst] = (part[0][fl] + part[0][fl + 16]) + (part[0][fl + 32] + part[0][fl + 48]);
 }
 
-int compute_units() {
-#ifndef NERFHIP_EMU
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-            cus = v;
-        else
-            cus = 256;
-    }
-    return cus;
-#else
-    return 3;  // (the CPU suite walks the persistent loop)
-#endif
-}
-
-template <class K>
-int lds_limit(K kern, int bytes) {
-#ifndef NERFHIP_EMU
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) {
-        nh_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize=%d): %s", bytes, hipGetErrorString(e));
-        return NERFHIP_ERR_LAUNCH;
-    }
-#else
-    (void)kern;
-    (void)bytes;
-#endif
-    return NERFHIP_OK;
-}
-
 template <int L>
 int launch_bwd(const Bwd64rArgs& a, int grid, nerfhip_stream_t stream) {
     const int bytes = (r64_lds_floats(L) + 32) * 4 + NH_CLK_LDS_BYTES;
     if (a.stash) {
-        const int rc = lds_limit(k_bwd64r<L, true>, bytes);
+        const int rc = nh_lds_limit(k_bwd64r<L, true>, bytes);
         if (rc) return rc;
         NH_LAUNCH((k_bwd64r<L, true>), grid, 64 * NWV, bytes, stream, a);
         return nh_launch_status("bwd64r (stashed)");
     }
-    const int rc = lds_limit(k_bwd64r<L, false>, bytes);
+    const int rc = nh_lds_limit(k_bwd64r<L, false>, bytes);
     if (rc) return rc;
     NH_LAUNCH((k_bwd64r<L, false>), grid, 64 * NWV, bytes, stream, a);
     return nh_launch_status("bwd64r");
@@ -919,12 +888,12 @@ template <int L>
 static int launch_fwd(const Fwd64rArgs& a, int grid, nerfhip_stream_t stream) {
     const int bytes = (r64_layout(L).image_floats + 32) * 4 + NH_CLK_LDS_BYTES;
     if (a.stash) {
-        const int rc = lds_limit(k_fwd64r<L, true>, bytes);
+        const int rc = nh_lds_limit(k_fwd64r<L, true>, bytes);
         if (rc) return rc;
         NH_LAUNCH((k_fwd64r<L, true>), grid, 64 * NWF, bytes, stream, a);
         return nh_launch_status("fwd64r (stashing)");
     }
-    const int rc = lds_limit(k_fwd64r<L, false>, bytes);
+    const int rc = nh_lds_limit(k_fwd64r<L, false>, bytes);
     if (rc) return rc;
     NH_LAUNCH((k_fwd64r<L, false>), grid, 64 * NWF, bytes, stream, a);
     return nh_launch_status("fwd64r");
@@ -965,7 +934,7 @@ int nh_mlp64r_forward(nerfhip_plan* p, const float* packed, const NhMlpInput& in
     a.stash = stash;
     a.clk = nh_prof_clock_slot(NH_CLK_FWD);
     const int64_t wgs = nh_ceil_div(nh_ceil_div(M, 16), NWF);
-    const int cus = compute_units();
+    const int cus = nh_compute_units();
     const int grid = (int)(wgs < cus ? wgs : cus);
     switch (p->L) {
         case 1: return launch_fwd<1>(a, grid, stream);
@@ -978,7 +947,7 @@ int nh_mlp64r_forward(nerfhip_plan* p, const float* packed, const NhMlpInput& in
 // workgroups of a fused backward over M sample points: one per compute unit, at most one per round
 static int r64_grid(int64_t M) {
     const int64_t rounds = nh_ceil_div(M, 16 * R64_TILES);
-    const int cus = compute_units();
+    const int cus = nh_compute_units();
     return (int)(rounds < cus ? (rounds < 1 ? 1 : rounds) : cus);
 }
 

@@ -822,38 +822,6 @@ NH_KERNEL void NH_LB(512, 2) k_mlp_dgrad_f16x3w(DgradWArgs a) {
     regions_end(cx, a.rmax);
 }
 
-// compute units of the current device (the emulator: 3, so that the CPU suite walks the persistent loop)
-int w_compute_units() {
-#ifndef NERFHIP_EMU
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-            cus = v;
-        else
-            cus = 256;
-    }
-    return cus;
-#else
-    return 3;
-#endif
-}
-
-template <class K>
-int w_lds_limit(K kern, int bytes) {
-#ifndef NERFHIP_EMU
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) {
-        nh_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize=%d): %s", bytes, hipGetErrorString(e));
-        return NERFHIP_ERR_LAUNCH;
-    }
-#else
-    (void)kern;
-    (void)bytes;
-#endif
-    return NERFHIP_OK;
-}
-
 }  // namespace
 
 int nh_mlp_forward_f16w(nerfhip_plan* p, const float* packed, const NhMlpInput& in, int64_t M, float* out, float* stash,
@@ -900,12 +868,12 @@ int nh_mlp_forward_f16w(nerfhip_plan* p, const float* packed, const NhMlpInput& 
     const int64_t groups = nh_ceil_div(M, 128);
     a.groups = groups;
     // as many workgroups as are resident at once: one 8-wave workgroup per CU (256-wide nets: its LDS; 128-wide: its 173-202 VGPRs)
-    const int64_t resident = (int64_t)w_compute_units();
+    const int64_t resident = (int64_t)nh_compute_units();
     const int64_t grid = groups < resident ? groups : resident;
     int rc = NERFHIP_OK;
 #define NH_FWDW_T(WW, VV, TT)                                                                                     \
     {                                                                                                             \
-        rc = w_lds_limit(k_mlp_fwd_f16x3w<WW, VV, TT>, WShape<WW>::LDS_BYTES + RM_LDS);                             \
+        rc = nh_lds_limit(k_mlp_fwd_f16x3w<WW, VV, TT>, WShape<WW>::LDS_BYTES + RM_LDS);                            \
         if (rc) return rc;                                                                                        \
         NH_LAUNCH_NAMED("k_mlp_fwd_f16x3w<" #WW ", " #VV ", " #TT ">", (k_mlp_fwd_f16x3w<WW, VV, TT>), grid, 512,      \
                         WShape<WW>::LDS_BYTES + RM_LDS, stream, a);                                               \
@@ -953,12 +921,12 @@ int nh_mlp_dgrad_f16w(nerfhip_plan* p, const float* packed, const float* g_out, 
     d.cidx = cpt ? cpt->idx : nullptr;
     d.cstats = cpt ? cpt->stats : nullptr;
     d.cstash_listed = (cpt && cpt->stash_in_list_order) ? 1 : 0;
-    const int64_t resident = (int64_t)w_compute_units();
+    const int64_t resident = (int64_t)nh_compute_units();
     const int64_t grid = d.groups < resident ? d.groups : resident;
     int rc = NERFHIP_OK;
 #define NH_BWDW(WW, VV)                                                                                           \
     {                                                                                                             \
-        rc = w_lds_limit(k_mlp_dgrad_f16x3w<WW, VV>, WShape<WW>::LDS_BYTES + RM_LDS);                               \
+        rc = nh_lds_limit(k_mlp_dgrad_f16x3w<WW, VV>, WShape<WW>::LDS_BYTES + RM_LDS);                              \
         if (rc) return rc;                                                                                        \
         NH_LAUNCH_NAMED("k_mlp_dgrad_f16x3w<" #WW ", " #VV ">", (k_mlp_dgrad_f16x3w<WW, VV>), grid, 512,               \
                         WShape<WW>::LDS_BYTES + RM_LDS, stream, d);                                               \

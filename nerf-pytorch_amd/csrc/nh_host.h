@@ -55,3 +55,36 @@ static inline int nh_launch_status(const char* what) {
 #endif
 
 static inline int64_t nh_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// compute units of the current device (the emulator: 3, so that the CPU suite walks the persistent loops)
+static inline int nh_compute_units() {
+#ifndef NERFHIP_EMU
+    static int cus = 0;
+    if (cus == 0) {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
+            cus = v;
+        else
+            cus = 256;
+    }
+    return cus;
+#else
+    return 3;
+#endif
+}
+
+// raises the dynamic-LDS limit of `kern` to `bytes` (the MLP and weight-gradient kernels use most of a CU's 160 KB)
+template <class K>
+static inline int nh_lds_limit(K kern, int bytes) {
+#ifndef NERFHIP_EMU
+    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) {
+        nh_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize=%d): %s", bytes, hipGetErrorString(e));
+        return NERFHIP_ERR_LAUNCH;
+    }
+#else
+    (void)kern;
+    (void)bytes;
+#endif
+    return NERFHIP_OK;
+}

@@ -21,7 +21,7 @@ struct NhCompact {
     int* stats;
     int* counts;  // per 2048-sample block (k_compact_count)
     int* idx;
-    // the stash the backward kernels read is ITSELF in list order (written by a forward over the list: nh_mlp_backward_recompute):
+    // the stash the backward kernels read is ITSELF in list order (written by a forward over the list: nh_mlp_backward, recomputing):
     // ReLU masks and activation rows of slot c sit at slot c -- nothing is gathered but d(raw output)
     bool stash_in_list_order;
 };
@@ -31,21 +31,26 @@ int nh_compact_build(const float* g_out, int64_t M, const NhCompact& c, nerfhip_
 
 int nh_mlp_forward(nerfhip_plan* p, const float* packed, const NhMlpInput& in, int64_t M, float* out, float* stash,
                    nerfhip_stream_t stream);
-// the training forward of the fused render: writes into `stash` what THIS plan's backward mode will read there -- the general stash
-// (modes 0, 1), nothing (the recomputing modes 2, 3, 4), the register-image stash of the stashed fused backward (mode 5)
+// What a backward over M sample points of a plan does, and so what its training forward leaves in the stash: resolved in ONE place,
+// nh_bwd_flow (mlp.hip; the table of the six modes of nerfhip_plan_set_bwd_compaction is its comment).
+struct NhBwdFlow {
+    bool list;       // the backward builds the sample list (NhCompact) and its kernels walk it; the d(pre-activation) images are in list order
+    bool recompute;  // the training forward leaves no general stash: the backward works from the forward's input
+    bool fused;      // the backward is the one kernel of mlp64r.hip (no d(pre-activation) images); else dgrad -> wgrad -> reduce
+    bool reg_image;  // the training forward leaves the register-image stash of nh_r64.h, which the fused backward reads
+};
+// in_render: the backward gets the forward's input again and owns the stash (the fused render); need_images: someone reads the
+// d(pre-activation) images afterwards (the ray gradient, a caller of nerfhip_mlp_bwd).  recompute / reg_image depend on neither the
+// images nor the cotangents: the training forward asks with need_images = false.
+NhBwdFlow nh_bwd_flow(const nerfhip_plan* p, int64_t M, bool in_render, bool need_images);
+// the training forward of the fused render: writes into `stash` what nh_bwd_flow says THIS plan's backward will read there
 int nh_mlp_forward_training(nerfhip_plan* p, const float* packed, const NhMlpInput& in, int64_t M, float* out, float* stash,
                             nerfhip_stream_t stream);
-int nh_mlp_backward(nerfhip_plan* p, const float* packed, const float* g_out, int64_t M, const float* stash,
-                    float* scratch, int64_t scratch_bytes, float* g_params, nerfhip_stream_t stream);
-// plans with bwd_compact == 2 inside the fused render: the forward over `in` wrote no stash; lists the samples with a non-zero
-// d(raw output) row, re-runs the forward for them (writing `stash` in list order) and differentiates those
-// need_images: the caller reads the d(pre-activation) images afterwards (the ray gradient): a plan in a fused mode (3 / 4: mlp64r.hip
-// leaves none) then runs as mode 2
-int nh_mlp_backward_recompute(nerfhip_plan* p, const float* packed, const NhMlpInput& in, const float* g_out, int64_t M, float* stash,
-                              float* scratch, int64_t scratch_bytes, float* g_params, bool need_images, nerfhip_stream_t stream);
+// the backward, by nh_bwd_flow.  in: the input of the forward of this launch (nh_mlp_forward_training; `stash` and `scratch` are the
+// render's own), or NULL: `stash` is the caller's general stash and is only read
+int nh_mlp_backward(nerfhip_plan* p, const float* packed, const NhMlpInput* in, const float* g_out, int64_t M, float* stash,
+                    float* scratch, int64_t scratch_bytes, float* g_params, bool need_images, nerfhip_stream_t stream);
 int64_t nh_mlp_bwd_scratch_bytes(nerfhip_plan* p, int64_t M);
-// a backward over M sample points of this plan re-runs its forward (bwd_compact == 2 and the launch compacts at all)
-bool nh_mlp_recomputes(const nerfhip_plan* p, int64_t M);
 
 // mlp16.hip: the forward / data-gradient chain on v_mfma_f32_16x16x4_f32, two waves per SIMD
 // (list: a forward over the samples of a compaction list only -- slot c computes sample idx[c] and writes ITS stash rows / masks at

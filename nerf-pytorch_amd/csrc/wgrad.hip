@@ -836,13 +836,8 @@ void wgrad_schedule(const nerfhip_plan* p, int64_t nt, WgradArgs& w, ReduceArgs*
 
 template <class MD>
 int launch_wgrad(const WgradArgs& w, const char* name, nerfhip_stream_t stream) {
-#ifndef NERFHIP_EMU
-    hipError_t e = hipFuncSetAttribute((const void*)k_wgrad<MD>, hipFuncAttributeMaxDynamicSharedMemorySize, MD::LDS_BYTES);
-    if (e != hipSuccess) {
-        nh_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize=%d): %s", MD::LDS_BYTES, hipGetErrorString(e));
-        return NERFHIP_ERR_LAUNCH;
-    }
-#endif
+    const int rc = nh_lds_limit(k_wgrad<MD>, MD::LDS_BYTES);
+    if (rc) return rc;
     NH_LAUNCH_NAMED(name, (k_wgrad<MD>), w.total_wgs, 64 * MD::NWV, MD::LDS_BYTES, stream, w);
     return nh_launch_status("wgrad");
 }

@@ -466,21 +466,6 @@ NH_KERNEL void k_wgrad_reduce_f16x3(WgBArgs a) {
     }
 }
 
-template <class K>
-int w_lds_limit(K kern, int bytes) {
-#ifndef NERFHIP_EMU
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) {
-        nh_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize=%d): %s", bytes, hipGetErrorString(e));
-        return NERFHIP_ERR_LAUNCH;
-    }
-#else
-    (void)kern;
-    (void)bytes;
-#endif
-    return NERFHIP_OK;
-}
-
 // workgroups per launch, dealt evenly to its blocks: whole rounds of one workgroup per CU.  Blocks of one shape -- rows of the A
 // region, rows of a guest's side region -- share a launch (the kernel is a template over them): the full-height blocks without a
 // guest get NHW_WGS workgroups between them, every other block NHW_WGS_HALF of its own (a launch with fewer workgroups than CUs
@@ -587,13 +572,13 @@ int launch(WgBArgs& w, nerfhip_stream_t stream) {
     const int wgs = w.jobs[w.njobs - 1].wg0 + w.jobs[w.njobs - 1].nwg;
     int rc = NERFHIP_OK;
     if (w.cstats) {
-        rc = w_lds_limit(k_wgrad_f16x3<AR, BR, SA, SB, true>, S::LDS_BYTES);
+        rc = nh_lds_limit(k_wgrad_f16x3<AR, BR, SA, SB, true>, S::LDS_BYTES);
         if (rc) return rc;
         NH_LAUNCH_NAMED(AR == BR ? (SA || SB ? "k_wgrad_f16x3<full+side, compacted>" : "k_wgrad_f16x3<full, compacted>")
                                  : (SA || SB ? "k_wgrad_f16x3<half+side, compacted>" : "k_wgrad_f16x3<half, compacted>"),
                         (k_wgrad_f16x3<AR, BR, SA, SB, true>), wgs, NHW_THREADS, (S::LDS_BYTES), stream, w);
     } else {
-        rc = w_lds_limit(k_wgrad_f16x3<AR, BR, SA, SB>, S::LDS_BYTES);
+        rc = nh_lds_limit(k_wgrad_f16x3<AR, BR, SA, SB>, S::LDS_BYTES);
         if (rc) return rc;
         NH_LAUNCH_NAMED(AR == BR ? (SA || SB ? "k_wgrad_f16x3<full+side>" : "k_wgrad_f16x3<full>")
                                  : (SA || SB ? "k_wgrad_f16x3<half+side>" : "k_wgrad_f16x3<half>"),
