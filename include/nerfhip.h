@@ -468,6 +468,34 @@ int nerfhip_select_rays_bwd(const nerfhip_select_cfg* cfg, const float* c2w, int
                             const float* g_rays, const float* g_rays_2, int g_rays_stride, void* tmp, int64_t tmp_bytes,
                             float* g_c2w, nerfhip_stream_t stream);
 
+/* ---- one batch over a stack of views (batching across the image set; refining all cameras of a capture at once) --------
+ * The image branch of nerfhip_select_rays over the population num_views * H * W: global index g addresses view
+ * v = g / (H * W) and the reference's flat select index k = g % (H * W) of that view (row k % height, col k / height, as
+ * above).  poses: dev, the pose of view v starts at poses + v * pose_view_stride floats, row-major with row stride
+ * pose_ld >= 4 (a contiguous [V, 4, 4] or [V, 3, 4] table, or a strided slice of a larger one; pose_view_stride >=
+ * 2 * pose_ld + 4 when num_views > 1); images: dev [V, H, W, channels] or NULL.  Height, width, focal, near / far, NDC and
+ * viewdirs come from cfg and are shared by all views.  select_inds: dev int64 [n] global indices in [0, V * H * W), or NULL:
+ * positions cfg->first .. + n - 1 of the keyed permutation of [0, V * H * W) (ranks take disjoint slices, as above).
+ * Row i equals, bit for bit, the row nerfhip_select_rays writes for (poses[v], images[v], select_inds = {k}); with
+ * num_views == 1 the whole call equals nerfhip_select_rays.  Limits: 1 <= num_views <= NERFHIP_MAX_VIEWS,
+ * num_views * H * W <= 2^32.  One launch. */
+#define NERFHIP_MAX_VIEWS 65536
+int nerfhip_select_rays_views(const nerfhip_select_cfg* cfg, int num_views, const float* poses, int64_t pose_view_stride,
+                              int pose_ld, const float* images, const int64_t* select_inds, int64_t n, float* rays,
+                              float* target, int64_t* inds_out, nerfhip_stream_t stream);
+/* Its VJP w.r.t. the poses.  inds: dev int64 [n], the inds_out of the forward; g_rays / g_rays_2 / g_rays_stride: as for
+ * nerfhip_select_rays_bwd; g_poses: dev float [V][3][4], written completely (a view without a ray in the batch, and n == 0:
+ * exact zeros).  g_poses[v] is bit-identical to what nerfhip_select_rays_bwd returns for pose v when handed only the rays
+ * of view v in ascending batch position: the rays are grouped by view with integer work only (a stable counting sort) and
+ * each view is summed along the single-view tree with n = n_v.  No floating-point atomics; the result depends on the rays'
+ * view assignment and values only.  tmp: dev scratch of nerfhip_pose_grad_views_tmp_bytes(n, num_views) bytes (0 for
+ * n == 0; -1 for n < 0, n >= 2^31 or num_views outside 1 .. NERFHIP_MAX_VIEWS).  Three launches on `stream` (one for
+ * n == 0), their grids functions of (n, num_views) only. */
+int64_t nerfhip_pose_grad_views_tmp_bytes(int64_t n, int num_views);
+int nerfhip_select_rays_views_bwd(const nerfhip_select_cfg* cfg, int num_views, const float* poses, int64_t pose_view_stride,
+                                  int pose_ld, const int64_t* inds, int64_t n, const float* g_rays, const float* g_rays_2,
+                                  int g_rays_stride, void* tmp, int64_t tmp_bytes, float* g_poses, nerfhip_stream_t stream);
+
 /* cast_to_image (eval_nerf.py:23-29): ToPILImage of a float image = mul(255) then byte conversion (truncation).
  * rgb: dev [pixels, in_channels >= 3] (first three used); out: dev uint8 [pixels, 3] (H, W, 3 byte order). */
 int nerfhip_cast_to_image(const float* rgb, int in_channels, int64_t pixels, uint8_t* out, nerfhip_stream_t stream);

@@ -3,6 +3,8 @@
 //     colours (train_nerf.py:210-227, cached branch :175-194) -- one launch instead of a host permutation of the
 //     whole image, a full-image get_ray_bundle and three fancy-index gathers;
 //   * its backward to the pose (pose refinement): d(loss)/d(rays) -> d(loss)/d(c2w[:3, :4]), a fixed-order reduction;
+//   * both over a stack of views (one batch spread over V images and V poses; one gradient per pose, each reduced in the
+//     single-view order over its own rays);
 //   * 8-bit output: cast_to_image / cast_to_disparity_image (eval_nerf.py:23-36).
 // Everything here is HBM/latency-bound byte and index work: one thread per ray / pixel, coalesced rows.
 #include "nh_host.h"
@@ -143,6 +145,70 @@ extern "C" int nerfhip_select_cached_rays(const nerfhip_select_cfg* cfg, const f
                          inds_out, stream, "select_cached_rays");
 }
 
+// ---- the image branch over a stack of views ---------------------------------------------------------------------------
+// Population V * H * W: global index g = v * (H * W) + k addresses view v and the reference's flat select index k of that
+// view (row k % H, col k / H, as in k_select_rays).  Pose of view v: poses + v * view_stride, row stride ld; image of view v:
+// images + v * H * W * channels.  Intrinsics, near / far, NDC and viewdirs are shared by all views.  Row i is, bit for bit,
+// the row k_select_rays writes for (poses[v], images[v], select_inds = {k}): the same helpers on the same operands.
+NH_KERNEL void k_select_rays_views(nerfhip_select_cfg s, NhNdc ndc, const float* __restrict__ poses, int64_t view_stride, int ld,
+                                   const float* __restrict__ images, uint64_t population, const int64_t* __restrict__ inds_in,
+                                   int64_t n, float* __restrict__ rays, float* __restrict__ target_out,
+                                   int64_t* __restrict__ inds_out) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    int64_t g;
+    if (inds_in) {
+        g = inds_in[i];
+    } else {
+        NhPerm p = nh_perm_key(s.seed, s.step, population);
+        g = (int64_t)nh_perm_at(p, (uint64_t)(s.first + i));
+    }
+    if (inds_out) inds_out[i] = g;
+    const int64_t hw = (int64_t)s.height * s.width;
+    const int64_t v = g / hw, k = g - v * hw;
+    const int64_t row = k % s.height, col = k / s.height;
+    float o[3], d[3], vd[3];
+    nh_pinhole_ray(s.height, s.width, s.focal, poses + v * view_stride, ld, row, col, o, d);
+    vd[0] = d[0], vd[1] = d[1], vd[2] = d[2];
+    if (s.ndc) nh_ndc_ray(ndc, o, d);
+    nh_write_ray_row(rays + i * (s.use_viewdirs ? 11 : 8), o, d, s.near, s.far, s.use_viewdirs ? vd : nullptr);
+    if (images) {
+        const float* px = images + (v * hw + row * s.width + col) * s.channels;
+        for (int c = 0; c < s.channels; ++c) target_out[i * s.channels + c] = px[c];
+    }
+}
+
+// what both views entry points ask of the pose table
+static int views_check(const nerfhip_select_cfg* cfg, int num_views, const float* poses, int64_t view_stride, int ld,
+                       const char* what) {
+    NH_REQUIRE(cfg && poses && cfg->height > 0 && cfg->width > 0, "%s: bad arguments", what);
+    NH_REQUIRE(num_views >= 1 && num_views <= NERFHIP_MAX_VIEWS, "%s: num_views must be 1 .. %d (got %d)", what, NERFHIP_MAX_VIEWS,
+               num_views);
+    NH_REQUIRE(ld >= 4, "%s: pose_ld must be >= 4 (got %d)", what, ld);
+    NH_REQUIRE(num_views == 1 || view_stride >= 2 * (int64_t)ld + 4,
+               "%s: pose_view_stride %lld cannot hold the 3 rows of a pose at row stride %d", what, (long long)view_stride, ld);
+    NH_REQUIRE((int64_t)num_views * cfg->height * cfg->width <= ((int64_t)1 << 32), "%s: num_views * height * width exceeds 2^32", what);
+    return NERFHIP_OK;
+}
+
+extern "C" int nerfhip_select_rays_views(const nerfhip_select_cfg* cfg, int num_views, const float* poses,
+                                         int64_t pose_view_stride, int pose_ld, const float* images, const int64_t* select_inds,
+                                         int64_t n, float* rays, float* target, int64_t* inds_out, nerfhip_stream_t stream) {
+    const char* what = "select_rays_views";
+    int rc = views_check(cfg, num_views, poses, pose_view_stride, pose_ld, what);
+    if (rc) return rc;
+    const int64_t population = (int64_t)num_views * cfg->height * cfg->width;
+    NH_REQUIRE(n >= 0 && (n == 0 || rays), "%s: bad arguments", what);
+    NH_REQUIRE(!images || (target && cfg->channels >= 1 && cfg->channels <= 4), "%s: bad target arguments", what);
+    NH_REQUIRE(select_inds || (cfg->first >= 0 && cfg->first + n <= population),
+               "%s: first + n exceeds the population (sampling is without replacement)", what);
+    if (n == 0) return NERFHIP_OK;
+    NhNdc ndc = {cfg->ndc_near, cfg->ndc_cw, cfg->ndc_ch, cfg->ndc_two_near, cfg->ndc_neg_two_near};
+    NH_LAUNCH(k_select_rays_views, nh_ceil_div(n, 256), 256, 0, stream, *cfg, ndc, poses, pose_view_stride, pose_ld, images,
+              (uint64_t)population, select_inds, n, rays, target, inds_out);
+    return nh_launch_status(what);
+}
+
 // ---- pose VJP: d(loss)/d(c2w[:3, :4]) from d(loss)/d(rays) (what autograd gives the reference's pose) --------------------
 // get_ray_bundle is linear in the pose: d = c2w[:3, :3] dc, o = c2w[:3, 3] (nh_pinhole_ray), so ray r contributes
 // g_c2w[c][k] += g_d[c] dc[k] (k < 3) and g_c2w[c][3] += g_o[c].  The select form first runs the packing and NDC backward of
@@ -173,8 +239,8 @@ struct PoseVjpArgs {
 };
 
 // this ray's 12 terms: t[c * 4 + k] = g_d[c] dc[k] (k < 3), t[c * 4 + 3] = g_o[c]
-NH_DEVICE void pose_vjp_ray(const PoseVjpArgs& a, int64_t i, float* t) {
-    const int64_t k = a.inds ? a.inds[i] : i;
+// (ray i of the batch, k: its select index / linear pixel id)
+NH_DEVICE void pose_vjp_ray_at(const PoseVjpArgs& a, int64_t i, int64_t k, float* t) {
     int64_t row, col;
     if (a.select) {
         row = k % a.s.height, col = k / a.s.height;  // (k_select_rays)
@@ -220,6 +286,24 @@ NH_DEVICE void pose_vjp_ray(const PoseVjpArgs& a, int64_t i, float* t) {
         t[c * 4 + 3] = go[c];
     }
 }
+NH_DEVICE void pose_vjp_ray(const PoseVjpArgs& a, int64_t i, float* t) { pose_vjp_ray_at(a, i, a.inds ? a.inds[i] : i, t); }
+
+// the 12 sums of a workgroup from its threads' sums: xor butterfly per wave, then the 4 waves in wave order -> dst[12]
+NH_DEVICE void pv_block_sum(float* acc, float (*s_part)[12], float* dst) {
+#pragma unroll
+    for (int j = 0; j < 12; ++j) acc[j] = nh_wave_sum(acc[j]);
+    const int wave = nh_wave_in_block();
+    if (nh_lane() == 0) {
+#pragma unroll
+        for (int j = 0; j < 12; ++j) s_part[wave][j] = acc[j];
+    }
+    nh_block_sync();
+    if (threadIdx.x < 12) {
+        float v = s_part[0][threadIdx.x];
+        for (int w = 1; w < PV_THREADS / 64; ++w) v += s_part[w][threadIdx.x];
+        dst[threadIdx.x] = v;
+    }
+}
 
 NH_KERNEL void k_pose_vjp_part(PoseVjpArgs a) {
     NH_SHARED float s_part[PV_THREADS / 64][12];
@@ -233,19 +317,7 @@ NH_KERNEL void k_pose_vjp_part(PoseVjpArgs a) {
 #pragma unroll
         for (int j = 0; j < 12; ++j) acc[j] += t[j];
     }
-#pragma unroll
-    for (int j = 0; j < 12; ++j) acc[j] = nh_wave_sum(acc[j]);
-    const int wave = nh_wave_in_block();
-    if (nh_lane() == 0) {
-#pragma unroll
-        for (int j = 0; j < 12; ++j) s_part[wave][j] = acc[j];
-    }
-    nh_block_sync();
-    if (threadIdx.x < 12) {
-        float v = s_part[0][threadIdx.x];
-        for (int w = 1; w < PV_THREADS / 64; ++w) v += s_part[w][threadIdx.x];
-        a.tmp[(int64_t)blockIdx.x * 12 + threadIdx.x] = v;
-    }
+    pv_block_sum(acc, s_part, a.tmp + (int64_t)blockIdx.x * 12);
 }
 
 NH_KERNEL void k_pose_vjp_sum(const float* __restrict__ tmp, int wgs, float* __restrict__ g_c2w) {
@@ -269,7 +341,176 @@ int pose_vjp_launch(const PoseVjpArgs& a, int64_t tmp_bytes, float* g_c2w, nerfh
     return nh_launch_status(what);
 }
 
+// ---- the pose VJP over a stack of views -----------------------------------------------------------------------------------
+// g_poses[v] = the single-view result for pose v on the rays of view v alone, in ascending batch position -- bit for bit: the n_v
+// rays of a view are ranked (a stable counting sort of the batch by view) and then summed along the single-view tree with n = n_v.
+// Three launches whose grids depend on (n, V) only; integer bookkeeping only between them; no atomics:
+//   k_pose_views_group -- workgroup v: off[v] = rays of views < v, cnt[v] = n_v (one scan of the n indices; view membership is two
+//       compares against v H W, no division), then a second scan ranks view v's rays in batch order (prefix sums over the wave and
+//       the 4 waves, PVG_PER consecutive rays per thread) and writes their batch positions to list[off[v] + rank];
+//   k_pose_views_part -- floor(n / 256) + V workgroups; view v owns the slots slot0(v) = off[v] / 256 + v ... + G(n_v) - 1 (disjoint:
+//       G(n_v) <= ceil(n_v / 256) <= floor((off[v] + n_v) / 256) - floor(off[v] / 256) + 1); workgroup w finds its (v, b) by bisection
+//       over slot0, and is partial b of view v: k_pose_vjp_part's loop and sums over list positions b 256 + t + q 256 G(n_v);
+//   k_pose_views_sum -- workgroup v is k_pose_vjp_sum over view v's G(n_v) partials (none: exact zeros).
+constexpr int PVG_PER = 4;
+
+struct PoseViewsArgs {
+    PoseVjpArgs a;        // c2w: the pose table; inds: GLOBAL indices v H W + k; tmp: the slots' partials [floor(n / 256) + V][12]
+    int num_views;
+    int64_t view_stride, hw;
+    int *cnt, *off, *list;  // [V], [V], [n]
+};
+
+NH_DEVICE int pv_wgs_of(int n) {
+    const int g = (n + PV_THREADS - 1) / PV_THREADS;
+    return g < PV_MAX_WGS ? g : PV_MAX_WGS;
+}
+NH_DEVICE int wave_sum_i(int v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += nh_shfl_xor_i(v, m);
+    return v;
+}
+
+NH_KERNEL void k_pose_views_group(PoseViewsArgs p) {
+    NH_SHARED int s_less[PV_THREADS / 64], s_eq[PV_THREADS / 64], s_tot[PV_THREADS / 64];
+    const int lane = nh_lane(), wave = nh_wave_in_block();
+    const int n = (int)p.a.n;
+    const int64_t lo = (int64_t)blockIdx.x * p.hw, hi = lo + p.hw;
+    int less = 0, eq = 0;
+    for (int i = (int)threadIdx.x; i < n; i += PV_THREADS) {
+        const int64_t g = p.a.inds[i];
+        less += g < lo ? 1 : 0;
+        eq += (g >= lo && g < hi) ? 1 : 0;
+    }
+    less = wave_sum_i(less), eq = wave_sum_i(eq);
+    if (lane == 0) s_less[wave] = less, s_eq[wave] = eq;
+    nh_block_sync();
+    int off = 0, cnt = 0;
+    for (int w = 0; w < PV_THREADS / 64; ++w) off += s_less[w], cnt += s_eq[w];
+    if (threadIdx.x == 0) p.off[blockIdx.x] = off, p.cnt[blockIdx.x] = cnt;
+    // ranks in batch order: chunks of 256 * PVG_PER rays, thread t holds PVG_PER consecutive ones
+    int done = 0;
+    for (int base = 0; base < n && done < cnt; base += PV_THREADS * PVG_PER) {
+        const int i0 = base + (int)threadIdx.x * PVG_PER;
+        int flags = 0, c = 0;
+#pragma unroll
+        for (int e = 0; e < PVG_PER; ++e) {
+            if (i0 + e < n) {
+                const int64_t g = p.a.inds[i0 + e];
+                if (g >= lo && g < hi) flags |= 1 << e, ++c;
+            }
+        }
+        int incl = c;  // inclusive prefix sum of c over the wave
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int o = nh_shfl_i(incl, lane - d < 0 ? 0 : lane - d);
+            if (lane >= d) incl += o;
+        }
+        if (lane == 63) s_tot[wave] = incl;
+        nh_block_sync();
+        int r = off + done + incl - c, total = 0;
+        for (int w = 0; w < PV_THREADS / 64; ++w) {
+            if (w < wave) r += s_tot[w];
+            total += s_tot[w];
+        }
+#pragma unroll
+        for (int e = 0; e < PVG_PER; ++e)
+            if (flags & (1 << e)) p.list[r++] = i0 + e;
+        done += total;
+        nh_block_sync();  // (s_tot is rewritten by the next chunk)
+    }
+}
+
+NH_KERNEL void k_pose_views_part(PoseViewsArgs p) {
+    NH_SHARED float s_part[PV_THREADS / 64][12];
+    const int w = (int)blockIdx.x;
+    int v = 0, top = p.num_views - 1;  // the last view whose first slot is <= w (slot0 is strictly increasing, slot0(0) = 0)
+    while (v < top) {
+        const int mid = (v + top + 1) >> 1;
+        if (p.off[mid] / PV_THREADS + mid <= w)
+            v = mid;
+        else
+            top = mid - 1;
+    }
+    const int off = p.off[v], nv = p.cnt[v];
+    const int b = w - (off / PV_THREADS + v), wgs = pv_wgs_of(nv);
+    if (b >= wgs) return;  // (a slot no view uses; the whole workgroup leaves)
+    PoseVjpArgs a = p.a;
+    a.c2w = p.a.c2w + (int64_t)v * p.view_stride;
+    const int64_t g0 = (int64_t)v * p.hw;
+    float acc[12];
+#pragma unroll
+    for (int j = 0; j < 12; ++j) acc[j] = 0.0f;
+    const int step = wgs * PV_THREADS;
+    for (int r = b * PV_THREADS + (int)threadIdx.x; r < nv; r += step) {
+        const int64_t i = p.list[off + r];
+        float t[12];
+        pose_vjp_ray_at(a, i, a.inds[i] - g0, t);
+#pragma unroll
+        for (int j = 0; j < 12; ++j) acc[j] += t[j];
+    }
+    pv_block_sum(acc, s_part, p.a.tmp + (int64_t)w * 12);
+}
+
+// (cnt == NULL: no rays at all)
+NH_KERNEL void k_pose_views_sum(const float* __restrict__ part, const int* __restrict__ cnt, const int* __restrict__ off,
+                                float* __restrict__ g_poses) {
+    const int j = nh_wave_in_block(), lane = nh_lane(), view = (int)blockIdx.x;
+    const int wgs = cnt ? pv_wgs_of(cnt[view]) : 0;
+    const int64_t slot0 = cnt ? off[view] / PV_THREADS + view : 0;
+    float v = 0.0f;
+    for (int q = lane; q < wgs; q += 64) v += part[(slot0 + q) * 12 + j];
+    v = nh_wave_sum(v);
+    if (lane == 0) g_poses[(int64_t)view * 12 + j] = v;
+}
+
+int64_t pv_views_words(int64_t n, int num_views, int64_t* slots) {
+    *slots = n / PV_THREADS + num_views;
+    return *slots * 12 + 2 * (int64_t)num_views + n;
+}
+
 }  // namespace
+
+extern "C" int64_t nerfhip_pose_grad_views_tmp_bytes(int64_t n, int num_views) {
+    int64_t slots;
+    if (n < 0 || n >= ((int64_t)1 << 31) || num_views < 1 || num_views > NERFHIP_MAX_VIEWS) return -1;
+    return n == 0 ? 0 : pv_views_words(n, num_views, &slots) * (int64_t)sizeof(float);
+}
+
+extern "C" int nerfhip_select_rays_views_bwd(const nerfhip_select_cfg* cfg, int num_views, const float* poses,
+                                             int64_t pose_view_stride, int pose_ld, const int64_t* inds, int64_t n,
+                                             const float* g_rays, const float* g_rays_2, int g_rays_stride, void* tmp,
+                                             int64_t tmp_bytes, float* g_poses, nerfhip_stream_t stream) {
+    const char* what = "select_rays_views_bwd";
+    int rc = views_check(cfg, num_views, poses, pose_view_stride, pose_ld, what);
+    if (rc) return rc;
+    NH_REQUIRE(n >= 0 && n < ((int64_t)1 << 31) && g_poses && (n == 0 || (inds && g_rays)), "%s: bad arguments", what);
+    NH_REQUIRE(g_rays_stride >= (cfg->use_viewdirs ? 11 : 8), "%s: g_rays_stride must cover the %d columns of a ray row", what,
+               cfg->use_viewdirs ? 11 : 8);
+    const int64_t need = nerfhip_pose_grad_views_tmp_bytes(n, num_views);
+    NH_REQUIRE(tmp_bytes >= need && (need == 0 || tmp),
+               "%s: tmp must hold nerfhip_pose_grad_views_tmp_bytes(n, num_views) = %lld bytes", what, (long long)need);
+    PoseViewsArgs p;
+    memset(&p, 0, sizeof(p));
+    if (n > 0) {
+        int64_t slots;
+        pv_views_words(n, num_views, &slots);
+        p.a.s = *cfg;
+        p.a.ndc = NhNdc{cfg->ndc_near, cfg->ndc_cw, cfg->ndc_ch, cfg->ndc_two_near, cfg->ndc_neg_two_near};
+        p.a.select = 1, p.a.c2w = poses, p.a.ld = pose_ld, p.a.inds = inds, p.a.n = n, p.a.g_a = g_rays, p.a.g_b = g_rays_2;
+        p.a.g_stride = g_rays_stride, p.a.tmp = (float*)tmp;
+        p.num_views = num_views, p.view_stride = pose_view_stride, p.hw = (int64_t)cfg->height * cfg->width;
+        p.cnt = (int*)tmp + slots * 12, p.off = p.cnt + num_views, p.list = p.off + num_views;
+        NH_LAUNCH(k_pose_views_group, num_views, PV_THREADS, 0, stream, p);
+        rc = nh_launch_status(what);
+        if (rc) return rc;
+        NH_LAUNCH(k_pose_views_part, slots, PV_THREADS, 0, stream, p);
+        rc = nh_launch_status(what);
+        if (rc) return rc;
+    }
+    NH_LAUNCH(k_pose_views_sum, num_views, 12 * 64, 0, stream, (const float*)p.a.tmp, (const int*)p.cnt, (const int*)p.off, g_poses);
+    return nh_launch_status(what);
+}
 
 extern "C" int64_t nerfhip_pose_grad_tmp_bytes(int64_t n) { return n < 0 ? -1 : pv_wgs(n) * 12 * (int64_t)sizeof(float); }
 

@@ -412,6 +412,46 @@ class TrainEngine:
         self.optimizer_step(lr)
         return self.loss
 
+    def step_on_views(self, images, poses, height, width, focal_length, options, num_random_rays, lr=None, global_rays=None,
+                      pose_grads=None):
+        """step_on_image over a resident stack of views: this rank's rays are drawn from ALL of `images` (V, H, W, 3|4) with the
+        rays of each generated from its own row of `poses` (V, >=3, 4) -- train_utils.select_training_rays_views --, then `step`.
+        Same rank slicing (first = rank * n, or the shard_bounds slice of `global_rays`) over the permutation of V * H * W, same
+        ray_offset = first for the in-kernel draws, no host work besides launches.
+        pose_grads: None, or a contiguous float32 (V, 3, 4) tensor on the engine's device: the step also writes
+        d(loss)/d(poses[v, :3, :4]) of every view into it (zeros for a view without a ray in the batch): the render backward with
+        the ray gradient, then nerfhip_select_rays_views_bwd on the main stream after the two streams joined; still no host
+        synchronisation.  The engine's Adam updates the nets as usual (lr=0 freezes them).  One rank only."""
+        from .parallel import shard_bounds
+        from .train_utils import select_training_rays_views, select_training_rays_views_bwd
+        if global_rays is None:
+            n = int(num_random_rays)
+            first = self.rank * n
+        else:
+            first, hi = shard_bounds(int(global_rays), self.rank, self.world)
+            n = hi - first
+        if pose_grads is None:
+            rays, target, _ = select_training_rays_views(height, width, focal_length, poses, images, n, options, seed=self.seed,
+                                                         step=self.step_count, first=first)
+            return self.step(rays, target, ray_offset=first, lr=lr, global_rays=global_rays)
+        self._no_pose_grad_across_ranks("pose_grads")
+        if (not isinstance(pose_grads, torch.Tensor) or pose_grads.device != self.dev or pose_grads.dtype != torch.float32
+                or tuple(pose_grads.shape) != (poses.shape[0], 3, 4) or not pose_grads.is_contiguous()):
+            raise RuntimeError("TrainEngine: pose_grads must be a contiguous float32 (%d, 3, 4) tensor on %s"
+                               % (poses.shape[0], self.dev))
+        with torch.no_grad():
+            rays, target, used = select_training_rays_views(height, width, focal_length, poses, images, n, options,
+                                                            seed=self.seed, step=self.step_count, first=first)
+        if getattr(self, "_ray_grad_n", -1) != n:
+            self._ray_grad = torch.empty((n, self.stride), dtype=torch.float32, device=self.dev)
+            self._ray_grad_n = n
+        self.forward_backward(rays, target, first, global_rays, None, self._ray_grad)
+        with torch.cuda.device(self.dev):
+            select_training_rays_views_bwd(height, width, focal_length, poses, used, self._ray_grad, options, self.ray_grad_coarse,
+                                           out=pose_grads)
+        self.optimizer_step(lr)
+        return self.loss
+
     @staticmethod
     def lr_at(iteration, lr0=5e-3, lr_decay=250, lr_decay_factor=0.1):
         """train_nerf.py:264-270: lr0 * factor ** (i / (lr_decay * 1000))."""

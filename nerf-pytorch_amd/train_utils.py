@@ -422,6 +422,116 @@ def select_training_rays_bwd(height, width, focal_length, pose, select_inds, g_r
     return _pose_vjp(cfg, _select_pose(pose), used, g_rays, g_rays_2, out)
 
 
+# ---- one batch over a stack of views --------------------------------------------------------------------------------------------
+def _select_poses(poses):
+    if poses.dim() != 3 or poses.shape[1] < 3 or poses.shape[2] < 4:
+        raise RuntimeError("poses must be a (V, >=3, >=4) tensor (got shape %s)" % (tuple(poses.shape),))
+    p = poses.detach().float()
+    ok = p.stride(2) == 1 and p.stride(1) >= 4 and (p.shape[0] == 1 or p.stride(0) >= 2 * p.stride(1) + 4)
+    return p if ok else p.contiguous()
+
+
+def _select_views_launch(cfg, poses, images, select_inds, n):
+    dev = poses.device
+    rays = torch.empty((n, 11 if cfg.use_viewdirs else 8), dtype=torch.float32, device=dev)
+    target = torch.empty((n, cfg.channels), dtype=torch.float32, device=dev) if images is not None else None
+    used = torch.empty((n,), dtype=torch.int64, device=dev)
+    with L.launch_on(poses, images, select_inds, rays) as st:
+        L.get_lib().select_rays_views(C.byref(cfg), poses.shape[0], poses.data_ptr(), poses.stride(0), poses.stride(1),
+                                      images.data_ptr() if images is not None else None,
+                                      select_inds.data_ptr() if select_inds is not None else None, n, rays.data_ptr(),
+                                      target.data_ptr() if target is not None else None, used.data_ptr(), st)
+    return rays, target, used
+
+
+def _pose_views_vjp(cfg, poses, used, g_rays, g_rays_2, out=None):
+    """nerfhip_select_rays_views_bwd on the current stream: d(loss)/d(poses[:, :3, :4]) (V x 3 x 4 float32)."""
+    lib = L.get_lib()
+    n, nv = used.numel(), poses.shape[0]
+    tb = lib.pose_grad_views_tmp_bytes(n, nv)
+    if tb < 0:
+        raise RuntimeError("select_training_rays_views: %d rays over %d views is outside the kernel's limits" % (n, nv))
+    tmp = torch.empty(tb // 4 + 1, dtype=torch.float32, device=poses.device)
+    if out is None:
+        out = torch.empty((nv, 3, 4), dtype=torch.float32, device=poses.device)
+    with L.launch_on(poses, used, g_rays, g_rays_2, tmp, out) as st:
+        lib.select_rays_views_bwd(C.byref(cfg), nv, poses.data_ptr(), poses.stride(0), poses.stride(1), used.data_ptr(), n,
+                                  g_rays.data_ptr(), g_rays_2.data_ptr() if g_rays_2 is not None else None, g_rays.stride(0),
+                                  tmp.data_ptr(), tb, out.data_ptr(), st)
+    return out
+
+
+class _SelectRaysViews(torch.autograd.Function):
+    """select_training_rays_views with the per-view pose VJP (nerfhip_select_rays_views_bwd): the gradient flows from the rays to
+    the [:, :3, :4] entries of the pose table; targets and indices carry none.  The forward issues exactly the launch of the plain
+    call."""
+
+    @staticmethod
+    def forward(ctx, poses, cfg, images, select_inds, n):
+        p = _select_poses(poses)
+        rays, target, used = _select_views_launch(cfg, p, images, select_inds, n)
+        ctx.keep = (cfg, p, used)
+        ctx.poses_shape = (poses.shape, poses.dtype)
+        ctx.mark_non_differentiable(*[t for t in (target, used) if t is not None])
+        ctx.set_materialize_grads(False)
+        return rays, target, used
+
+    @staticmethod
+    def backward(ctx, g_rays, _g_target, _g_used):
+        if g_rays is None:
+            return (None,) * 5
+        cfg, p, used = ctx.keep
+        g34 = _pose_views_vjp(cfg, p, used, g_rays.contiguous().float(), None)
+        shape, dtype = ctx.poses_shape
+        g = torch.zeros(shape, dtype=dtype, device=p.device)
+        g[:, :3, :4] = g34.to(dtype)
+        return g, None, None, None, None
+
+
+def select_training_rays_views(height, width, focal_length, poses, images, num_random_rays, options, select_inds=None, seed=0,
+                               step=0, first=0):
+    """select_training_rays over a stack of views, in ONE launch: `num_random_rays` distinct (view, pixel) pairs drawn from all of
+    `images` (V, H, W, 3|4; or None) with the rays of each generated from its own row of `poses` (V, >=3, 4; device; a strided
+    slice of a larger table is read in place).  Intrinsics and options are shared by the views.  The indices (third output, and
+    `select_inds` when given) are global: v * H * W + k, k the reference's flat select index in view v.  Returns (rays, target,
+    select_inds) as select_training_rays does; every row equals the row that call makes for (poses[v], images[v], [k]).
+    With `poses` requiring grad the rays are differentiable w.r.t. them: the backward runs the per-view pose VJP
+    (select_training_rays_views_bwd), so every view with a ray in the batch gets its gradient from one step."""
+    n = int(num_random_rays)
+    channels = 3 if images is None else images.shape[-1]
+    cfg = _select_cfg(height, width, focal_length, options, channels, seed, step, first)
+    if images is not None:
+        if images.dim() != 4 or images.shape[0] != poses.shape[0] or tuple(images.shape[1:3]) != (cfg.height, cfg.width):
+            raise RuntimeError("select_training_rays_views: images must be (V, H, W, C) with V = %d, H = %d, W = %d (got %s)"
+                               % (poses.shape[0], cfg.height, cfg.width, tuple(images.shape)))
+        images = images.detach().float().contiguous()
+    if select_inds is not None:
+        select_inds = torch.as_tensor(select_inds, dtype=torch.int64, device=poses.device).contiguous()
+    if torch.is_grad_enabled() and poses.requires_grad:
+        return _SelectRaysViews.apply(poses, cfg, images, select_inds, n)
+    return _select_views_launch(cfg, _select_poses(poses), images, select_inds, n)
+
+
+def select_training_rays_views_bwd(height, width, focal_length, poses, select_inds, g_rays, options, g_rays_2=None, out=None):
+    """The per-view pose VJP of select_training_rays_views without autograd: d(loss)/d(poses[:, :3, :4]) (V x 3 x 4 float32 device
+    tensor; written into `out` when given) from d(loss)/d(rays) rows `g_rays` (+ `g_rays_2`, added row by row) at the global
+    `select_inds` of the forward.  Entry v is bit-identical to select_training_rays_bwd on the rays of view v alone (in batch
+    order); a view without a ray gets zeros.  Enqueued on the current stream; no host synchronisation."""
+    cfg = _select_cfg(height, width, focal_length, options, 3, 0, 0, 0)
+    what = "select_training_rays_views_bwd"
+    for name, g in (("g_rays", g_rays), ("g_rays_2", g_rays_2)):
+        if g is not None and (g.dtype != torch.float32 or g.dim() != 2 or g.stride(1) != 1
+                              or g.shape[1] < (11 if cfg.use_viewdirs else 8)):
+            raise RuntimeError("%s: %s must be float32 rows of the ray layout (got %s, shape %s)" % (what, name, g.dtype, tuple(g.shape)))
+    if g_rays_2 is not None and (g_rays_2.shape != g_rays.shape or g_rays_2.stride() != g_rays.stride()):
+        raise RuntimeError("%s: g_rays_2 must have the layout of g_rays" % what)
+    p = _select_poses(poses)
+    if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != (p.shape[0], 3, 4) or not out.is_contiguous()):
+        raise RuntimeError("%s: out must be a contiguous float32 (%d, 3, 4) tensor" % (what, p.shape[0]))
+    used = torch.as_tensor(select_inds, dtype=torch.int64, device=poses.device).contiguous()
+    return _pose_views_vjp(cfg, p, used, g_rays, g_rays_2, out)
+
+
 def select_cached_training_rays(cache_dict, num_random_rays, options, select_inds=None, seed=0, step=0, first=0):
     """The cached branch (train_nerf.py:175-194): rows of cache_dict["ray_bundle"] (2, ., 3) and of
     cache_dict["target"][..., :3], both already on the device."""
