@@ -496,6 +496,23 @@ int nerfhip_select_rays_views_bwd(const nerfhip_select_cfg* cfg, int num_views, 
                                   int pose_ld, const int64_t* inds, int64_t n, const float* g_rays, const float* g_rays_2,
                                   int g_rays_stride, void* tmp, int64_t tmp_bytes, float* g_poses, nerfhip_stream_t stream);
 
+/* ---- camera table: one se(3) twist per view composed onto a base pose (the parametrisation pose refinement steps) --------
+ * poses[v] = base[v] * Exp(xi[v]): a camera-frame perturbation.  xi: dev float [V][6] = [w (3), v (3)]; Exp is the full SE(3)
+ * exponential: R = I + A W + B W^2, t = (I + B W + C W^2) v with W = hat(w), th = |w|, A = sin th / th, B = (1 - cos th) / th^2,
+ * C = (th - sin th) / th^3 (evaluated without cancellation; th = 0 included).  base: dev, the base pose of view v is 3 rows of
+ * base_ld >= 4 floats at base + v * base_view_stride (the strided-table convention of nerfhip_select_rays_views;
+ * base_view_stride >= 2 * base_ld + 4 when num_views > 1).  poses: dev float [V][3][4], contiguous -- directly a pose table of
+ * nerfhip_select_rays_views (pose_ld 4, pose_view_stride 12).  A view whose six twist entries are all zero gets its base bit for
+ * bit.  Limits: 1 <= num_views <= NERFHIP_MAX_VIEWS.  One launch. */
+int nerfhip_pose_table_fwd(const float* xi, const float* base, int64_t base_view_stride, int base_ld, int num_views,
+                           float* poses, nerfhip_stream_t stream);
+/* Its VJP w.r.t. the twists (closed form; base carries no gradient).  g_poses: dev float [V][3][4] = d(loss)/d(poses), e.g. what
+ * nerfhip_select_rays_views_bwd wrote; active: dev, one byte per view, or NULL = every view active: an inactive view (byte 0) gets
+ * exact zeros and its g_poses row is not read (freezing an anchor view fixes the gauge); g_xi: dev float [V][6], written
+ * completely.  The twists are stepped with nerfhip_adam_step on the flat [V * 6] vector.  One launch. */
+int nerfhip_pose_table_bwd(const float* xi, const float* base, int64_t base_view_stride, int base_ld, int num_views,
+                           const float* g_poses, const unsigned char* active, float* g_xi, nerfhip_stream_t stream);
+
 /* cast_to_image (eval_nerf.py:23-29): ToPILImage of a float image = mul(255) then byte conversion (truncation).
  * rgb: dev [pixels, in_channels >= 3] (first three used); out: dev uint8 [pixels, 3] (H, W, 3 byte order). */
 int nerfhip_cast_to_image(const float* rgb, int in_channels, int64_t pixels, uint8_t* out, nerfhip_stream_t stream);

@@ -3,10 +3,11 @@
 Import as ``nerf_pytorch_amd`` (the alias package next to this directory).  Mirrors the reference's star-export
 surface for the hot path (nerf/__init__.py:1-7): nerf_helpers, volume_rendering_utils, train_utils, models.
 Next to the path: on-device training-ray selection (train_utils.select_training_rays, over a stack of views:
-select_training_rays_views), the 8-bit output stage (eval_utils) and the reference's .ckpt / .data formats (io_utils).  Dataset loaders, the YAML config
+select_training_rays_views; their cameras as se(3) twists on base poses: cameras.CameraTable / se3_poses), the 8-bit output stage (eval_utils) and the reference's .ckpt / .data formats (io_utils).  Dataset loaders, the YAML config
 tree and the CLI scripts of the reference are out of scope.
 """
 from . import eval_utils, io_utils, models  # noqa: F401
+from .cameras import CameraTable, se3_poses  # noqa: F401
 from .cfg import AttrDict, make_options  # noqa: F401
 from .engine import TrainEngine  # noqa: F401
 from .models import FlexibleNeRFModel  # noqa: F401

@@ -140,6 +140,8 @@ _PROTOS = {
     "nerfhip_pose_grad_views_tmp_bytes": (c_i64, [c_i64, C.c_int]),
     "nerfhip_select_rays_views_bwd": (C.c_int, [C.POINTER(SelectCfg), C.c_int, c_f, c_i64, C.c_int, c_f, c_i64, c_f, c_f, C.c_int,
                                                 c_f, c_i64, c_f, c_f]),
+    "nerfhip_pose_table_fwd": (C.c_int, [c_f, c_f, c_i64, C.c_int, C.c_int, c_f, c_f]),
+    "nerfhip_pose_table_bwd": (C.c_int, [c_f, c_f, c_i64, C.c_int, C.c_int, c_f, c_f, c_f, c_f]),
     "nerfhip_cast_to_image": (C.c_int, [c_f, C.c_int, c_i64, c_f, c_f]),
     "nerfhip_cast_to_disparity_image": (C.c_int, [c_f, c_i64, c_f, c_f, c_f]),
 }

@@ -1,0 +1,143 @@
+"""Camera table: se(3) pose refinement composed, differentiated and stepped on the device.
+
+pose[v] = base[v] @ Exp(xi[v]) -- a camera-frame perturbation; xi = [w (3), v (3)] and Exp the full SE(3) exponential (the
+reference's lieutils.SE3.Exp, twist order [w, v]).  One launch composes every view (nerfhip_pose_table_fwd), one launch pulls
+d(loss)/d(poses) back to the twists (nerfhip_pose_table_bwd), and the twists are stepped by the fused Adam kernel the nets use
+(nerfhip_adam_step on the flat [V * 6] vector).
+
+* ``se3_poses(xi, base)`` -- the drop-in form: an autograd node when `xi` requires grad, the same launch otherwise.
+* ``CameraTable`` -- owns the twists, their Adam state and every buffer; ``TrainEngine.step_on_views(cameras=table)`` runs the joint
+  field-and-camera step with no host work besides launches.
+"""
+import torch
+
+from . import _lib as L
+
+
+def _base_table(base, num_views):
+    if base.dim() != 3 or base.shape[0] != num_views or base.shape[1] < 3 or base.shape[2] < 4:
+        raise RuntimeError("base must be a (V = %d, >=3, >=4) tensor (got shape %s)" % (num_views, tuple(base.shape)))
+    b = base.detach().float()
+    ok = b.stride(2) == 1 and b.stride(1) >= 4 and (b.shape[0] == 1 or b.stride(0) >= 2 * b.stride(1) + 4)
+    return b if ok else b.contiguous()
+
+
+def _twists(xi):
+    if xi.dim() != 2 or xi.shape[1] != 6 or xi.shape[0] < 1:
+        raise RuntimeError("xi must be a (V, 6) tensor of twists [w, v] (got shape %s)" % (tuple(xi.shape),))
+    return xi.detach().float().contiguous()
+
+
+def _compose(xi, base, out):
+    with L.launch_on(xi, base, out) as st:
+        L.get_lib().pose_table_fwd(xi.data_ptr(), base.data_ptr(), base.stride(0), base.stride(1), xi.shape[0], out.data_ptr(), st)
+    return out
+
+
+def _pull_back(xi, base, g_poses, active, out):
+    with L.launch_on(xi, base, g_poses, active, out) as st:
+        L.get_lib().pose_table_bwd(xi.data_ptr(), base.data_ptr(), base.stride(0), base.stride(1), xi.shape[0], g_poses.data_ptr(),
+                                   active.data_ptr() if active is not None else None, out.data_ptr(), st)
+    return out
+
+
+class _Se3Poses(torch.autograd.Function):
+    """se3_poses with its closed-form VJP: the gradient flows from the (V, 3, 4) poses to the twists; the base carries none.  The
+    forward issues exactly the launch of the plain call."""
+
+    @staticmethod
+    def forward(ctx, xi, base):
+        x, b = _twists(xi), _base_table(base, xi.shape[0])
+        ctx.save_for_backward(xi, base)   # (the inputs themselves: changing one in place before the backward is an autograd error)
+        return _compose(x, b, torch.empty((x.shape[0], 3, 4), dtype=torch.float32, device=x.device))
+
+    @staticmethod
+    def backward(ctx, g_poses):
+        xi, base = ctx.saved_tensors
+        x = _twists(xi)
+        g = _pull_back(x, _base_table(base, x.shape[0]), g_poses.float().contiguous(), None, torch.empty_like(x))
+        return g.to(xi.dtype), None
+
+
+def se3_poses(xi, base):
+    """poses (V, 3, 4) = base[:, :3, :4] @ Exp(xi): one launch.  xi: (V, 6) twists [w, v] on the device; base: (V, >=3, 4) (a strided
+    slice of a larger table is read in place).  The result is directly a pose table of select_training_rays_views.  With `xi`
+    requiring grad the poses are differentiable w.r.t. it (one more launch in the backward), so
+    select_training_rays_views(..., poses=se3_poses(xi, base), ...) -> loss.backward() -> torch.optim.Adam([xi]) refines the
+    cameras; `base` gets no gradient.  A view whose twist is exactly zero gets its base bit for bit."""
+    if torch.is_grad_enabled() and xi.requires_grad:
+        return _Se3Poses.apply(xi, base)
+    x = _twists(xi)
+    return _compose(x, _base_table(base, x.shape[0]), torch.empty((x.shape[0], 3, 4), dtype=torch.float32, device=x.device))
+
+
+class CameraTable:
+    """The cameras of a capture under refinement: one twist per view on top of a fixed base pose, with the Adam state of the
+    twists.  Every buffer is allocated here once; poses(), backward() and step() are one launch each on the current stream of the
+    table's device, with no host synchronisation.
+
+    base_poses: (V, >=3, 4) device tensor (copied).  active: None (every view is refined) or V booleans: an inactive view's
+    gradient is exactly zero, so its twist stays where it is -- at zero its pose stays its base bit for bit (freezing one anchor
+    view fixes the gauge of a joint refinement)."""
+
+    def __init__(self, base_poses, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, active=None):
+        if not isinstance(base_poses, torch.Tensor) or not base_poses.is_cuda:
+            raise RuntimeError("CameraTable needs the base poses on a CUDA (HIP) device (nerf_pytorch_amd has no CPU path)")
+        if base_poses.dim() != 3 or base_poses.shape[0] < 1 or base_poses.shape[1] < 3 or base_poses.shape[2] != 4:
+            raise RuntimeError("base_poses must be a (V, >=3, 4) tensor (got shape %s)" % (tuple(base_poses.shape),))
+        self.lib = L.get_lib()
+        self.dev = base_poses.device
+        self.base = base_poses.detach()[:, :3, :4].float().contiguous().clone()
+        self.num_views = v = self.base.shape[0]
+        self.lr, self.betas, self.eps = lr, betas, eps
+        self.step_count = 0
+        mk = lambda *s: torch.zeros(s, dtype=torch.float32, device=self.dev)  # noqa: E731
+        self.xi, self.exp_avg, self.exp_avg_sq = mk(v, 6), mk(v, 6), mk(v, 6)
+        self.g_xi, self.g_poses, self._poses = mk(v, 6), mk(v, 3, 4), mk(v, 3, 4)
+        self.active = None
+        if active is not None:
+            a = torch.as_tensor(active, device=self.dev)
+            if a.numel() != v:
+                raise RuntimeError("active must hold one flag per view (%d), got %d" % (v, a.numel()))
+            self.active = (a.reshape(v) != 0).to(torch.uint8).contiguous()
+
+    def poses(self):
+        """Composes base @ Exp(xi) into the table's own (V, 3, 4) buffer and returns it (overwritten by the next call)."""
+        return _compose(self.xi, self.base, self._poses)
+
+    def backward(self, g_poses=None):
+        """d(loss)/d(xi) (the table's own (V, 6) buffer) from d(loss)/d(poses): `g_poses`, a contiguous float32 (V, 3, 4) device
+        tensor, or None for the table's own `g_poses` buffer (the one step_on_views(cameras=...) fills)."""
+        g = self.g_poses if g_poses is None else g_poses
+        if (not isinstance(g, torch.Tensor) or g.device != self.dev or g.dtype != torch.float32
+                or tuple(g.shape) != (self.num_views, 3, 4) or not g.is_contiguous()):
+            raise RuntimeError("CameraTable: g_poses must be a contiguous float32 (%d, 3, 4) tensor on %s" % (self.num_views, self.dev))
+        return _pull_back(self.xi, self.base, g, self.active, self.g_xi)
+
+    def step(self, lr=None):
+        """One Adam step of the twists on the gradient the last backward() left."""
+        self.step_count += 1
+        b1, b2 = self.betas
+        with L.launch_on(self.xi, self.g_xi) as st:
+            self.lib.adam_step(self.xi.data_ptr(), self.g_xi.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                               self.xi.numel(), self.lr if lr is None else lr, b1, b2, self.eps, self.step_count, 1.0, st)
+
+    def pose_matrices(self):
+        """The current poses as a detached (V, 4, 4) tensor (bottom row 0 0 0 1), e.g. for saving."""
+        out = torch.zeros((self.num_views, 4, 4), dtype=torch.float32, device=self.dev)
+        out[:, :3] = self.poses()
+        out[:, 3, 3] = 1.0
+        return out
+
+    def state_dict(self):
+        return dict(xi=self.xi.clone(), exp_avg=self.exp_avg.clone(), exp_avg_sq=self.exp_avg_sq.clone(), step=self.step_count,
+                    base=self.base.clone())
+
+    def load_state_dict(self, state):
+        for k in ("xi", "exp_avg", "exp_avg_sq", "base"):
+            t = getattr(self, k)
+            if tuple(state[k].shape) != tuple(t.shape):
+                raise RuntimeError("CameraTable.load_state_dict: %s has shape %s, the table holds %s"
+                                   % (k, tuple(state[k].shape), tuple(t.shape)))
+            t.copy_(state[k])
+        self.step_count = int(state["step"])

@@ -5,6 +5,7 @@
 //   * its backward to the pose (pose refinement): d(loss)/d(rays) -> d(loss)/d(c2w[:3, :4]), a fixed-order reduction;
 //   * both over a stack of views (one batch spread over V images and V poses; one gradient per pose, each reduced in the
 //     single-view order over its own rays);
+//   * the camera table: one se(3) twist per view composed onto a base pose, and its VJP (the parametrisation pose refinement steps);
 //   * 8-bit output: cast_to_image / cast_to_disparity_image (eval_nerf.py:23-36).
 // Everything here is HBM/latency-bound byte and index work: one thread per ray / pixel, coalesced rows.
 #include "nh_host.h"
@@ -542,6 +543,203 @@ extern "C" int nerfhip_select_rays_bwd(const nerfhip_select_cfg* cfg, const floa
     a.select = 1, a.c2w = c2w, a.ld = c2w_ld, a.inds = inds, a.n = n, a.g_a = g_rays, a.g_b = g_rays_2;
     a.g_stride = g_rays_stride, a.tmp = (float*)tmp;
     return pose_vjp_launch(a, tmp_bytes, g_c2w, stream, "select_rays_bwd");
+}
+
+// ---- camera table: pose[v] = base[v] Exp(xi[v]) and its VJP (se(3) pose refinement) ---------------------------------------------------
+// xi = [w (3), v (3)]; Exp the SE(3) exponential: R = I + c1 W + c2 W^2, t = (I + c2 W + c3 W^2) v, W = hat(w), x = |w|^2 and
+//     c_n(x) = sum_k (-1)^k x^k / (2k + n)!      (c0 = cos, c1 = sin th / th, c2 = (1 - cos th) / th^2, c3 = (th - sin th) / th^3)
+// with  c_n = 1 / n! - x c_{n+2}  and  d c_n / dx = -(c_{n+1} - n c_{n+2}) / 2.  One thread per view and a few hundred flops each: the
+// arithmetic runs in fp64 (inputs and outputs are fp32), so what is left of the error is the last rounding -- and, in the closed form,
+// what nh_sincos hands over.
+//   x < PT_SERIES_BELOW (= 10 > pi^2: every twist of the principal domain |w| <= pi): c4 and c5 from their power series (PT_TERMS terms,
+//       the first one left out < 1e-17 at x = 10), c3, c2, c1 from the recurrence upwards; no square root, no division, and x = 0 gives
+//       1 / n! exactly -- the generators' derivative.
+//   x >= PT_SERIES_BELOW (a twist that wraps round): th = sqrt(x), (s, c) = nh_sincos of the fp32 head of th / 2, corrected to first
+//       order for its fp64 tail; sin th = 2 s c and 1 - cos th = 2 s^2 keep their relative accuracy at every multiple of pi; c3, c4, c5
+//       from the recurrence downwards (x >= 10: 1 / n! - c_n does not cancel below 0.4 / n!).
+constexpr double PT_SERIES_BELOW = 10.0;
+constexpr int PT_TERMS = 13;
+constexpr int PT_THREADS = 256;
+
+namespace {
+
+template <int N>
+NH_DEVICE double pt_series(double x) {  // n! c_n(x) = 1 - x / ((n + 1)(n + 2)) (1 - x / ((n + 3)(n + 4)) (1 - ...))
+    double s = 1.0;
+#pragma unroll
+    for (int k = PT_TERMS; k >= 1; --k) s = 1.0 - x * (1.0 / (double)((2 * k + N - 1) * (2 * k + N))) * s;
+    return s;
+}
+
+// c[n] = c_n(x), n = 1 .. 5
+NH_DEVICE void pt_coefs(double x, double* c) {
+    if (x < PT_SERIES_BELOW) {
+        c[5] = pt_series<5>(x) * (1.0 / 120.0);
+        c[4] = pt_series<4>(x) * (1.0 / 24.0);
+        c[3] = 1.0 / 6.0 - x * c[5];
+        c[2] = 0.5 - x * c[4];
+        c[1] = 1.0 - x * c[3];
+    } else {
+        const double th = sqrt(x), h = 0.5 * th;
+        const float hh = (float)h, hl = (float)(h - (double)hh);
+        float sf, cf;
+        nh_sincos(hh, &sf, &cf);
+        const double s = (double)sf + (double)cf * (double)hl, cc = (double)cf - (double)sf * (double)hl;
+        c[1] = 2.0 * s * cc / th;
+        c[2] = 2.0 * s * s / x;
+        c[3] = (1.0 - c[1]) / x;
+        c[4] = (0.5 - c[2]) / x;
+        c[5] = (1.0 / 6.0 - c[3]) / x;
+    }
+}
+
+struct PoseTableArgs {
+    const float *xi, *base;  // [V][6]; 3 rows of ld floats at base + v * view_stride
+    int64_t view_stride;
+    int ld, num_views;
+};
+
+// the twist and the base of view v; returns whether the twist is exactly zero
+NH_DEVICE bool pt_load(const PoseTableArgs& p, int v, double* w, double* u, const float** base) {
+    const float* xi = p.xi + (int64_t)v * 6;
+    bool zero = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float a = xi[k], b = xi[3 + k];
+        w[k] = (double)a, u[k] = (double)b;
+        zero = zero && a == 0.0f && b == 0.0f;
+    }
+    *base = p.base + (int64_t)v * p.view_stride;
+    return zero;
+}
+
+NH_KERNEL void k_pose_table_fwd(PoseTableArgs p, float* __restrict__ poses) {
+    const int v = (int)(blockIdx.x * PT_THREADS + threadIdx.x);
+    if (v >= p.num_views) return;
+    double w[3], u[3], c[6];
+    const float* b;
+    const bool zero = pt_load(p, v, w, u, &b);
+    float* out = poses + (int64_t)v * 12;
+    if (zero) {  // Exp(0) = I: the base itself, bit for bit (signed zeros included)
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) out[4 * i + j] = b[(int64_t)i * p.ld + j];
+        return;
+    }
+    const double x = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
+    pt_coefs(x, c);
+    const double W[3][3] = {{0.0, -w[2], w[1]}, {w[2], 0.0, -w[0]}, {-w[1], w[0], 0.0}};
+    double D[3][3], t[3];  // D = R - I; t = V v
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        double q = 0.0;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const double w2 = w[i] * w[j] - (i == j ? x : 0.0);  // (W^2)[i][j]
+            D[i][j] = c[1] * W[i][j] + c[2] * w2;
+            q += (c[2] * W[i][j] + c[3] * w2) * u[j];
+        }
+        t[i] = u[i] + q;
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const double r0 = (double)b[(int64_t)i * p.ld], r1 = (double)b[(int64_t)i * p.ld + 1], r2 = (double)b[(int64_t)i * p.ld + 2];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) out[4 * i + j] = (float)(((r0 * D[0][j] + r1 * D[1][j]) + r2 * D[2][j]) + (j == 0 ? r0 : j == 1 ? r1 : r2));
+        out[4 * i + 3] = (float)(((r0 * t[0] + r1 * t[1]) + r2 * t[2]) + (double)b[(int64_t)i * p.ld + 3]);
+    }
+}
+
+// d(loss)/d(xi[v]) from d(loss)/d(poses[v]): G = base_R^T g_R and gt = base_R^T g_t are the cotangents of R and t;
+//   <H, a W + b W^2> has the w-gradient  2 w (a' <H, W> + b' <H, W^2>) + a ax(H) + b ((H + H^T) w - 2 w tr H),
+//   <H, W> = w . ax(H),  <H, W^2> = w^T H w - x tr H,  ax(H) = (H21 - H12, H02 - H20, H10 - H01),
+// once with H = G, (a, b) = (c1, c2) and once with H = gt v^T, (a, b) = (c2, c3); d/dv = V^T gt.
+NH_KERNEL void k_pose_table_bwd(PoseTableArgs p, const float* __restrict__ g_poses, const unsigned char* __restrict__ active,
+                                float* __restrict__ g_xi) {
+    const int v = (int)(blockIdx.x * PT_THREADS + threadIdx.x);
+    if (v >= p.num_views) return;
+    float* out = g_xi + (int64_t)v * 6;
+    if (active && !active[v]) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) out[k] = 0.0f;
+        return;
+    }
+    double w[3], u[3], c[6];
+    const float* b;
+    pt_load(p, v, w, u, &b);
+    const float* g = g_poses + (int64_t)v * 12;
+    double G[3][3], gt[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double b0 = (double)b[k], b1 = (double)b[(int64_t)p.ld + k], b2 = (double)b[2 * (int64_t)p.ld + k];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) G[k][j] = b0 * (double)g[j] + b1 * (double)g[4 + j] + b2 * (double)g[8 + j];
+        gt[k] = b0 * (double)g[3] + b1 * (double)g[7] + b2 * (double)g[11];
+    }
+    const double x = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
+    pt_coefs(x, c);
+    const double d1 = -0.5 * (c[2] - c[3]), d2 = -0.5 * (c[3] - 2.0 * c[4]), d3 = -0.5 * (c[4] - 3.0 * c[5]);  // d c_n / dx
+    // rotation: H = G
+    const double ax[3] = {G[2][1] - G[1][2], G[0][2] - G[2][0], G[1][0] - G[0][1]};
+    const double tr = G[0][0] + G[1][1] + G[2][2];
+    double hw[3], wHw = 0.0;  // (H + H^T) w
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        hw[k] = 0.0;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) hw[k] += (G[k][j] + G[j][k]) * w[j];
+        wHw += 0.5 * hw[k] * w[k];
+    }
+    const double w_ax = w[0] * ax[0] + w[1] * ax[1] + w[2] * ax[2];
+    // translation: H = gt v^T
+    const double at[3] = {u[1] * gt[2] - u[2] * gt[1], u[2] * gt[0] - u[0] * gt[2], u[0] * gt[1] - u[1] * gt[0]};  // v x gt
+    const double wg = w[0] * gt[0] + w[1] * gt[1] + w[2] * gt[2], wu = w[0] * u[0] + w[1] * u[1] + w[2] * u[2];
+    const double gu = gt[0] * u[0] + gt[1] * u[1] + gt[2] * u[2];
+    const double w_at = w[0] * at[0] + w[1] * at[1] + w[2] * at[2];
+    const double through_x = 2.0 * ((d1 * w_ax + d2 * (wHw - x * tr)) + (d2 * w_at + d3 * (wg * wu - x * gu)));
+    const double wxg[3] = {w[1] * gt[2] - w[2] * gt[1], w[2] * gt[0] - w[0] * gt[2], w[0] * gt[1] - w[1] * gt[0]};  // w x gt
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double rot = c[1] * ax[k] + c[2] * (hw[k] - 2.0 * w[k] * tr);
+        const double tra = c[2] * at[k] + c[3] * ((gt[k] * wu + u[k] * wg) - 2.0 * w[k] * gu);
+        out[k] = (float)(w[k] * through_x + (rot + tra));
+        out[3 + k] = (float)(gt[k] + (c[3] * (w[k] * wg - x * gt[k]) - c[2] * wxg[k]));
+    }
+}
+
+int pose_table_check(const float* xi, const float* base, int64_t view_stride, int ld, int num_views, const char* what) {
+    NH_REQUIRE(xi && base, "%s: xi and base must not be NULL", what);
+    NH_REQUIRE(num_views >= 1 && num_views <= NERFHIP_MAX_VIEWS, "%s: num_views must be 1 .. %d (got %d)", what, NERFHIP_MAX_VIEWS,
+               num_views);
+    NH_REQUIRE(ld >= 4, "%s: base_ld must be >= 4 (got %d)", what, ld);
+    NH_REQUIRE(num_views == 1 || view_stride >= 2 * (int64_t)ld + 4,
+               "%s: base_view_stride %lld cannot hold the 3 rows of a pose at row stride %d", what, (long long)view_stride, ld);
+    return NERFHIP_OK;
+}
+
+}  // namespace
+
+extern "C" int nerfhip_pose_table_fwd(const float* xi, const float* base, int64_t base_view_stride, int base_ld, int num_views,
+                                      float* poses, nerfhip_stream_t stream) {
+    const char* what = "pose_table_fwd";
+    int rc = pose_table_check(xi, base, base_view_stride, base_ld, num_views, what);
+    if (rc) return rc;
+    NH_REQUIRE(poses, "%s: poses must not be NULL", what);
+    const PoseTableArgs p = {xi, base, base_view_stride, base_ld, num_views};
+    NH_LAUNCH(k_pose_table_fwd, nh_ceil_div(num_views, PT_THREADS), PT_THREADS, 0, stream, p, poses);
+    return nh_launch_status(what);
+}
+
+extern "C" int nerfhip_pose_table_bwd(const float* xi, const float* base, int64_t base_view_stride, int base_ld, int num_views,
+                                      const float* g_poses, const unsigned char* active, float* g_xi, nerfhip_stream_t stream) {
+    const char* what = "pose_table_bwd";
+    int rc = pose_table_check(xi, base, base_view_stride, base_ld, num_views, what);
+    if (rc) return rc;
+    NH_REQUIRE(g_poses && g_xi, "%s: g_poses and g_xi must not be NULL", what);
+    const PoseTableArgs p = {xi, base, base_view_stride, base_ld, num_views};
+    NH_LAUNCH(k_pose_table_bwd, nh_ceil_div(num_views, PT_THREADS), PT_THREADS, 0, stream, p, g_poses, active, g_xi);
+    return nh_launch_status(what);
 }
 
 // ---- 8-bit output stage (eval_nerf.py:23-36) ---------------------------------------------------------------------------

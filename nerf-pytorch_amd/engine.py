@@ -413,7 +413,7 @@ class TrainEngine:
         return self.loss
 
     def step_on_views(self, images, poses, height, width, focal_length, options, num_random_rays, lr=None, global_rays=None,
-                      pose_grads=None):
+                      pose_grads=None, cameras=None):
         """step_on_image over a resident stack of views: this rank's rays are drawn from ALL of `images` (V, H, W, 3|4) with the
         rays of each generated from its own row of `poses` (V, >=3, 4) -- train_utils.select_training_rays_views --, then `step`.
         Same rank slicing (first = rank * n, or the shard_bounds slice of `global_rays`) over the permutation of V * H * W, same
@@ -421,9 +421,16 @@ class TrainEngine:
         pose_grads: None, or a contiguous float32 (V, 3, 4) tensor on the engine's device: the step also writes
         d(loss)/d(poses[v, :3, :4]) of every view into it (zeros for a view without a ray in the batch): the render backward with
         the ray gradient, then nerfhip_select_rays_views_bwd on the main stream after the two streams joined; still no host
-        synchronisation.  The engine's Adam updates the nets as usual (lr=0 freezes them).  One rank only."""
+        synchronisation.  The engine's Adam updates the nets as usual (lr=0 freezes them).  One rank only.
+        cameras: None, or a cameras.CameraTable on the engine's device (then `poses` must be None and `pose_grads` must not be
+        given): the joint field-and-camera step -- the table composes its poses, the batch is drawn from them, the pose gradients
+        land in the table's own buffer and are pulled back to its twists, the nets take their Adam step and the twists theirs (the
+        table's own lr).  All of it on the main stream after the two streams joined; no host synchronisation.  One rank only."""
         from .parallel import shard_bounds
         from .train_utils import select_training_rays_views, select_training_rays_views_bwd
+        if cameras is not None:
+            return self._step_on_cameras(cameras, images, poses, height, width, focal_length, options, num_random_rays, lr,
+                                         global_rays, pose_grads)
         if global_rays is None:
             n = int(num_random_rays)
             first = self.rank * n
@@ -450,6 +457,41 @@ class TrainEngine:
             select_training_rays_views_bwd(height, width, focal_length, poses, used, self._ray_grad, options, self.ray_grad_coarse,
                                            out=pose_grads)
         self.optimizer_step(lr)
+        return self.loss
+
+    def _step_on_cameras(self, cameras, images, poses, height, width, focal_length, options, num_random_rays, lr, global_rays,
+                         pose_grads):
+        """step_on_views(cameras=...): cameras.poses() -> selection -> forward_backward with the ray gradient -> the per-view pose VJP
+        into cameras.g_poses -> cameras.backward() -> the nets' optimizer_step -> cameras.step()."""
+        from .parallel import shard_bounds
+        from .train_utils import select_training_rays_views, select_training_rays_views_bwd
+        if poses is not None:
+            raise RuntimeError("TrainEngine: with cameras=... the poses come from the table: pass poses=None")
+        if pose_grads is not None:
+            raise RuntimeError("TrainEngine: cameras=... and pose_grads=... exclude each other (the table owns its gradient buffer)")
+        self._no_pose_grad_across_ranks("cameras")
+        if cameras.dev != self.dev:
+            raise RuntimeError("TrainEngine: the camera table lives on %s, the engine on %s" % (cameras.dev, self.dev))
+        if global_rays is None:
+            n = int(num_random_rays)
+            first = self.rank * n
+        else:
+            first, hi = shard_bounds(int(global_rays), self.rank, self.world)
+            n = hi - first
+        table = cameras.poses()
+        with torch.no_grad():
+            rays, target, used = select_training_rays_views(height, width, focal_length, table, images, n, options,
+                                                            seed=self.seed, step=self.step_count, first=first)
+        if getattr(self, "_ray_grad_n", -1) != n:
+            self._ray_grad = torch.empty((n, self.stride), dtype=torch.float32, device=self.dev)
+            self._ray_grad_n = n
+        self.forward_backward(rays, target, first, global_rays, None, self._ray_grad)
+        with torch.cuda.device(self.dev):
+            select_training_rays_views_bwd(height, width, focal_length, table, used, self._ray_grad, options, self.ray_grad_coarse,
+                                           out=cameras.g_poses)
+        cameras.backward()
+        self.optimizer_step(lr)
+        cameras.step()
         return self.loss
 
     @staticmethod
