@@ -12,14 +12,13 @@ d(loss)/d(poses) back to the twists (nerfhip_pose_table_bwd), and the twists are
 import torch
 
 from . import _lib as L
+from .train_utils import _pose_table
 
 
 def _base_table(base, num_views):
     if base.dim() != 3 or base.shape[0] != num_views or base.shape[1] < 3 or base.shape[2] < 4:
         raise RuntimeError("base must be a (V = %d, >=3, >=4) tensor (got shape %s)" % (num_views, tuple(base.shape)))
-    b = base.detach().float()
-    ok = b.stride(2) == 1 and b.stride(1) >= 4 and (b.shape[0] == 1 or b.stride(0) >= 2 * b.stride(1) + 4)
-    return b if ok else b.contiguous()
+    return _pose_table(base, True)
 
 
 def _twists(xi):

@@ -4,7 +4,8 @@
 //     whole image, a full-image get_ray_bundle and three fancy-index gathers;
 //   * its backward to the pose (pose refinement): d(loss)/d(rays) -> d(loss)/d(c2w[:3, :4]), a fixed-order reduction;
 //   * both over a stack of views (one batch spread over V images and V poses; one gradient per pose, each reduced in the
-//     single-view order over its own rays);
+//     single-view order over its own rays): the selection is ONE kernel for one image, a stack of views and the cached bundle,
+//     and both forms of the backward end in ONE sum kernel;
 //   * the camera table: one se(3) twist per view composed onto a base pose, and its VJP (the parametrisation pose refinement steps);
 //   * 8-bit output: cast_to_image / cast_to_disparity_image (eval_nerf.py:23-36).
 // Everything here is HBM/latency-bound byte and index work: one thread per ray / pixel, coalesced rows.
@@ -72,11 +73,15 @@ extern "C" int nerfhip_select_indices(uint64_t seed, uint64_t step, int64_t popu
 }
 
 // ---- fused selection -> rays -> packed rows + target gather ----------------------------------------------------------
-// c2w != NULL: image branch (rays generated for the selected pixels only); else cached branch (rows of the stored
-// ray bundle).  The rest is run_one_iter_of_nerf's prologue (train_utils.py:143-168): viewdirs from the pre-NDC
-// directions, optional ndc_rays with near = 1.0, [o d near far viewdirs] rows.
-NH_KERNEL void k_select_rays(nerfhip_select_cfg s, NhNdc ndc, const float* __restrict__ c2w, int ld,
-                             const float* __restrict__ cached_o, const float* __restrict__ cached_d,
+// poses != NULL: image branch (rays generated for the selected pixels only) over a stack of num_views views; else cached
+// branch (rows of the stored ray bundle).  The rest is run_one_iter_of_nerf's prologue (train_utils.py:143-168): viewdirs
+// from the pre-NDC directions, optional ndc_rays with near = 1.0, [o d near far viewdirs] rows.
+// Image branch, population V * H * W: global index g = v * (H * W) + k addresses view v and the reference's flat select index
+// k of that view.  Pose of view v: poses + v * view_stride, row stride ld; image of view v: targets + v * H * W * channels.
+// Intrinsics, near / far, NDC and viewdirs are shared by all views.  One view (nerfhip_select_rays; the views entry point
+// at V = 1): g is k itself, nothing is divided out.
+NH_KERNEL void k_select_rays(nerfhip_select_cfg s, NhNdc ndc, const float* __restrict__ poses, int64_t view_stride, int ld,
+                             int num_views, const float* __restrict__ cached_o, const float* __restrict__ cached_d,
                              const float* __restrict__ targets, uint64_t population,
                              const int64_t* __restrict__ inds_in, int64_t n, float* __restrict__ rays,
                              float* __restrict__ target_out, int64_t* __restrict__ inds_out) {
@@ -91,13 +96,19 @@ NH_KERNEL void k_select_rays(nerfhip_select_cfg s, NhNdc ndc, const float* __res
     }
     if (inds_out) inds_out[i] = k;
     float o[3], d[3], v[3];
-    int64_t pix;  // row-major position of the target pixel
-    if (c2w) {
+    int64_t pix;  // position of the target pixel: row-major, view by view
+    if (poses) {
+        int64_t view = 0, base = 0;
+        if (num_views > 1) {
+            const int64_t hw = (int64_t)s.height * s.width;
+            view = k / hw, base = view * hw;
+            k -= base;
+        }
         // coords = stack(meshgrid_xy(arange(H), arange(W)), -1).reshape(-1, 2): entry k is (k % H, k / H), used as
         // (row, col) -- train_nerf.py:214-225
         int64_t row = k % s.height, col = k / s.height;
-        nh_pinhole_ray(s.height, s.width, s.focal, c2w, ld, row, col, o, d);
-        pix = row * s.width + col;
+        nh_pinhole_ray(s.height, s.width, s.focal, poses + view * view_stride, ld, row, col, o, d);
+        pix = base + row * s.width + col;
     } else {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -114,27 +125,51 @@ NH_KERNEL void k_select_rays(nerfhip_select_cfg s, NhNdc ndc, const float* __res
     }
 }
 
-static int select_launch(const nerfhip_select_cfg* cfg, const float* c2w, int ld, const float* co, const float* cd,
-                         const float* targets, int64_t population, const int64_t* inds, int64_t n, float* rays,
-                         float* target_out, int64_t* inds_out, nerfhip_stream_t stream, const char* what) {
+static NhNdc ndc_of(const nerfhip_select_cfg* cfg) {
+    return NhNdc{cfg->ndc_near, cfg->ndc_cw, cfg->ndc_ch, cfg->ndc_two_near, cfg->ndc_neg_two_near};
+}
+
+// the checks and the launch of the three selection entry points (`what`: the entry point, for the messages)
+static int select_launch(const char* what, const nerfhip_select_cfg* cfg, int num_views, const float* poses, int64_t view_stride,
+                         int ld, const float* co, const float* cd, const float* targets, int64_t population, const int64_t* inds,
+                         int64_t n, float* rays, float* target_out, int64_t* inds_out, nerfhip_stream_t stream) {
     NH_REQUIRE(cfg && n >= 0 && (n == 0 || rays), "%s: bad arguments", what);
     NH_REQUIRE(!targets || (target_out && cfg->channels >= 1 && cfg->channels <= 4), "%s: bad target arguments", what);
     NH_REQUIRE(population >= 0 && population <= ((int64_t)1 << 32), "%s: bad population", what);
     NH_REQUIRE(inds || (cfg->first >= 0 && cfg->first + n <= population),
                "%s: first + n exceeds the population (sampling is without replacement)", what);
     if (n == 0) return NERFHIP_OK;
-    NhNdc ndc = {cfg->ndc_near, cfg->ndc_cw, cfg->ndc_ch, cfg->ndc_two_near, cfg->ndc_neg_two_near};
-    NH_LAUNCH(k_select_rays, nh_ceil_div(n, 256), 256, 0, stream, *cfg, ndc, c2w, ld, co, cd, targets,
-              (uint64_t)population, inds, n, rays, target_out, inds_out);
+    NH_LAUNCH(k_select_rays, nh_ceil_div(n, 256), 256, 0, stream, *cfg, ndc_of(cfg), poses, view_stride, ld, num_views, co, cd,
+              targets, (uint64_t)population, inds, n, rays, target_out, inds_out);
     return nh_launch_status(what);
+}
+
+// the layout of a table of num_views poses (`name`: "pose" or "base", the parameters' prefix, for the messages)
+static int table_check(int num_views, int64_t view_stride, int ld, const char* name, const char* what) {
+    NH_REQUIRE(num_views >= 1 && num_views <= NERFHIP_MAX_VIEWS, "%s: num_views must be 1 .. %d (got %d)", what, NERFHIP_MAX_VIEWS,
+               num_views);
+    NH_REQUIRE(ld >= 4, "%s: %s_ld must be >= 4 (got %d)", what, name, ld);
+    NH_REQUIRE(num_views == 1 || view_stride >= 2 * (int64_t)ld + 4,
+               "%s: %s_view_stride %lld cannot hold the 3 rows of a pose at row stride %d", what, name, (long long)view_stride, ld);
+    return NERFHIP_OK;
+}
+
+// what both views entry points ask of the pose table
+static int views_check(const nerfhip_select_cfg* cfg, int num_views, const float* poses, int64_t view_stride, int ld,
+                       const char* what) {
+    NH_REQUIRE(cfg && poses && cfg->height > 0 && cfg->width > 0, "%s: bad arguments", what);
+    int rc = table_check(num_views, view_stride, ld, "pose", what);
+    if (rc) return rc;
+    NH_REQUIRE((int64_t)num_views * cfg->height * cfg->width <= ((int64_t)1 << 32), "%s: num_views * height * width exceeds 2^32", what);
+    return NERFHIP_OK;
 }
 
 extern "C" int nerfhip_select_rays(const nerfhip_select_cfg* cfg, const float* c2w, int c2w_ld, const float* image,
                                    const int64_t* select_inds, int64_t n, float* rays, float* target,
                                    int64_t* inds_out, nerfhip_stream_t stream) {
     NH_REQUIRE(cfg && c2w && c2w_ld >= 4 && cfg->height > 0 && cfg->width > 0, "select_rays: bad arguments");
-    return select_launch(cfg, c2w, c2w_ld, nullptr, nullptr, image, (int64_t)cfg->height * cfg->width, select_inds, n,
-                         rays, target, inds_out, stream, "select_rays");
+    return select_launch("select_rays", cfg, 1, c2w, 0, c2w_ld, nullptr, nullptr, image, (int64_t)cfg->height * cfg->width,
+                         select_inds, n, rays, target, inds_out, stream);
 }
 
 extern "C" int nerfhip_select_cached_rays(const nerfhip_select_cfg* cfg, const float* ray_origins,
@@ -142,72 +177,17 @@ extern "C" int nerfhip_select_cached_rays(const nerfhip_select_cfg* cfg, const f
                                           const int64_t* select_inds, int64_t n, float* rays, float* target,
                                           int64_t* inds_out, nerfhip_stream_t stream) {
     NH_REQUIRE(cfg && ray_origins && ray_directions, "select_cached_rays: bad arguments");
-    return select_launch(cfg, nullptr, 0, ray_origins, ray_directions, targets, population, select_inds, n, rays, target,
-                         inds_out, stream, "select_cached_rays");
-}
-
-// ---- the image branch over a stack of views ---------------------------------------------------------------------------
-// Population V * H * W: global index g = v * (H * W) + k addresses view v and the reference's flat select index k of that
-// view (row k % H, col k / H, as in k_select_rays).  Pose of view v: poses + v * view_stride, row stride ld; image of view v:
-// images + v * H * W * channels.  Intrinsics, near / far, NDC and viewdirs are shared by all views.  Row i is, bit for bit,
-// the row k_select_rays writes for (poses[v], images[v], select_inds = {k}): the same helpers on the same operands.
-NH_KERNEL void k_select_rays_views(nerfhip_select_cfg s, NhNdc ndc, const float* __restrict__ poses, int64_t view_stride, int ld,
-                                   const float* __restrict__ images, uint64_t population, const int64_t* __restrict__ inds_in,
-                                   int64_t n, float* __restrict__ rays, float* __restrict__ target_out,
-                                   int64_t* __restrict__ inds_out) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    int64_t g;
-    if (inds_in) {
-        g = inds_in[i];
-    } else {
-        NhPerm p = nh_perm_key(s.seed, s.step, population);
-        g = (int64_t)nh_perm_at(p, (uint64_t)(s.first + i));
-    }
-    if (inds_out) inds_out[i] = g;
-    const int64_t hw = (int64_t)s.height * s.width;
-    const int64_t v = g / hw, k = g - v * hw;
-    const int64_t row = k % s.height, col = k / s.height;
-    float o[3], d[3], vd[3];
-    nh_pinhole_ray(s.height, s.width, s.focal, poses + v * view_stride, ld, row, col, o, d);
-    vd[0] = d[0], vd[1] = d[1], vd[2] = d[2];
-    if (s.ndc) nh_ndc_ray(ndc, o, d);
-    nh_write_ray_row(rays + i * (s.use_viewdirs ? 11 : 8), o, d, s.near, s.far, s.use_viewdirs ? vd : nullptr);
-    if (images) {
-        const float* px = images + (v * hw + row * s.width + col) * s.channels;
-        for (int c = 0; c < s.channels; ++c) target_out[i * s.channels + c] = px[c];
-    }
-}
-
-// what both views entry points ask of the pose table
-static int views_check(const nerfhip_select_cfg* cfg, int num_views, const float* poses, int64_t view_stride, int ld,
-                       const char* what) {
-    NH_REQUIRE(cfg && poses && cfg->height > 0 && cfg->width > 0, "%s: bad arguments", what);
-    NH_REQUIRE(num_views >= 1 && num_views <= NERFHIP_MAX_VIEWS, "%s: num_views must be 1 .. %d (got %d)", what, NERFHIP_MAX_VIEWS,
-               num_views);
-    NH_REQUIRE(ld >= 4, "%s: pose_ld must be >= 4 (got %d)", what, ld);
-    NH_REQUIRE(num_views == 1 || view_stride >= 2 * (int64_t)ld + 4,
-               "%s: pose_view_stride %lld cannot hold the 3 rows of a pose at row stride %d", what, (long long)view_stride, ld);
-    NH_REQUIRE((int64_t)num_views * cfg->height * cfg->width <= ((int64_t)1 << 32), "%s: num_views * height * width exceeds 2^32", what);
-    return NERFHIP_OK;
+    return select_launch("select_cached_rays", cfg, 0, nullptr, 0, 0, ray_origins, ray_directions, targets, population,
+                         select_inds, n, rays, target, inds_out, stream);
 }
 
 extern "C" int nerfhip_select_rays_views(const nerfhip_select_cfg* cfg, int num_views, const float* poses,
                                          int64_t pose_view_stride, int pose_ld, const float* images, const int64_t* select_inds,
                                          int64_t n, float* rays, float* target, int64_t* inds_out, nerfhip_stream_t stream) {
-    const char* what = "select_rays_views";
-    int rc = views_check(cfg, num_views, poses, pose_view_stride, pose_ld, what);
+    int rc = views_check(cfg, num_views, poses, pose_view_stride, pose_ld, "select_rays_views");
     if (rc) return rc;
-    const int64_t population = (int64_t)num_views * cfg->height * cfg->width;
-    NH_REQUIRE(n >= 0 && (n == 0 || rays), "%s: bad arguments", what);
-    NH_REQUIRE(!images || (target && cfg->channels >= 1 && cfg->channels <= 4), "%s: bad target arguments", what);
-    NH_REQUIRE(select_inds || (cfg->first >= 0 && cfg->first + n <= population),
-               "%s: first + n exceeds the population (sampling is without replacement)", what);
-    if (n == 0) return NERFHIP_OK;
-    NhNdc ndc = {cfg->ndc_near, cfg->ndc_cw, cfg->ndc_ch, cfg->ndc_two_near, cfg->ndc_neg_two_near};
-    NH_LAUNCH(k_select_rays_views, nh_ceil_div(n, 256), 256, 0, stream, *cfg, ndc, poses, pose_view_stride, pose_ld, images,
-              (uint64_t)population, select_inds, n, rays, target, inds_out);
-    return nh_launch_status(what);
+    return select_launch("select_rays_views", cfg, num_views, poses, pose_view_stride, pose_ld, nullptr, nullptr, images,
+                         (int64_t)num_views * cfg->height * cfg->width, select_inds, n, rays, target, inds_out, stream);
 }
 
 // ---- pose VJP: d(loss)/d(c2w[:3, :4]) from d(loss)/d(rays) (what autograd gives the reference's pose) --------------------
@@ -218,12 +198,16 @@ extern "C" int nerfhip_select_rays_views(const nerfhip_select_cfg* cfg, int num_
 // k_pose_vjp_part -- G(n) = min(ceil(n / 256), 1024) workgroups of 256 threads; thread t of workgroup b sums rays
 // i = b * 256 + t + q * 256 G (q = 0, 1, ...) in q order, each wave combines its lanes by an xor butterfly, lane 0 of each wave
 // hands its 12 sums to LDS and the workgroup's sums of its 4 waves (in wave order) go to tmp[b][12]; k_pose_vjp_sum -- one
-// workgroup, wave j sums tmp[p][j] over p = lane, lane + 64, ... in p order, then an xor butterfly.
+// workgroup (per view: the views form below runs the same kernel), wave j sums tmp[p][j] over p = lane, lane + 64, ... in p order,
+// then an xor butterfly.
 namespace {
 
 constexpr int PV_THREADS = 256, PV_MAX_WGS = 1024;
 
-int64_t pv_wgs(int64_t n) { return n <= 0 ? 0 : (nh_ceil_div(n, PV_THREADS) < PV_MAX_WGS ? nh_ceil_div(n, PV_THREADS) : PV_MAX_WGS); }
+// G(n) (constexpr: for the host and for the kernels)
+constexpr int64_t pv_wgs(int64_t n) {
+    return n <= 0 ? 0 : ((n + PV_THREADS - 1) / PV_THREADS < PV_MAX_WGS ? (n + PV_THREADS - 1) / PV_THREADS : PV_MAX_WGS);
+}
 
 struct PoseVjpArgs {
     nerfhip_select_cfg s;
@@ -238,6 +222,16 @@ struct PoseVjpArgs {
     int g_stride;
     float* tmp;               // [G][12] workgroup partials
 };
+
+PoseVjpArgs select_vjp_args(const nerfhip_select_cfg* cfg, const float* c2w, int ld, const int64_t* inds, int64_t n,
+                            const float* g_rays, const float* g_rays_2, int g_rays_stride, void* tmp) {
+    PoseVjpArgs a;
+    memset(&a, 0, sizeof(a));
+    a.s = *cfg, a.ndc = ndc_of(cfg);
+    a.select = 1, a.c2w = c2w, a.ld = ld, a.inds = inds, a.n = n, a.g_a = g_rays, a.g_b = g_rays_2;
+    a.g_stride = g_rays_stride, a.tmp = (float*)tmp;
+    return a;
+}
 
 // this ray's 12 terms: t[c * 4 + k] = g_d[c] dc[k] (k < 3), t[c * 4 + 3] = g_o[c]
 // (ray i of the batch, k: its select index / linear pixel id)
@@ -321,12 +315,17 @@ NH_KERNEL void k_pose_vjp_part(PoseVjpArgs a) {
     pv_block_sum(acc, s_part, a.tmp + (int64_t)blockIdx.x * 12);
 }
 
-NH_KERNEL void k_pose_vjp_sum(const float* __restrict__ tmp, int wgs, float* __restrict__ g_c2w) {
-    const int j = nh_wave_in_block(), lane = nh_lane();
+// workgroup `view` sums its partials part[slot0 .. slot0 + wgs - 1][12] into g[view][12].  Single view (cnt == NULL): one
+// workgroup, the first `wgs` partials.  Views: the G(cnt[view]) partials from slot off[view] / 256 + view (k_pose_views_part).
+NH_KERNEL void k_pose_vjp_sum(const float* __restrict__ part, int wgs, const int* __restrict__ cnt, const int* __restrict__ off,
+                              float* __restrict__ g) {
+    const int j = nh_wave_in_block(), lane = nh_lane(), view = (int)blockIdx.x;
+    int64_t slot0 = 0;
+    if (cnt) wgs = (int)pv_wgs(cnt[view]), slot0 = off[view] / PV_THREADS + view;
     float v = 0.0f;
-    for (int p = lane; p < wgs; p += 64) v += tmp[(int64_t)p * 12 + j];
+    for (int q = lane; q < wgs; q += 64) v += part[(slot0 + q) * 12 + j];
     v = nh_wave_sum(v);
-    if (lane == 0) g_c2w[j] = v;
+    if (lane == 0) g[(int64_t)view * 12 + j] = v;
 }
 
 int pose_vjp_launch(const PoseVjpArgs& a, int64_t tmp_bytes, float* g_c2w, nerfhip_stream_t stream, const char* what) {
@@ -338,7 +337,8 @@ int pose_vjp_launch(const PoseVjpArgs& a, int64_t tmp_bytes, float* g_c2w, nerfh
         int rc = nh_launch_status(what);
         if (rc) return rc;
     }
-    NH_LAUNCH(k_pose_vjp_sum, 1, 12 * 64, 0, stream, (const float*)a.tmp, (int)wgs, g_c2w);  // (n == 0: zeros)
+    NH_LAUNCH(k_pose_vjp_sum, 1, 12 * 64, 0, stream, (const float*)a.tmp, (int)wgs, (const int*)nullptr, (const int*)nullptr,
+              g_c2w);  // (n == 0: zeros)
     return nh_launch_status(what);
 }
 
@@ -352,7 +352,7 @@ int pose_vjp_launch(const PoseVjpArgs& a, int64_t tmp_bytes, float* g_c2w, nerfh
 //   k_pose_views_part -- floor(n / 256) + V workgroups; view v owns the slots slot0(v) = off[v] / 256 + v ... + G(n_v) - 1 (disjoint:
 //       G(n_v) <= ceil(n_v / 256) <= floor((off[v] + n_v) / 256) - floor(off[v] / 256) + 1); workgroup w finds its (v, b) by bisection
 //       over slot0, and is partial b of view v: k_pose_vjp_part's loop and sums over list positions b 256 + t + q 256 G(n_v);
-//   k_pose_views_sum -- workgroup v is k_pose_vjp_sum over view v's G(n_v) partials (none: exact zeros).
+//   k_pose_vjp_sum -- V workgroups: workgroup v sums view v's G(n_v) partials (none: exact zeros).
 constexpr int PVG_PER = 4;
 
 struct PoseViewsArgs {
@@ -362,10 +362,6 @@ struct PoseViewsArgs {
     int *cnt, *off, *list;  // [V], [V], [n]
 };
 
-NH_DEVICE int pv_wgs_of(int n) {
-    const int g = (n + PV_THREADS - 1) / PV_THREADS;
-    return g < PV_MAX_WGS ? g : PV_MAX_WGS;
-}
 NH_DEVICE int wave_sum_i(int v) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v += nh_shfl_xor_i(v, m);
@@ -434,7 +430,7 @@ NH_KERNEL void k_pose_views_part(PoseViewsArgs p) {
             top = mid - 1;
     }
     const int off = p.off[v], nv = p.cnt[v];
-    const int b = w - (off / PV_THREADS + v), wgs = pv_wgs_of(nv);
+    const int b = w - (off / PV_THREADS + v), wgs = (int)pv_wgs(nv);
     if (b >= wgs) return;  // (a slot no view uses; the whole workgroup leaves)
     PoseVjpArgs a = p.a;
     a.c2w = p.a.c2w + (int64_t)v * p.view_stride;
@@ -451,18 +447,6 @@ NH_KERNEL void k_pose_views_part(PoseViewsArgs p) {
         for (int j = 0; j < 12; ++j) acc[j] += t[j];
     }
     pv_block_sum(acc, s_part, p.a.tmp + (int64_t)w * 12);
-}
-
-// (cnt == NULL: no rays at all)
-NH_KERNEL void k_pose_views_sum(const float* __restrict__ part, const int* __restrict__ cnt, const int* __restrict__ off,
-                                float* __restrict__ g_poses) {
-    const int j = nh_wave_in_block(), lane = nh_lane(), view = (int)blockIdx.x;
-    const int wgs = cnt ? pv_wgs_of(cnt[view]) : 0;
-    const int64_t slot0 = cnt ? off[view] / PV_THREADS + view : 0;
-    float v = 0.0f;
-    for (int q = lane; q < wgs; q += 64) v += part[(slot0 + q) * 12 + j];
-    v = nh_wave_sum(v);
-    if (lane == 0) g_poses[(int64_t)view * 12 + j] = v;
 }
 
 int64_t pv_views_words(int64_t n, int num_views, int64_t* slots) {
@@ -496,10 +480,7 @@ extern "C" int nerfhip_select_rays_views_bwd(const nerfhip_select_cfg* cfg, int 
     if (n > 0) {
         int64_t slots;
         pv_views_words(n, num_views, &slots);
-        p.a.s = *cfg;
-        p.a.ndc = NhNdc{cfg->ndc_near, cfg->ndc_cw, cfg->ndc_ch, cfg->ndc_two_near, cfg->ndc_neg_two_near};
-        p.a.select = 1, p.a.c2w = poses, p.a.ld = pose_ld, p.a.inds = inds, p.a.n = n, p.a.g_a = g_rays, p.a.g_b = g_rays_2;
-        p.a.g_stride = g_rays_stride, p.a.tmp = (float*)tmp;
+        p.a = select_vjp_args(cfg, poses, pose_ld, inds, n, g_rays, g_rays_2, g_rays_stride, tmp);
         p.num_views = num_views, p.view_stride = pose_view_stride, p.hw = (int64_t)cfg->height * cfg->width;
         p.cnt = (int*)tmp + slots * 12, p.off = p.cnt + num_views, p.list = p.off + num_views;
         NH_LAUNCH(k_pose_views_group, num_views, PV_THREADS, 0, stream, p);
@@ -509,7 +490,8 @@ extern "C" int nerfhip_select_rays_views_bwd(const nerfhip_select_cfg* cfg, int 
         rc = nh_launch_status(what);
         if (rc) return rc;
     }
-    NH_LAUNCH(k_pose_views_sum, num_views, 12 * 64, 0, stream, (const float*)p.a.tmp, (const int*)p.cnt, (const int*)p.off, g_poses);
+    NH_LAUNCH(k_pose_vjp_sum, num_views, 12 * 64, 0, stream, (const float*)p.a.tmp, 0, (const int*)p.cnt, (const int*)p.off,
+              g_poses);  // (n == 0: cnt is NULL, zeros)
     return nh_launch_status(what);
 }
 
@@ -536,13 +518,8 @@ extern "C" int nerfhip_select_rays_bwd(const nerfhip_select_cfg* cfg, const floa
                "select_rays_bwd: bad arguments");
     NH_REQUIRE(g_rays_stride >= (cfg->use_viewdirs ? 11 : 8), "select_rays_bwd: g_rays_stride must cover the %d columns of a ray row",
                cfg->use_viewdirs ? 11 : 8);
-    PoseVjpArgs a;
-    memset(&a, 0, sizeof(a));
-    a.s = *cfg;
-    a.ndc = NhNdc{cfg->ndc_near, cfg->ndc_cw, cfg->ndc_ch, cfg->ndc_two_near, cfg->ndc_neg_two_near};
-    a.select = 1, a.c2w = c2w, a.ld = c2w_ld, a.inds = inds, a.n = n, a.g_a = g_rays, a.g_b = g_rays_2;
-    a.g_stride = g_rays_stride, a.tmp = (float*)tmp;
-    return pose_vjp_launch(a, tmp_bytes, g_c2w, stream, "select_rays_bwd");
+    return pose_vjp_launch(select_vjp_args(cfg, c2w, c2w_ld, inds, n, g_rays, g_rays_2, g_rays_stride, tmp), tmp_bytes, g_c2w, stream,
+                           "select_rays_bwd");
 }
 
 // ---- camera table: pose[v] = base[v] Exp(xi[v]) and its VJP (se(3) pose refinement) ---------------------------------------------------
@@ -708,22 +685,13 @@ NH_KERNEL void k_pose_table_bwd(PoseTableArgs p, const float* __restrict__ g_pos
     }
 }
 
-int pose_table_check(const float* xi, const float* base, int64_t view_stride, int ld, int num_views, const char* what) {
-    NH_REQUIRE(xi && base, "%s: xi and base must not be NULL", what);
-    NH_REQUIRE(num_views >= 1 && num_views <= NERFHIP_MAX_VIEWS, "%s: num_views must be 1 .. %d (got %d)", what, NERFHIP_MAX_VIEWS,
-               num_views);
-    NH_REQUIRE(ld >= 4, "%s: base_ld must be >= 4 (got %d)", what, ld);
-    NH_REQUIRE(num_views == 1 || view_stride >= 2 * (int64_t)ld + 4,
-               "%s: base_view_stride %lld cannot hold the 3 rows of a pose at row stride %d", what, (long long)view_stride, ld);
-    return NERFHIP_OK;
-}
-
 }  // namespace
 
 extern "C" int nerfhip_pose_table_fwd(const float* xi, const float* base, int64_t base_view_stride, int base_ld, int num_views,
                                       float* poses, nerfhip_stream_t stream) {
     const char* what = "pose_table_fwd";
-    int rc = pose_table_check(xi, base, base_view_stride, base_ld, num_views, what);
+    NH_REQUIRE(xi && base, "%s: xi and base must not be NULL", what);
+    int rc = table_check(num_views, base_view_stride, base_ld, "base", what);
     if (rc) return rc;
     NH_REQUIRE(poses, "%s: poses must not be NULL", what);
     const PoseTableArgs p = {xi, base, base_view_stride, base_ld, num_views};
@@ -734,7 +702,8 @@ extern "C" int nerfhip_pose_table_fwd(const float* xi, const float* base, int64_
 extern "C" int nerfhip_pose_table_bwd(const float* xi, const float* base, int64_t base_view_stride, int base_ld, int num_views,
                                       const float* g_poses, const unsigned char* active, float* g_xi, nerfhip_stream_t stream) {
     const char* what = "pose_table_bwd";
-    int rc = pose_table_check(xi, base, base_view_stride, base_ld, num_views, what);
+    NH_REQUIRE(xi && base, "%s: xi and base must not be NULL", what);
+    int rc = table_check(num_views, base_view_stride, base_ld, "base", what);
     if (rc) return rc;
     NH_REQUIRE(g_poses && g_xi, "%s: g_poses and g_xi must not be NULL", what);
     const PoseTableArgs p = {xi, base, base_view_stride, base_ld, num_views};

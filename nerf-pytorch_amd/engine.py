@@ -383,34 +383,14 @@ class TrainEngine:
         stream after the two streams joined, nerfhip_select_rays_bwd; still no host synchronisation).  The engine's Adam
         updates the nets as usual (lr=0 freezes them); a pose parametrisation of one's own takes the gradient with
         torch.autograd.backward(pose_expr[:3, :4], pose_grad).  One rank only."""
-        from .parallel import shard_bounds
         from .train_utils import select_training_rays, select_training_rays_bwd
-        if global_rays is None:
-            n = int(num_random_rays)
-            first = self.rank * n
-        else:
-            first, hi = shard_bounds(int(global_rays), self.rank, self.world)
-            n = hi - first
-        if pose_grad is None:
-            rays, target, _ = select_training_rays(height, width, focal_length, pose, image, n, options, seed=self.seed,
-                                                   step=self.step_count, first=first)
-            return self.step(rays, target, ray_offset=first, lr=lr, global_rays=global_rays)
-        self._no_pose_grad_across_ranks("pose_grad")
-        if (not isinstance(pose_grad, torch.Tensor) or pose_grad.device != self.dev or pose_grad.dtype != torch.float32
-                or tuple(pose_grad.shape) != (3, 4) or not pose_grad.is_contiguous()):
-            raise RuntimeError("TrainEngine: pose_grad must be a contiguous float32 (3, 4) tensor on %s" % self.dev)
-        with torch.no_grad():
-            rays, target, used = select_training_rays(height, width, focal_length, pose, image, n, options, seed=self.seed,
-                                                      step=self.step_count, first=first)
-        if getattr(self, "_ray_grad_n", -1) != n:
-            self._ray_grad = torch.empty((n, self.stride), dtype=torch.float32, device=self.dev)
-            self._ray_grad_n = n
-        self.forward_backward(rays, target, first, global_rays, None, self._ray_grad)
-        with torch.cuda.device(self.dev):
-            select_training_rays_bwd(height, width, focal_length, pose, used, self._ray_grad, options, self.ray_grad_coarse,
-                                     out=pose_grad)
-        self.optimizer_step(lr)
-        return self.loss
+        if pose_grad is not None:
+            self._no_pose_grad_across_ranks("pose_grad")
+            self._check_pose_grads("pose_grad", pose_grad, (3, 4))
+        return self._step_on_selection(
+            lambda **kw: select_training_rays(height, width, focal_length, pose, image, options=options, **kw),
+            lambda used, g, g2: select_training_rays_bwd(height, width, focal_length, pose, used, g, options, g2, out=pose_grad),
+            pose_grad, num_random_rays, lr, global_rays)
 
     def step_on_views(self, images, poses, height, width, focal_length, options, num_random_rays, lr=None, global_rays=None,
                       pose_grads=None, cameras=None):
@@ -426,11 +406,39 @@ class TrainEngine:
         given): the joint field-and-camera step -- the table composes its poses, the batch is drawn from them, the pose gradients
         land in the table's own buffer and are pulled back to its twists, the nets take their Adam step and the twists theirs (the
         table's own lr).  All of it on the main stream after the two streams joined; no host synchronisation.  One rank only."""
-        from .parallel import shard_bounds
         from .train_utils import select_training_rays_views, select_training_rays_views_bwd
         if cameras is not None:
-            return self._step_on_cameras(cameras, images, poses, height, width, focal_length, options, num_random_rays, lr,
-                                         global_rays, pose_grads)
+            if poses is not None:
+                raise RuntimeError("TrainEngine: with cameras=... the poses come from the table: pass poses=None")
+            if pose_grads is not None:
+                raise RuntimeError("TrainEngine: cameras=... and pose_grads=... exclude each other (the table owns its gradient buffer)")
+            self._no_pose_grad_across_ranks("cameras")
+            if cameras.dev != self.dev:
+                raise RuntimeError("TrainEngine: the camera table lives on %s, the engine on %s" % (cameras.dev, self.dev))
+            # cameras.poses() -> selection -> forward_backward with the ray gradient -> the per-view pose VJP into cameras.g_poses ->
+            # cameras.backward() -> the nets' optimizer_step -> cameras.step()
+            poses, pose_grads = cameras.poses(), cameras.g_poses
+        elif pose_grads is not None:
+            self._no_pose_grad_across_ranks("pose_grads")
+            self._check_pose_grads("pose_grads", pose_grads, (poses.shape[0], 3, 4))
+        return self._step_on_selection(
+            lambda **kw: select_training_rays_views(height, width, focal_length, poses, images, options=options, **kw),
+            lambda used, g, g2: select_training_rays_views_bwd(height, width, focal_length, poses, used, g, options, g2, out=pose_grads),
+            pose_grads, num_random_rays, lr, global_rays, cameras)
+
+    def _check_pose_grads(self, name, g, shape):
+        if (not isinstance(g, torch.Tensor) or g.device != self.dev or g.dtype != torch.float32 or tuple(g.shape) != shape
+                or not g.is_contiguous()):
+            raise RuntimeError("TrainEngine: %s must be a contiguous float32 (%s) tensor on %s"
+                               % (name, ", ".join(str(d) for d in shape), self.dev))
+
+    def _step_on_selection(self, select, vjp, pose_grads, num_random_rays, lr, global_rays, cameras=None):
+        """What step_on_image and step_on_views share: this rank's slice of the step's permutation, `select(num_random_rays=, seed=,
+        step=, first=)` -> (rays, target, select indices), then `step`; or, with `pose_grads` (the buffer `vjp` fills),
+        forward_backward with the ray gradient, `vjp(select indices, ray gradient, coarse ray gradient)` on the main stream after
+        the two streams joined, optimizer_step.  `cameras` (the table whose poses and gradient buffer the callables use): its
+        backward() follows the VJP, its step() the nets' Adam."""
+        from .parallel import shard_bounds
         if global_rays is None:
             n = int(num_random_rays)
             first = self.rank * n
@@ -438,60 +446,21 @@ class TrainEngine:
             first, hi = shard_bounds(int(global_rays), self.rank, self.world)
             n = hi - first
         if pose_grads is None:
-            rays, target, _ = select_training_rays_views(height, width, focal_length, poses, images, n, options, seed=self.seed,
-                                                         step=self.step_count, first=first)
+            rays, target, _ = select(num_random_rays=n, seed=self.seed, step=self.step_count, first=first)
             return self.step(rays, target, ray_offset=first, lr=lr, global_rays=global_rays)
-        self._no_pose_grad_across_ranks("pose_grads")
-        if (not isinstance(pose_grads, torch.Tensor) or pose_grads.device != self.dev or pose_grads.dtype != torch.float32
-                or tuple(pose_grads.shape) != (poses.shape[0], 3, 4) or not pose_grads.is_contiguous()):
-            raise RuntimeError("TrainEngine: pose_grads must be a contiguous float32 (%d, 3, 4) tensor on %s"
-                               % (poses.shape[0], self.dev))
         with torch.no_grad():
-            rays, target, used = select_training_rays_views(height, width, focal_length, poses, images, n, options,
-                                                            seed=self.seed, step=self.step_count, first=first)
+            rays, target, used = select(num_random_rays=n, seed=self.seed, step=self.step_count, first=first)
         if getattr(self, "_ray_grad_n", -1) != n:
             self._ray_grad = torch.empty((n, self.stride), dtype=torch.float32, device=self.dev)
             self._ray_grad_n = n
         self.forward_backward(rays, target, first, global_rays, None, self._ray_grad)
         with torch.cuda.device(self.dev):
-            select_training_rays_views_bwd(height, width, focal_length, poses, used, self._ray_grad, options, self.ray_grad_coarse,
-                                           out=pose_grads)
+            vjp(used, self._ray_grad, self.ray_grad_coarse)
+        if cameras is not None:
+            cameras.backward()
         self.optimizer_step(lr)
-        return self.loss
-
-    def _step_on_cameras(self, cameras, images, poses, height, width, focal_length, options, num_random_rays, lr, global_rays,
-                         pose_grads):
-        """step_on_views(cameras=...): cameras.poses() -> selection -> forward_backward with the ray gradient -> the per-view pose VJP
-        into cameras.g_poses -> cameras.backward() -> the nets' optimizer_step -> cameras.step()."""
-        from .parallel import shard_bounds
-        from .train_utils import select_training_rays_views, select_training_rays_views_bwd
-        if poses is not None:
-            raise RuntimeError("TrainEngine: with cameras=... the poses come from the table: pass poses=None")
-        if pose_grads is not None:
-            raise RuntimeError("TrainEngine: cameras=... and pose_grads=... exclude each other (the table owns its gradient buffer)")
-        self._no_pose_grad_across_ranks("cameras")
-        if cameras.dev != self.dev:
-            raise RuntimeError("TrainEngine: the camera table lives on %s, the engine on %s" % (cameras.dev, self.dev))
-        if global_rays is None:
-            n = int(num_random_rays)
-            first = self.rank * n
-        else:
-            first, hi = shard_bounds(int(global_rays), self.rank, self.world)
-            n = hi - first
-        table = cameras.poses()
-        with torch.no_grad():
-            rays, target, used = select_training_rays_views(height, width, focal_length, table, images, n, options,
-                                                            seed=self.seed, step=self.step_count, first=first)
-        if getattr(self, "_ray_grad_n", -1) != n:
-            self._ray_grad = torch.empty((n, self.stride), dtype=torch.float32, device=self.dev)
-            self._ray_grad_n = n
-        self.forward_backward(rays, target, first, global_rays, None, self._ray_grad)
-        with torch.cuda.device(self.dev):
-            select_training_rays_views_bwd(height, width, focal_length, table, used, self._ray_grad, options, self.ray_grad_coarse,
-                                           out=cameras.g_poses)
-        cameras.backward()
-        self.optimizer_step(lr)
-        cameras.step()
+        if cameras is not None:
+            cameras.step()
         return self.loss
 
     @staticmethod

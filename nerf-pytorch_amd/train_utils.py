@@ -322,33 +322,67 @@ def _select_cfg(height, width, focal_length, options, channels, seed, step, firs
                        channels=int(channels), seed=int(seed) & 0xFFFFFFFFFFFFFFFF, step=int(step), first=int(first))
 
 
-def _select_pose(pose):
-    p = pose.detach().float()
-    return p if p.stride(-1) == 1 else p.contiguous()
+def _pose_table(poses, views):
+    """The pose(s) as the kernels read them: float32, unit column stride (and, with a view axis, rows and views that do not
+    overlap); a table that is laid out otherwise is copied.  A 2-D pose is the table with no view axis (`views` False)."""
+    if views and (poses.dim() != 3 or poses.shape[1] < 3 or poses.shape[2] < 4):
+        raise RuntimeError("poses must be a (V, >=3, >=4) tensor (got shape %s)" % (tuple(poses.shape),))
+    p = poses.detach().float()
+    ok = p.stride(-1) == 1 and (not views or (p.stride(1) >= 4 and (p.shape[0] == 1 or p.stride(0) >= 2 * p.stride(1) + 4)))
+    return p if ok else p.contiguous()
 
 
-def _select_launch(cfg, pose, image, select_inds, n):
-    dev = pose.device
+def _select_launch(cfg, poses, images, select_inds, n, views):
+    """nerfhip_select_rays (`poses` one pose, `images` one image) or, with a view axis, nerfhip_select_rays_views."""
+    dev = poses.device
     rays = torch.empty((n, 11 if cfg.use_viewdirs else 8), dtype=torch.float32, device=dev)
-    target = torch.empty((n, cfg.channels), dtype=torch.float32, device=dev) if image is not None else None
+    target = torch.empty((n, cfg.channels), dtype=torch.float32, device=dev) if images is not None else None
     used = torch.empty((n,), dtype=torch.int64, device=dev)
-    with L.launch_on(pose, image, select_inds, rays) as st:
-        L.get_lib().select_rays(C.byref(cfg), pose.data_ptr(), pose.stride(-2), image.data_ptr() if image is not None else None,
-                                select_inds.data_ptr() if select_inds is not None else None, n, rays.data_ptr(),
-                                target.data_ptr() if target is not None else None, used.data_ptr(), st)
+    lib = L.get_lib()
+    table = (poses.shape[0], poses.data_ptr(), poses.stride(0), poses.stride(1)) if views else (poses.data_ptr(), poses.stride(-2))
+    with L.launch_on(poses, images, select_inds, rays) as st:
+        (lib.select_rays_views if views else lib.select_rays)(
+            C.byref(cfg), *table, images.data_ptr() if images is not None else None,
+            select_inds.data_ptr() if select_inds is not None else None, n, rays.data_ptr(),
+            target.data_ptr() if target is not None else None, used.data_ptr(), st)
     return rays, target, used
 
 
+def _pose_vjp(cfg, poses, used, g_rays, g_rays_2, views, out=None):
+    """nerfhip_select_rays_bwd / nerfhip_select_rays_views_bwd on the current stream: d(loss)/d(pose[:3, :4]) (3 x 4 float32; with a
+    view axis V x 3 x 4) of the rays the select call with `cfg` / `poses` made at the select indices `used`, from d(loss)/d(rays)
+    rows g_rays (+ g_rays_2, added row by row)."""
+    lib = L.get_lib()
+    n = used.numel()
+    if views:
+        nv = poses.shape[0]
+        tb = lib.pose_grad_views_tmp_bytes(n, nv)
+        if tb < 0:
+            raise RuntimeError("select_training_rays_views: %d rays over %d views is outside the kernel's limits" % (n, nv))
+        fn, table, shape = lib.select_rays_views_bwd, (nv, poses.data_ptr(), poses.stride(0), poses.stride(1)), (nv, 3, 4)
+    else:
+        tb = lib.pose_grad_tmp_bytes(n)
+        fn, table, shape = lib.select_rays_bwd, (poses.data_ptr(), poses.stride(-2)), (3, 4)
+    tmp = torch.empty(tb // 4 + 1, dtype=torch.float32, device=poses.device)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=poses.device)
+    with L.launch_on(poses, used, g_rays, g_rays_2, tmp, out) as st:
+        fn(C.byref(cfg), *table, used.data_ptr(), n, g_rays.data_ptr(), g_rays_2.data_ptr() if g_rays_2 is not None else None,
+           g_rays.stride(0), tmp.data_ptr(), tb, out.data_ptr(), st)
+    return out
+
+
 class _SelectRays(torch.autograd.Function):
-    """select_training_rays with the pose VJP (nerfhip_select_rays_bwd): the gradient flows from the rays to the pose (its
-    [:3, :4] entries); target and select indices carry none.  The forward issues exactly the launch of the plain call."""
+    """select_training_rays / select_training_rays_views with the pose VJP (nerfhip_select_rays_bwd / nerfhip_select_rays_views_bwd):
+    the gradient flows from the rays to the [:3, :4] entries of the pose (of every pose of the table); targets and select indices
+    carry none.  The forward issues exactly the launch of the plain call."""
 
     @staticmethod
-    def forward(ctx, pose, cfg, image, select_inds, n):
-        p = _select_pose(pose)
-        rays, target, used = _select_launch(cfg, p, image, select_inds, n)
-        ctx.keep = (cfg, p, used)
-        ctx.pose_shape = (pose.shape, pose.dtype)
+    def forward(ctx, poses, cfg, images, select_inds, n, views):
+        p = _pose_table(poses, views)
+        rays, target, used = _select_launch(cfg, p, images, select_inds, n, views)
+        ctx.keep = (cfg, p, used, views)
+        ctx.poses_shape = (poses.shape, poses.dtype)
         ctx.mark_non_differentiable(*[t for t in (target, used) if t is not None])
         ctx.set_materialize_grads(False)
         return rays, target, used
@@ -356,29 +390,39 @@ class _SelectRays(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_rays, _g_target, _g_used):
         if g_rays is None:
-            return (None,) * 5
-        cfg, p, used = ctx.keep
-        g34 = _pose_vjp(cfg, p, used, g_rays.contiguous().float(), None)
-        shape, dtype = ctx.pose_shape
+            return (None,) * 6
+        cfg, p, used, views = ctx.keep
+        g34 = _pose_vjp(cfg, p, used, g_rays.contiguous().float(), None, views)
+        shape, dtype = ctx.poses_shape
         g = torch.zeros(shape, dtype=dtype, device=p.device)
-        g[:3, :4] = g34.to(dtype)
-        return g, None, None, None, None
+        g[..., :3, :4] = g34.to(dtype)
+        return g, None, None, None, None, None
 
 
-def _pose_vjp(cfg, pose, used, g_rays, g_rays_2, out=None):
-    """nerfhip_select_rays_bwd on the current stream: d(loss)/d(pose[:3, :4]) (3 x 4 float32) of the rays the select call with
-    `cfg` / `pose` made at the select indices `used`, from d(loss)/d(rays) rows g_rays (+ g_rays_2, added row by row)."""
-    lib = L.get_lib()
-    n = used.numel()
-    tb = lib.pose_grad_tmp_bytes(n)
-    tmp = torch.empty(tb // 4 + 1, dtype=torch.float32, device=pose.device)
-    if out is None:
-        out = torch.empty((3, 4), dtype=torch.float32, device=pose.device)
-    with L.launch_on(pose, used, g_rays, g_rays_2, tmp, out) as st:
-        lib.select_rays_bwd(C.byref(cfg), pose.data_ptr(), pose.stride(-2), used.data_ptr(), n, g_rays.data_ptr(),
-                            g_rays_2.data_ptr() if g_rays_2 is not None else None, g_rays.stride(0), tmp.data_ptr(), tb,
-                            out.data_ptr(), st)
-    return out
+def _select(cfg, poses, images, select_inds, n, views):
+    if images is not None:
+        images = images.detach().float().contiguous()
+    if select_inds is not None:
+        select_inds = torch.as_tensor(select_inds, dtype=torch.int64, device=poses.device).contiguous()
+    if torch.is_grad_enabled() and poses.requires_grad:
+        return _SelectRays.apply(poses, cfg, images, select_inds, n, views)
+    return _select_launch(cfg, _pose_table(poses, views), images, select_inds, n, views)
+
+
+def _select_bwd(what, cfg, poses, select_inds, g_rays, g_rays_2, out, views):
+    """The checks of g_rays / g_rays_2 / out (`what`: the public function, for the messages), then the VJP."""
+    for name, g in (("g_rays", g_rays), ("g_rays_2", g_rays_2)):
+        if g is not None and (g.dtype != torch.float32 or g.dim() != 2 or g.stride(1) != 1
+                              or g.shape[1] < (11 if cfg.use_viewdirs else 8)):
+            raise RuntimeError("%s: %s must be float32 rows of the ray layout (got %s, shape %s)" % (what, name, g.dtype, tuple(g.shape)))
+    if g_rays_2 is not None and (g_rays_2.shape != g_rays.shape or g_rays_2.stride() != g_rays.stride()):
+        raise RuntimeError("%s: g_rays_2 must have the layout of g_rays" % what)
+    p = _pose_table(poses, views)
+    shape = (p.shape[0], 3, 4) if views else (3, 4)
+    if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous()):
+        raise RuntimeError("%s: out must be a contiguous float32 (%s) tensor" % (what, ", ".join(str(d) for d in shape)))
+    used = torch.as_tensor(select_inds, dtype=torch.int64, device=poses.device).contiguous()
+    return _pose_vjp(cfg, p, used, g_rays, g_rays_2, views, out)
 
 
 def select_training_rays(height, width, focal_length, pose, image, num_random_rays, options, select_inds=None, seed=0,
@@ -390,17 +434,9 @@ def select_training_rays(height, width, focal_length, pose, image, num_random_ra
     predict_and_render_radiance or TrainEngine.step --, target (N, C), select_inds (N,)).
     With a `pose` that requires grad the rays are differentiable w.r.t. it (pose refinement, as the reference's torch
     arithmetic is): the backward runs the pose VJP kernel (select_training_rays_bwd)."""
-    n = int(num_random_rays)
     channels = 3 if image is None else image.shape[-1]
     cfg = _select_cfg(height, width, focal_length, options, channels, seed, step, first)
-    if image is not None:
-        image = image.detach().float().contiguous()
-    dev = pose.device
-    if select_inds is not None:
-        select_inds = torch.as_tensor(select_inds, dtype=torch.int64, device=dev).contiguous()
-    if torch.is_grad_enabled() and pose.requires_grad:
-        return _SelectRays.apply(pose, cfg, image, select_inds, n)
-    return _select_launch(cfg, _select_pose(pose), image, select_inds, n)
+    return _select(cfg, pose, image, select_inds, int(num_random_rays), False)
 
 
 def select_training_rays_bwd(height, width, focal_length, pose, select_inds, g_rays, options, g_rays_2=None, out=None):
@@ -409,83 +445,7 @@ def select_training_rays_bwd(height, width, focal_length, pose, select_inds, g_r
     `select_inds` (its third output), from d(loss)/d(rays) rows `g_rays` (+ `g_rays_2`, added row by row: e.g. the coarse and
     the fine net's parts that TrainEngine.forward_backward(ray_grad=...) leaves).  Enqueued on the current stream."""
     cfg = _select_cfg(height, width, focal_length, options, 3, 0, 0, 0)
-    for name, g in (("g_rays", g_rays), ("g_rays_2", g_rays_2)):
-        if g is not None and (g.dtype != torch.float32 or g.dim() != 2 or g.stride(1) != 1
-                              or g.shape[1] < (11 if cfg.use_viewdirs else 8)):
-            raise RuntimeError("select_training_rays_bwd: %s must be float32 rows of the ray layout (got %s, shape %s)"
-                               % (name, g.dtype, tuple(g.shape)))
-    if g_rays_2 is not None and (g_rays_2.shape != g_rays.shape or g_rays_2.stride() != g_rays.stride()):
-        raise RuntimeError("select_training_rays_bwd: g_rays_2 must have the layout of g_rays")
-    if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != (3, 4) or not out.is_contiguous()):
-        raise RuntimeError("select_training_rays_bwd: out must be a contiguous float32 (3, 4) tensor")
-    used = torch.as_tensor(select_inds, dtype=torch.int64, device=pose.device).contiguous()
-    return _pose_vjp(cfg, _select_pose(pose), used, g_rays, g_rays_2, out)
-
-
-# ---- one batch over a stack of views --------------------------------------------------------------------------------------------
-def _select_poses(poses):
-    if poses.dim() != 3 or poses.shape[1] < 3 or poses.shape[2] < 4:
-        raise RuntimeError("poses must be a (V, >=3, >=4) tensor (got shape %s)" % (tuple(poses.shape),))
-    p = poses.detach().float()
-    ok = p.stride(2) == 1 and p.stride(1) >= 4 and (p.shape[0] == 1 or p.stride(0) >= 2 * p.stride(1) + 4)
-    return p if ok else p.contiguous()
-
-
-def _select_views_launch(cfg, poses, images, select_inds, n):
-    dev = poses.device
-    rays = torch.empty((n, 11 if cfg.use_viewdirs else 8), dtype=torch.float32, device=dev)
-    target = torch.empty((n, cfg.channels), dtype=torch.float32, device=dev) if images is not None else None
-    used = torch.empty((n,), dtype=torch.int64, device=dev)
-    with L.launch_on(poses, images, select_inds, rays) as st:
-        L.get_lib().select_rays_views(C.byref(cfg), poses.shape[0], poses.data_ptr(), poses.stride(0), poses.stride(1),
-                                      images.data_ptr() if images is not None else None,
-                                      select_inds.data_ptr() if select_inds is not None else None, n, rays.data_ptr(),
-                                      target.data_ptr() if target is not None else None, used.data_ptr(), st)
-    return rays, target, used
-
-
-def _pose_views_vjp(cfg, poses, used, g_rays, g_rays_2, out=None):
-    """nerfhip_select_rays_views_bwd on the current stream: d(loss)/d(poses[:, :3, :4]) (V x 3 x 4 float32)."""
-    lib = L.get_lib()
-    n, nv = used.numel(), poses.shape[0]
-    tb = lib.pose_grad_views_tmp_bytes(n, nv)
-    if tb < 0:
-        raise RuntimeError("select_training_rays_views: %d rays over %d views is outside the kernel's limits" % (n, nv))
-    tmp = torch.empty(tb // 4 + 1, dtype=torch.float32, device=poses.device)
-    if out is None:
-        out = torch.empty((nv, 3, 4), dtype=torch.float32, device=poses.device)
-    with L.launch_on(poses, used, g_rays, g_rays_2, tmp, out) as st:
-        lib.select_rays_views_bwd(C.byref(cfg), nv, poses.data_ptr(), poses.stride(0), poses.stride(1), used.data_ptr(), n,
-                                  g_rays.data_ptr(), g_rays_2.data_ptr() if g_rays_2 is not None else None, g_rays.stride(0),
-                                  tmp.data_ptr(), tb, out.data_ptr(), st)
-    return out
-
-
-class _SelectRaysViews(torch.autograd.Function):
-    """select_training_rays_views with the per-view pose VJP (nerfhip_select_rays_views_bwd): the gradient flows from the rays to
-    the [:, :3, :4] entries of the pose table; targets and indices carry none.  The forward issues exactly the launch of the plain
-    call."""
-
-    @staticmethod
-    def forward(ctx, poses, cfg, images, select_inds, n):
-        p = _select_poses(poses)
-        rays, target, used = _select_views_launch(cfg, p, images, select_inds, n)
-        ctx.keep = (cfg, p, used)
-        ctx.poses_shape = (poses.shape, poses.dtype)
-        ctx.mark_non_differentiable(*[t for t in (target, used) if t is not None])
-        ctx.set_materialize_grads(False)
-        return rays, target, used
-
-    @staticmethod
-    def backward(ctx, g_rays, _g_target, _g_used):
-        if g_rays is None:
-            return (None,) * 5
-        cfg, p, used = ctx.keep
-        g34 = _pose_views_vjp(cfg, p, used, g_rays.contiguous().float(), None)
-        shape, dtype = ctx.poses_shape
-        g = torch.zeros(shape, dtype=dtype, device=p.device)
-        g[:, :3, :4] = g34.to(dtype)
-        return g, None, None, None, None
+    return _select_bwd("select_training_rays_bwd", cfg, pose, select_inds, g_rays, g_rays_2, out, False)
 
 
 def select_training_rays_views(height, width, focal_length, poses, images, num_random_rays, options, select_inds=None, seed=0,
@@ -497,19 +457,13 @@ def select_training_rays_views(height, width, focal_length, poses, images, num_r
     select_inds) as select_training_rays does; every row equals the row that call makes for (poses[v], images[v], [k]).
     With `poses` requiring grad the rays are differentiable w.r.t. them: the backward runs the per-view pose VJP
     (select_training_rays_views_bwd), so every view with a ray in the batch gets its gradient from one step."""
-    n = int(num_random_rays)
     channels = 3 if images is None else images.shape[-1]
     cfg = _select_cfg(height, width, focal_length, options, channels, seed, step, first)
-    if images is not None:
-        if images.dim() != 4 or images.shape[0] != poses.shape[0] or tuple(images.shape[1:3]) != (cfg.height, cfg.width):
-            raise RuntimeError("select_training_rays_views: images must be (V, H, W, C) with V = %d, H = %d, W = %d (got %s)"
-                               % (poses.shape[0], cfg.height, cfg.width, tuple(images.shape)))
-        images = images.detach().float().contiguous()
-    if select_inds is not None:
-        select_inds = torch.as_tensor(select_inds, dtype=torch.int64, device=poses.device).contiguous()
-    if torch.is_grad_enabled() and poses.requires_grad:
-        return _SelectRaysViews.apply(poses, cfg, images, select_inds, n)
-    return _select_views_launch(cfg, _select_poses(poses), images, select_inds, n)
+    if images is not None and (images.dim() != 4 or images.shape[0] != poses.shape[0]
+                               or tuple(images.shape[1:3]) != (cfg.height, cfg.width)):
+        raise RuntimeError("select_training_rays_views: images must be (V, H, W, C) with V = %d, H = %d, W = %d (got %s)"
+                           % (poses.shape[0], cfg.height, cfg.width, tuple(images.shape)))
+    return _select(cfg, poses, images, select_inds, int(num_random_rays), True)
 
 
 def select_training_rays_views_bwd(height, width, focal_length, poses, select_inds, g_rays, options, g_rays_2=None, out=None):
@@ -518,18 +472,7 @@ def select_training_rays_views_bwd(height, width, focal_length, poses, select_in
     `select_inds` of the forward.  Entry v is bit-identical to select_training_rays_bwd on the rays of view v alone (in batch
     order); a view without a ray gets zeros.  Enqueued on the current stream; no host synchronisation."""
     cfg = _select_cfg(height, width, focal_length, options, 3, 0, 0, 0)
-    what = "select_training_rays_views_bwd"
-    for name, g in (("g_rays", g_rays), ("g_rays_2", g_rays_2)):
-        if g is not None and (g.dtype != torch.float32 or g.dim() != 2 or g.stride(1) != 1
-                              or g.shape[1] < (11 if cfg.use_viewdirs else 8)):
-            raise RuntimeError("%s: %s must be float32 rows of the ray layout (got %s, shape %s)" % (what, name, g.dtype, tuple(g.shape)))
-    if g_rays_2 is not None and (g_rays_2.shape != g_rays.shape or g_rays_2.stride() != g_rays.stride()):
-        raise RuntimeError("%s: g_rays_2 must have the layout of g_rays" % what)
-    p = _select_poses(poses)
-    if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != (p.shape[0], 3, 4) or not out.is_contiguous()):
-        raise RuntimeError("%s: out must be a contiguous float32 (%d, 3, 4) tensor" % (what, p.shape[0]))
-    used = torch.as_tensor(select_inds, dtype=torch.int64, device=poses.device).contiguous()
-    return _pose_views_vjp(cfg, p, used, g_rays, g_rays_2, out)
+    return _select_bwd("select_training_rays_views_bwd", cfg, poses, select_inds, g_rays, g_rays_2, out, True)
 
 
 def select_cached_training_rays(cache_dict, num_random_rays, options, select_inds=None, seed=0, step=0, first=0):

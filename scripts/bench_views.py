@@ -27,8 +27,9 @@ LINES = {
     "fern_4x64": dict(H=378, W=504, focal=407.5, nc=64, nf=64, no_ndc=False, noise=1.0, near=0.0, far=1.0, views=20,
                       model=dict(num_layers=4, hidden_size=64, skip_connect_every=3, num_encoding_fn_xyz=6, num_encoding_fn_dir=4)),
 }
-SEL = ("k_select_rays", "k_select_rays_views")
-VJP = ("k_pose_vjp_part", "k_pose_vjp_sum", "k_pose_views_group", "k_pose_views_part", "k_pose_views_sum")
+SEL = ("k_select_rays",)                                                       # (one kernel: a single image is a stack of one view)
+VJP1 = ("k_pose_vjp_part", "k_pose_vjp_sum")                                    # the single-view VJP's two launches
+VJPV = ("k_pose_views_group", "k_pose_views_part", "k_pose_vjp_sum")             # the views VJP's three (the sum kernel is shared)
 
 
 def kernel_us(lib, names):
@@ -76,15 +77,15 @@ def launches(n, V, reps):
     _, _, used1 = T.select_training_rays(H, W, 555.5555, poses[0], imgs[0], n, opts, seed=1, step=0)
     out, out1 = torch.empty(V, 3, 4, device=dev), torch.empty(3, 4, device=dev)
     profiled(lib, reps, lambda: T.select_training_rays_views(H, W, 555.5555, poses, imgs, n, opts, seed=1, step=0))
-    res.update(kernel_us(lib, SEL))
+    res["select_views_us"] = kernel_us(lib, SEL)[SEL[0]]
     profiled(lib, reps, lambda: T.select_training_rays(H, W, 555.5555, poses[0], imgs[0], n, opts, seed=1, step=0))
-    res.update(kernel_us(lib, SEL))
+    res["select_single_us"] = kernel_us(lib, SEL)[SEL[0]]
     profiled(lib, reps, lambda: T.select_training_rays_views_bwd(H, W, 555.5555, poses, used, g, opts, g2, out=out))
-    res.update(kernel_us(lib, VJP))
+    res["views_vjp_kernels_us"] = kernel_us(lib, VJPV)
     profiled(lib, reps, lambda: T.select_training_rays_bwd(H, W, 555.5555, poses[0], used1, g, opts, g2, out=out1))
-    res.update(kernel_us(lib, VJP))
-    res["views_vjp_us"] = round(sum(res[k] for k in VJP[2:]), 2)
-    res["single_vjp_us"] = round(sum(res[k] for k in VJP[:2]), 2)
+    res["single_vjp_kernels_us"] = kernel_us(lib, VJP1)
+    res["views_vjp_us"] = round(sum(res["views_vjp_kernels_us"].values()), 2)
+    res["single_vjp_us"] = round(sum(res["single_vjp_kernels_us"].values()), 2)
     res["views_without_a_ray"] = int((torch.bincount(used // (H * W), minlength=V) == 0).sum())
     res["finite"] = bool(torch.isfinite(out).all())
     return res

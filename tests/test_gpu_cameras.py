@@ -48,7 +48,7 @@ def test_entry_points_reject_bad_arguments(gpu):
 # ---- drop-in autograd ---------------------------------------------------------------------------------------------------------------
 def test_dropin_twist_gradient_is_the_kernel_on_the_views_node_gradient():
     """se3_poses -> select_training_rays_views -> a cotangent on the rays -> backward(): xi.grad is, bit for bit, nerfhip_pose_table_bwd
-    applied to the poses gradient the _SelectRaysViews node gives a leaf table for the same rays; and the plain call (xi without
+    applied to the poses gradient the _SelectRays node gives a leaf table for the same rays; and the plain call (xi without
     grad) returns the bits of the autograd path's forward."""
     import nerf_pytorch_amd as N
     import nerf_pytorch_amd._lib as L

@@ -2,7 +2,8 @@
 of tests/backends.py: tests/test_views.py runs them on the wave emulator, tests/test_gpu_views.py on the product library.
 
 Every comparison with the single-view entry points is on the bits (the contract of include/nerfhip.h); the fp64 reference and the
-error bound of the VJP are those of tests/pose_vjp.py with n = the number of rays of the view.
+error bound of the VJP are those of tests/pose_vjp.py with n = the number of rays of the view.  The single-view and the cached
+entry points run the views kernels (one selection kernel, one sum kernel): their own edges are pinned here as well.
 """
 import ctypes as C
 
@@ -92,15 +93,58 @@ def case_selection(b, ndc, view, channels, layout):
     assert tgt is not None or not channels
 
 
-def case_single_view_is_select_rays(b):
+def case_single_view_is_select_rays(b, ndc, view, channels):
+    """nerfhip_select_rays is the V = 1 case of nerfhip_select_rays_views: the same rays, targets and indices on the bits."""
     H, W, n = 20, 16, 64
     focal = float(np.float32(17.5))
-    c2w = pose(3)
-    img = np.random.default_rng(1).random((H, W, 4), dtype=np.float32)
-    cfg = cfg_of(b, H, W, focal, False, True, 4, seed=11, step=3, first=64)
-    rays, tgt, used = select_views(b, cfg, c2w[None], 16, 4, 1, img[None], n)
-    r1, t1, u1 = b.select_rays(H, W, focal, c2w, img, n, 2.0, 6.0, seed=11, step=3, first=64)
-    assert np.array_equal(used, u1) and np.array_equal(bits(rays), bits(r1)) and np.array_equal(bits(tgt), bits(t1))
+    c2w = pose(3, llff=ndc)
+    img = np.random.default_rng(1).random((H, W, channels), dtype=np.float32) if channels else None
+    cfg = cfg_of(b, H, W, focal, ndc, view, channels or 3, seed=11, step=3, first=64)
+    rays, tgt, used = select_views(b, cfg, c2w[None], 16, 4, 1, img[None] if channels else None, n)
+    r1, t1, u1 = b.select_rays(H, W, focal, c2w, img, n, 2.0, 6.0, use_viewdirs=view, ndc=ndc, seed=11, step=3, first=64)
+    assert np.all(np.isfinite(rays)) and rays.shape == (n, 11 if view else 8)
+    assert np.array_equal(used, u1) and np.array_equal(bits(rays), bits(r1))
+    assert (tgt is None and t1 is None) if not channels else np.array_equal(bits(tgt), bits(t1))
+
+
+def case_single_view_row_stride(b):
+    """The single-view entry points at a row stride other than 4: the pose embedded in a NaN-filled buffer with c2w_ld = 5 gives the
+    bits of the contiguous 4 x 4 pose, forward and backward (H=5, W=7, every pixel once, by explicit indices)."""
+    H, W = 5, 7
+    focal = float(np.float32(6.3))
+    rng = np.random.default_rng(17)
+    inds = rng.permutation(H * W).astype(np.int64)
+    img = rng.random((H, W, 3), dtype=np.float32)
+    g = rng.normal(size=(H * W, 11)).astype(np.float32)
+    for ndc in (False, True):
+        c2w = pose(5, llff=ndc)
+        wide = np.full((3, 5), np.nan, dtype=np.float32)   # (select_one / one_bwd pass shape[1] as c2w_ld)
+        wide[:, :4] = c2w[:3, :4]
+        cfg = cfg_of(b, H, W, focal, ndc, True)
+        rays, tgt = select_one(b, cfg, c2w, img, inds)
+        rays5, tgt5 = select_one(b, cfg, wide, img, inds)
+        assert np.all(np.isfinite(rays))
+        assert np.array_equal(bits(rays), bits(rays5)) and np.array_equal(bits(tgt), bits(tgt5))
+        got, got5 = one_bwd(b, cfg, c2w, inds, g, None, 11), one_bwd(b, cfg, wide, inds, g, None, 11)
+        assert np.all(np.isfinite(got)) and np.array_equal(bits(got), bits(got5))
+
+
+def case_cached_rows_are_select_rays_rows(b, view):
+    """The cached branch of the selection kernel: the rows of the stored bundle (nerfhip_ray_bundle: pixel row * W + col) are, bit for
+    bit, the rows nerfhip_select_rays generates at the transposed index convention (k -> row k % H, col k / H); no NDC."""
+    H, W = 5, 7
+    focal = float(np.float32(6.3))
+    rng = np.random.default_rng(23)
+    c2w = pose(5)
+    img = rng.random((H, W, 3), dtype=np.float32)
+    k = rng.permutation(H * W).astype(np.int64)
+    ro, rd = b.ray_bundle(H, W, focal, c2w)
+    cached = (k % H) * W + k // H
+    rays_c, tgt_c, used_c = b.select_cached_rays(H, W, focal, ro, rd, np.ascontiguousarray(img.reshape(-1, 3)), H * W, 2.0, 6.0,
+                                                 inds=cached, use_viewdirs=view)
+    rays, tgt = select_one(b, cfg_of(b, H, W, focal, False, view), c2w, img, k)
+    assert np.array_equal(used_c, cached) and np.all(np.isfinite(rays_c))
+    assert np.array_equal(bits(rays_c), bits(rays)) and np.array_equal(bits(tgt_c), bits(tgt))
 
 
 def case_explicit_indices_and_rank_slices(b):
@@ -216,6 +260,26 @@ def case_vjp(b, which, ndc, view, two):
     # the embedded [V, 3, 4] table gives the same bits as the contiguous one
     table, vs, ld = pose_table(poses, "embedded")
     assert np.array_equal(bits(got), bits(views_bwd(b, cfg, table, vs, ld, V, inds, g, g2, stride)))
+
+
+def case_single_view_vjp_sum_edges(b, n):
+    """The sum kernel's single-view form at its edges -- n = 1 (one partial), 257 (two), 256 * 64 + 1 (65 partials: one more than a
+    wave has lanes, so the lane-strided loop takes a second trip): within the fp64 bound, and the bits of the views form at V = 1."""
+    rng = np.random.default_rng(53 + n)
+    H, W, focal = VH, VW, VFOCAL
+    c2w = pose(44, llff=True)
+    cfg = cfg_of(b, H, W, focal, True, True)
+    inds = rng.integers(0, H * W, size=n).astype(np.int64)
+    g = rng.normal(size=(n, 11)).astype(np.float32)
+    assert P.wgs(n) == {1: 1, 257: 2, 16385: 65}[n]
+    got = one_bwd(b, cfg, c2w, inds, g, None, 11)
+    assert np.all(np.isfinite(got))
+    assert np.array_equal(bits(got), bits(views_bwd(b, cfg, c2w[None], 16, 4, 1, inds, g, None, 11)[0]))
+    want = P.oracle_select_vjp(H, W, focal, c2w, inds, g.astype(np.float64), True, True)
+    bound = P.bound(n, P.magnitude(H, W, focal, c2w, inds, True, g_rays=np.abs(g.astype(np.float64)), ndc=True, view=True))
+    err = np.abs(got.astype(np.float64) - want)
+    print("single-view VJP, n = %d: worst error / bound = %.3f" % (n, float((err / np.maximum(bound, 1e-300)).max())))
+    assert np.all(err <= bound), (n, float((err / np.maximum(bound, 1e-300)).max()))
 
 
 def case_vjp_no_rays(b):
