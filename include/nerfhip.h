@@ -513,6 +513,30 @@ int nerfhip_pose_table_fwd(const float* xi, const float* base, int64_t base_view
 int nerfhip_pose_table_bwd(const float* xi, const float* base, int64_t base_view_stride, int base_ld, int num_views,
                            const float* g_poses, const unsigned char* active, float* g_xi, nerfhip_stream_t stream);
 
+/* ---- coarse-to-fine window over the encoding's frequency bands (BARF; joint pose-and-field training from poor poses) --------
+ * Every encoding column enters the net through a linear layer, and W (w (.) gamma(x)) = (W diag(w)) gamma(x): the net on a windowed
+ * encoding is the unwindowed net run on theta_eff = theta (.) m, m = 1 except on the weight columns that multiply a windowed band.
+ * So the forward packs its image from theta_eff, the input / ray gradient reads theta_eff where it reads the flat vector
+ * (nerfhip_mlp_bwd_input, nerfhip_render_bwd_rays), and d(loss)/d(theta) = m (.) d(loss)/d(theta_eff); no other kernel changes.
+ * Band k of an encoding owns the six columns sin(3), cos(3) of frequency k (nerf/nerf_helpers.py:130-157); the include_input
+ * columns are never windowed.  The caller evaluates w_k(alpha) = (1 - cos(pi clamp(alpha - k, 0, 1))) / 2 on the host in fp64 and
+ * rounds once to fp32: the kernels take the weights by value and do one IEEE multiply per windowed entry. */
+typedef struct nerfhip_window {
+    float xyz[16]; /* band weights of the xyz encoding (entries beyond num_encoding_fn_xyz are not read) */
+    float dir[10]; /* ... of the direction encoding */
+} nerfhip_window;
+/* Host-only.  host_table: uint8[nerfhip_plan_num_params]: one code per entry of the flat parameter vector -- 0 = not windowed,
+ * 1 + k = multiplies xyz band k, 17 + k = direction band k.  Windowed: the encoding columns of layer1.weight, the trailing dim_xyz
+ * columns of every skip layer's layers_xyz.{i}.weight (cat(h, xyz): hidden first), the trailing dim_dir columns of
+ * layers_dir.0.weight (cat(feat, view)). */
+int nerfhip_plan_window_index(nerfhip_plan_t plan, uint8_t* host_table);
+/* out[i] = codes[i] ? params[i] * weight(codes[i]) : params[i], weight(1 + k) = w->xyz[k], weight(17 + k) = w->dir[k] (a code above
+ * 26 is read as 0).  params, out: dev float[n], distinct buffers; codes: dev uint8[n].  One launch. */
+int nerfhip_window_params(const float* params, const uint8_t* codes, int64_t n, const nerfhip_window* w, float* out,
+                          nerfhip_stream_t stream);
+/* The same multiply in place on a flat gradient: an entry of a closed band (weight 0) becomes an exact zero. */
+int nerfhip_window_grads(float* g_params, const uint8_t* codes, int64_t n, const nerfhip_window* w, nerfhip_stream_t stream);
+
 /* cast_to_image (eval_nerf.py:23-29): ToPILImage of a float image = mul(255) then byte conversion (truncation).
  * rgb: dev [pixels, in_channels >= 3] (first three used); out: dev uint8 [pixels, 3] (H, W, 3 byte order). */
 int nerfhip_cast_to_image(const float* rgb, int in_channels, int64_t pixels, uint8_t* out, nerfhip_stream_t stream);

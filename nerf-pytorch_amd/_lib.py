@@ -56,6 +56,11 @@ class SelectCfg(C.Structure):
                 ("first", c_i64)]
 
 
+class Window(C.Structure):
+    """nerfhip_window: the band weights of the two encodings, passed by pointer and copied into the kernel arguments."""
+    _fields_ = [("xyz", C.c_float * 16), ("dir", C.c_float * 10)]
+
+
 _PROTOS = {
     "nerfhip_version": (C.c_int, []),
     "nerfhip_last_error": (C.c_char_p, []),
@@ -142,6 +147,9 @@ _PROTOS = {
                                                 c_f, c_i64, c_f, c_f]),
     "nerfhip_pose_table_fwd": (C.c_int, [c_f, c_f, c_i64, C.c_int, C.c_int, c_f, c_f]),
     "nerfhip_pose_table_bwd": (C.c_int, [c_f, c_f, c_i64, C.c_int, C.c_int, c_f, c_f, c_f, c_f]),
+    "nerfhip_plan_window_index": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "nerfhip_window_params": (C.c_int, [c_f, c_f, c_i64, C.POINTER(Window), c_f, c_f]),
+    "nerfhip_window_grads": (C.c_int, [c_f, c_f, c_i64, C.POINTER(Window), c_f]),
     "nerfhip_cast_to_image": (C.c_int, [c_f, C.c_int, c_i64, c_f, c_f]),
     "nerfhip_cast_to_disparity_image": (C.c_int, [c_f, c_i64, c_f, c_f, c_f]),
 }

@@ -19,12 +19,13 @@ void nh_set_error(const char* fmt, ...) {
 extern "C" const char* nerfhip_last_error(void) { return g_err; }
 extern "C" int nerfhip_version(void) {
 #ifdef NH_DIAG  // (make variant: an A/B or diagnostic build -- nh_diag.h; the Python package refuses it)
-    return 107 + NH_DIAG_VERSION_FLAG;
+    return 108 + NH_DIAG_VERSION_FLAG;
 #else
-    return 107;  // (102: round 6 -- the compacted backward's three entry points; 103: + the fused backward modes 3 / 4 of 64-wide nets; 104: + mode 5;
+    return 108;  // (102: round 6 -- the compacted backward's three entry points; 103: + the fused backward modes 3 / 4 of 64-wide nets; 104: + mode 5;
                  // 105: + the pose VJP, nerfhip_pose_grad_tmp_bytes / nerfhip_ray_bundle_bwd / nerfhip_select_rays_bwd;
                  // 106: + batches over a stack of views, nerfhip_select_rays_views / _views_bwd / nerfhip_pose_grad_views_tmp_bytes;
-                 // 107: + the camera table, nerfhip_pose_table_fwd / nerfhip_pose_table_bwd)
+                 // 107: + the camera table, nerfhip_pose_table_fwd / nerfhip_pose_table_bwd;
+                 // 108: + the encoding window, nerfhip_plan_window_index / nerfhip_window_params / nerfhip_window_grads)
 #endif
 }
 extern "C" int nerfhip_is_emulated(void) {
@@ -423,6 +424,62 @@ extern "C" int nerfhip_pack_weights(const float* params, const int32_t* table, i
     NH_REQUIRE(params && table && packed && n >= 0, "pack_weights: bad arguments");
     NH_LAUNCH(k_pack_weights, nh_ceil_div(n, 256), 256, 0, stream, params, table, n, packed);
     return nh_launch_status("pack_weights");
+}
+
+// ---- encoding window (nerfhip.h: theta_eff = theta (.) m, d/d(theta) = m (.) d/d(theta_eff)) ------------------------------------
+// The 26 band weights ride in the kernel arguments.  A thread takes four consecutive entries: one 16-byte load / store and one
+// 4-byte code load where the pointers allow it (`vec`, decided by the host) and the four lie inside n, else entry by entry.
+struct NhWindowLut {
+    float w[26];  // code c = 1 .. 26 -> w[c - 1]
+};
+NH_DEVICE float nh_window_mul(float p, unsigned c, const NhWindowLut& lut) { return (c - 1u) < 26u ? p * lut.w[c - 1u] : p; }
+
+NH_DEVICE void nh_window_quad(const float* src, const uint8_t* codes, int64_t n, int vec, const NhWindowLut& lut, float* dst) {
+    const int64_t i0 = 4 * ((int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+    if (i0 >= n) return;
+    if (vec && i0 + 4 <= n) {
+        const float4 p = *(const float4*)(src + i0);
+        const uint32_t c = *(const uint32_t*)(codes + i0);
+        *(float4*)(dst + i0) = make_float4(nh_window_mul(p.x, c & 255u, lut), nh_window_mul(p.y, (c >> 8) & 255u, lut),
+                                           nh_window_mul(p.z, (c >> 16) & 255u, lut), nh_window_mul(p.w, c >> 24, lut));
+        return;
+    }
+    for (int64_t i = i0; i < n && i < i0 + 4; ++i) dst[i] = nh_window_mul(src[i], codes[i], lut);
+}
+
+NH_KERNEL void k_window_params(const float* __restrict__ params, const uint8_t* __restrict__ codes, int64_t n, int vec,
+                               NhWindowLut lut, float* __restrict__ out) {
+    nh_window_quad(params, codes, n, vec, lut, out);
+}
+NH_KERNEL void k_window_grads(float* g, const uint8_t* __restrict__ codes, int64_t n, int vec, NhWindowLut lut) {
+    nh_window_quad(g, codes, n, vec, lut, g);
+}
+
+static NhWindowLut nh_window_lut(const nerfhip_window* w) {
+    NhWindowLut lut;
+    for (int k = 0; k < 16; ++k) lut.w[k] = w->xyz[k];
+    for (int k = 0; k < 10; ++k) lut.w[16 + k] = w->dir[k];
+    return lut;
+}
+static int nh_window_vec(const void* a, const void* b, const void* codes) {
+    return (((uintptr_t)a | (uintptr_t)b) & 15u) == 0 && ((uintptr_t)codes & 3u) == 0;
+}
+
+extern "C" int nerfhip_window_params(const float* params, const uint8_t* codes, int64_t n, const nerfhip_window* w, float* out,
+                                     nerfhip_stream_t stream) {
+    if (n == 0) return NERFHIP_OK;  // empty input: nothing to launch, pointers may be NULL
+    NH_REQUIRE(params && codes && w && out && out != params && n >= 0, "window_params: bad arguments");
+    NH_LAUNCH(k_window_params, nh_ceil_div(nh_ceil_div(n, 4), 256), 256, 0, stream, params, codes, n, nh_window_vec(params, out, codes),
+              nh_window_lut(w), out);
+    return nh_launch_status("window_params");
+}
+
+extern "C" int nerfhip_window_grads(float* g_params, const uint8_t* codes, int64_t n, const nerfhip_window* w, nerfhip_stream_t stream) {
+    if (n == 0) return NERFHIP_OK;  // empty input: nothing to launch, pointers may be NULL
+    NH_REQUIRE(g_params && codes && w && n >= 0, "window_grads: bad arguments");
+    NH_LAUNCH(k_window_grads, nh_ceil_div(nh_ceil_div(n, 4), 256), 256, 0, stream, g_params, codes, n,
+              nh_window_vec(g_params, g_params, codes), nh_window_lut(w));
+    return nh_launch_status("window_grads");
 }
 
 // ---- loss (train_nerf.py:244-258) ------------------------------------------------------------------------------------

@@ -926,6 +926,25 @@ extern "C" int nerfhip_plan_pack_index(nerfhip_plan_t plan, int32_t* host_table)
     return NERFHIP_OK;
 }
 
+// One code per flat parameter (nerfhip.h): which encoding band, if any, the entry multiplies.  Read off the tensor table: the
+// encoding columns are the trailing enc_cols columns of the tensor (all of layer1.weight's), raw input first when included.
+extern "C" int nerfhip_plan_window_index(nerfhip_plan_t plan, uint8_t* host_table) {
+    NH_REQUIRE(plan && host_table, "plan_window_index: bad arguments");
+    memset(host_table, 0, (size_t)plan->nparams);
+    auto mark = [&](int tensor, int enc_cols, int include_input, int first_code) {
+        const NhTensor& t = plan->tensors[tensor];
+        const int col0 = t.cols - enc_cols;
+        for (int r = 0; r < t.rows; ++r)
+            for (int c = include_input ? 3 : 0; c < enc_cols; ++c)
+                host_table[t.off + (int64_t)r * t.cols + col0 + c] = (uint8_t)(first_code + (c - (include_input ? 3 : 0)) / 6);
+    };
+    mark(plan->t_layer1_w, plan->Dx, plan->cfg.include_input_xyz, 1);
+    for (int i = 0; i < plan->L - 1; ++i)
+        if (plan->is_skip(i)) mark(plan->t_xyz_w[i], plan->Dx, plan->cfg.include_input_xyz, 1);
+    if (plan->view) mark(plan->t_dir_w, plan->Dd, plan->cfg.include_input_dir, 17);
+    return NERFHIP_OK;
+}
+
 extern "C" int nerfhip_plan_set_freqs(nerfhip_plan_t plan, const float* freqs_xyz, const float* freqs_dir) {
     NH_REQUIRE(plan && freqs_xyz, "plan_set_freqs: bad arguments");
     for (int k = 0; k < 16; ++k) {

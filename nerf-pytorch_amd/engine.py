@@ -31,7 +31,7 @@ from .parallel import allreduce_gradients
 class TrainEngine:
     def __init__(self, model_coarse, model_fine, num_coarse, num_fine, perturb=True, lindisp=False, white_background=False,
                  noise_std=0.0, lr=5e-3, betas=(0.9, 0.999), eps=1e-8, seed=0, process_group=None, world_size=None,
-                 rank=None, overlap=None, always_reduce=False, backward=None):
+                 rank=None, overlap=None, always_reduce=False, backward=None, window=None, total_steps=None):
         self.lib = L.get_lib()
         self.mc, self.mf = model_coarse, model_fine if num_fine > 0 else None
         self.dev = model_coarse.flat_params.device
@@ -90,11 +90,46 @@ class TrainEngine:
         self._zero_frac = self._stats.frac   # last known fraction of all-zero d(loss)/d(raw) rows per net (updated in place)
         # steps run dense / compacted / recomputed / fused / fused over the list / fused over the stash, per net ("auto")
         self.backward_modes_used = {"coarse": [0, 0, 0, 0, 0, 0], "fine": [0, 0, 0, 0, 0, 0]}
+        # coarse-to-fine encoding window (BARF; FlexibleNeRFModel.set_encoding_window), set on both nets for every step: None -- the
+        # engine sets none (a window set on the models by hand is honoured); (start, end) in units of step_count / total_steps -- per
+        # encoding alpha = (progress - start) / (end - start) * num_encoding_fn: closed up to `start`, fully open from `end` on;
+        # or a callable step -> (alpha_xyz, alpha_dir)
+        if window is not None and not callable(window):
+            start, end = (float(v) for v in window)
+            if not end > start or not total_steps or total_steps <= 0:
+                raise ValueError("TrainEngine: window=(start, end) needs end > start and total_steps > 0 (got %r, total_steps=%r)"
+                                 % (window, total_steps))
+            window = (start, end)
+        self.window, self.total_steps = window, total_steps
+        self._set_window()
         self.t_vals = linspace01(num_coarse, self.dev)
         self.u_det = linspace01(num_fine, self.dev) if num_fine > 0 else None
         self.repack()
 
+    def window_alphas(self, step):
+        """(alpha_xyz, alpha_dir) of the schedule at step `step` (None without one)."""
+        if self.window is None:
+            return None
+        if callable(self.window):
+            return tuple(self.window(step))
+        start, end = self.window
+        t = (step / float(self.total_steps) - start) / (end - start)
+        return (t * self.mc.cfg["num_encoding_fn_xyz"], t * self.mc.cfg["num_encoding_fn_dir"])
+
+    def _set_window(self):
+        """Puts both nets under the schedule's window of the step about to run (step_count); True if that changed a window."""
+        alphas = self.window_alphas(self.step_count)
+        changed = False
+        if alphas is not None:
+            for _, m in self._nets:
+                if m.encoding_window != alphas:
+                    m.set_encoding_window(*alphas)
+                    changed = True
+        return changed
+
     def repack(self):
+        # (under an encoding window each pack is preceded by the theta_eff kernel; the buffer it fills is what a step's ray gradient
+        # multiplies by)
         self.packed_c = self.mc._packed(True)
         self.packed_f = self.mf._packed(True) if self.mf is not None else None
 
@@ -184,6 +219,8 @@ class TrainEngine:
         gscale = 1.0 if global_rays is None else float(n) * self.world / float(global_rays)
         if self.backward == "auto":
             self._choose_backward_modes()
+        if self._set_window():   # (optimizer_step packed for this step already; only a step_count or schedule changed by hand gets here)
+            self.repack()
         self._prepare(n)
         b = self._bufs
         nf = self.cfg.num_fine
@@ -216,8 +253,9 @@ class TrainEngine:
             g_rays_c, (tmp_c, tmp_f, tmpb) = self._ray_grad_bufs(n)
             if g_rays_c is None:
                 g_rays_c = ray_grad
-            pc_flat = self.mc.flat_params.data_ptr()
-            pf_flat = self.mf.flat_params.data_ptr() if nf > 0 else None
+            # (the flat vectors as the nets run: theta_eff under an encoding window, as the last repack left it)
+            pc_flat = self.mc._theta_eff(refresh=False).data_ptr()
+            pf_flat = self.mf._theta_eff(refresh=False).data_ptr() if nf > 0 else None
         self._pending = []
         with torch.cuda.device(self.dev):
             main, side = self._streams()
@@ -233,6 +271,7 @@ class TrainEngine:
                 else:
                     lib.render_bwd_rays(*bwd_head, C.byref(cot_c), *bwd_tail, L.PART_COARSE, pc_flat, pf_flat, tmp_c.data_ptr(),
                                         tmpb, g_rays_c.data_ptr(), stream_handle)
+                self.mc._window_grads(gc, self.mc._window_w, stream_handle)   # (behind its backward, ahead of its all-reduce)
 
             if two:
                 e1, e2 = self._ev
@@ -249,6 +288,7 @@ class TrainEngine:
                 else:
                     lib.render_bwd_rays(*bwd_head, C.byref(cot_f), *bwd_tail, L.PART_FINE, pc_flat, pf_flat, tmp_f.data_ptr(), tmpb,
                                         ray_grad.data_ptr(), st)
+                self.mf._window_grads(gf, self.mf._window_w, st)
                 if self._reduce:  # in flight while the coarse backward computes
                     self._pending.append(allreduce_gradients(gf, self.pg, async_op=True, single_rank=True))
             if two:
@@ -362,6 +402,7 @@ class TrainEngine:
                 lib.adam_step(self.mf.flat_params.data_ptr(), self.grad[n0:].data_ptr(), self.exp_avg[n0:].data_ptr(),
                               self.exp_avg_sq[n0:].data_ptr(), self.nf_params, lr, b1, b2, self.eps, self.step_count, scale,
                               st)
+        self._set_window()   # (the window of the step that follows: its images are packed here)
         self.repack()
 
     def step(self, rays, target, ray_offset=0, lr=None, global_rays=None, draws=None, ray_grad=None):

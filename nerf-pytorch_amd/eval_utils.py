@@ -79,7 +79,7 @@ def render_pose_rows(height, width, focal_length, pose, model_coarse, model_fine
     independent, so no rank ever needs another rank's data and there is no collective; the concatenation of the ranks'
     blocks in rank order is bit-identical to the image one rank renders (parallel.gather_image_rows does that for a
     writer on rank 0).  Returns (outputs, (row_lo, row_hi)) with `outputs` the 6-tuple of run_one_iter_of_nerf shaped
-    (rows, width, .)."""
+    (rows, width, .).  The nets render under their current encoding window (FlexibleNeRFModel.set_encoding_window), if one is set."""
     from .nerf_helpers import get_rays_at_pixels
     from .parallel import shard_bounds
     from .train_utils import run_one_iter_of_nerf

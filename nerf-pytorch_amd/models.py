@@ -14,7 +14,7 @@ import torch
 
 from . import _lib as L
 from . import backward_mode as BM
-from .nerf_helpers import frequency_bands_cpu
+from .nerf_helpers import encoding_window_weights, frequency_bands_cpu
 
 
 PRECISIONS = {"fp32": L.PRECISION_FP32, "f16x3": L.PRECISION_F16X3, "f16x3_fwd": L.PRECISION_F16X3_FWD,
@@ -84,7 +84,9 @@ class _MlpFunction(torch.autograd.Function):
                         stash.data_ptr() if stash is not None else None, st)
         ctx.model, ctx.m, ctx.stash, ctx.packed = model, m, stash, packed
         # (the input gradient multiplies by the weights of this forward: keep a copy only if it will be asked for)
-        ctx.flat = model._flat.clone() if (need and need_x) else None
+        # (... multiplied by the encoding window of this forward, if one is set: theta_eff)
+        ctx.flat = model._theta_eff(copy=True) if (need and need_x) else None
+        ctx.window = model._window_w   # (the node's backward windows its gradient as its forward was windowed, whatever is set by then)
         return out
 
     @staticmethod
@@ -98,6 +100,7 @@ class _MlpFunction(torch.autograd.Function):
         with L.launch_on(g, scratch, gflat, ctx.packed, ctx.stash) as st:
             lib.mlp_bwd(model._plan, ctx.packed.data_ptr(), g.data_ptr(), m, ctx.stash.data_ptr(), scratch.data_ptr(), sb,
                         gflat.data_ptr(), st)
+        model._window_grads(gflat, ctx.window)
         gx = None
         if ctx.flat is not None and ctx.needs_input_grad[1]:
             gx = torch.empty((m, model.dim_xyz + model.dim_dir), dtype=torch.float32, device=g.device)
@@ -161,6 +164,8 @@ class FlexibleNeRFModel(torch.nn.Module):
         self._inf_owner = None
         self._inf_table = None
         self._inf_packed = None
+        self._window_codes = None
+        self._eff = None
         if getattr(self, "inference_precision", "fp32") != "fp32":
             self._inf_owner = _PlanHandle(self.cfg, PRECISIONS[self.inference_precision])
         self._fused_ok = None
@@ -272,6 +277,73 @@ class FlexibleNeRFModel(torch.nn.Module):
         self._fused_ok = (self._plan, ok)
         return ok
 
+    # ---- coarse-to-fine encoding window (BARF) --------------------------------------------------------------------------
+    encoding_window = None   # (alpha_xyz, alpha_dir) as given to set_encoding_window, or None
+    _window_w = None         # the band weights of that window (_lib.Window; replaced, never modified: autograd nodes keep theirs)
+
+    def set_encoding_window(self, alpha_xyz=None, alpha_dir=None):
+        """Coarse-to-fine window over the frequency bands of the two encodings (BARF, for training the nets together with the cameras
+        from poor poses): band k of an encoding is multiplied by w_k(alpha) = (1 - cos(pi clamp(alpha - k, 0, 1))) / 2 -- closed for
+        alpha <= k, open for alpha >= k + 1; the include_input columns always pass.  alpha_xyz / alpha_dir: the progress of the xyz /
+        direction encoding in bands (alpha >= num_encoding_fn: fully open); None for one of them leaves that encoding open; None for both
+        clears the window: exactly the code path of a model that never had one.
+        The windowed net is this net run on theta_eff = theta (.) m(alpha) (include/nerfhip.h): with a window set every weight image is
+        packed from theta_eff (training and inference passes, fused render and TrainEngine alike), the input / ray / pose gradient
+        multiplies by theta_eff, and every parameter gradient comes back multiplied by m -- the weights of a closed band get an exactly
+        zero gradient, so Adam leaves them at their initial values until the band opens.  Schedule state, not a parameter: state_dict
+        is unchanged.  May be changed between steps (TrainEngine(window=...) does, per step); a backward runs under the window of its
+        forward."""
+        if alpha_xyz is None and alpha_dir is None:
+            self.encoding_window, self._window_w = None, None
+            return self
+        w = L.Window()
+        for field, alpha, bands in ((w.xyz, alpha_xyz, self.cfg["num_encoding_fn_xyz"]),
+                                    (w.dir, alpha_dir, self.cfg["num_encoding_fn_dir"] if self.use_viewdirs else 0)):
+            for k in range(len(field)):
+                field[k] = 1.0
+            if alpha is not None:
+                for k, v in enumerate(encoding_window_weights(alpha, bands)):
+                    field[k] = v   # (ctypes rounds the fp64 value to fp32 once, to nearest)
+        self.encoding_window, self._window_w = (alpha_xyz, alpha_dir), w
+        return self
+
+    def _codes(self):
+        """nerfhip_plan_window_index on the parameters' device (uploaded once per device)."""
+        dev = self._flat.device
+        if self._window_codes is None or self._window_codes.device != dev:
+            host = torch.empty(self.num_flat_params, dtype=torch.uint8)
+            L.get_lib().plan_window_index(self._plan, host.data_ptr())
+            self._window_codes = host.to(dev)
+        return self._window_codes
+
+    def _theta_eff(self, refresh=True, copy=False):
+        """The flat vector the kernels' view of this net is built from: the parameters themselves without a window, else theta_eff in
+        the model's own buffer (refresh=False: as the last pack left it -- no launch) or in a fresh one (copy=True)."""
+        if self._window_w is None:
+            return self._flat.clone() if copy else self._flat
+        if copy or self._eff is None or self._eff.device != self._flat.device:
+            eff, refresh = torch.empty_like(self._flat), True
+            if not copy:
+                self._eff = eff
+        else:
+            eff = self._eff
+        if refresh:
+            codes = self._codes()
+            with L.launch_on(self._flat, codes, eff) as st:
+                L.get_lib().window_params(self._flat.data_ptr(), codes.data_ptr(), self.num_flat_params, C.byref(self._window_w),
+                                          eff.data_ptr(), st)
+        return eff
+
+    def _window_grads(self, gflat, window, stream=None):
+        """d(loss)/d(theta) = m (.) d(loss)/d(theta_eff), in place on a flat gradient of this net (`window`: the _lib.Window of the
+        forward it belongs to; None: nothing to do).  stream: a raw stream handle of the gradient's device, default its current one."""
+        if window is None:
+            return
+        codes = self._codes()
+        with L.launch_on(gflat, codes) as st:
+            L.get_lib().window_grads(gflat.data_ptr(), codes.data_ptr(), self.num_flat_params, C.byref(window),
+                                     st if stream is None else stream)
+
     def set_inference_precision(self, precision):
         """Arithmetic of this model's forward passes that no backward follows (torch.no_grad() / mode="validation"):
         "fp32" (default) or "f16x3" (NERFHIP_PRECISION_F16X3: fp16 pieces, fp32-grade products, > 2x the inference
@@ -303,21 +375,26 @@ class FlexibleNeRFModel(torch.nn.Module):
             self._inf_packed = torch.empty(n, dtype=torch.float32, device=dev)
         # (re-packed on every call, like _packed(): ~30 us against a render chunk's milliseconds.  The parameters are written
         # behind torch's back -- the fused Adam kernel, views re-homed with .data -- so no version counter can be trusted)
-        with L.launch_on(self._flat, self._inf_table, self._inf_packed) as st:
-            lib.pack_weights_plan(plan, self._flat.data_ptr(), self._inf_table.data_ptr(), self._inf_packed.data_ptr(), st)
+        src = self._theta_eff()
+        with L.launch_on(src, self._inf_table, self._inf_packed) as st:
+            lib.pack_weights_plan(plan, src.data_ptr(), self._inf_table.data_ptr(), self._inf_packed.data_ptr(), st)
         return self._inf_packed
 
     def __getstate__(self):
         # copy.deepcopy / pickle: the native handle and every cache derived from it stay behind; the parameters travel
         # as ordinary tensors and are re-homed into a fresh flat buffer by __setstate__
         state = self.__dict__.copy()
-        for k in ("_plan_owner", "_flat", "_flat_grad", "_pack_table", "_packed_buf", "_inf_owner", "_inf_table", "_inf_packed"):
+        for k in ("_plan_owner", "_flat", "_flat_grad", "_pack_table", "_packed_buf", "_inf_owner", "_inf_table", "_inf_packed",
+                  "_window_codes", "_eff"):
             state[k] = None
+        state["_window_w"] = None   # (rebuilt from encoding_window)
         return state   # (set_backward_compaction("auto"): _stats travels without its copy in flight, StatsReader.__getstate__)
 
     def __setstate__(self, state):
         super().__setstate__(state)
         self._native_init()
+        if self.encoding_window is not None:
+            self.set_encoding_window(*self.encoding_window)
 
     def _named(self):
         return dict(self.named_parameters())
@@ -339,6 +416,8 @@ class FlexibleNeRFModel(torch.nn.Module):
         self._packed_buf = None
         self._inf_table = None
         self._inf_packed = None
+        self._window_codes = None
+        self._eff = None
 
     def _apply(self, fn, *a, **k):
         r = super()._apply(fn, *a, **k)
@@ -376,11 +455,12 @@ class FlexibleNeRFModel(torch.nn.Module):
             self._packed_buf = torch.empty(n, dtype=torch.float32, device=dev)
             force = True
         if force:
-            with L.launch_on(self._flat, self._pack_table, self._packed_buf) as st:
+            src = self._theta_eff()   # (the parameters; under an encoding window theta_eff, written just ahead of the gather)
+            with L.launch_on(src, self._pack_table, self._packed_buf) as st:
                 if self._plan_owner.precision:
-                    lib.pack_weights_plan(self._plan, self._flat.data_ptr(), self._pack_table.data_ptr(), self._packed_buf.data_ptr(), st)
+                    lib.pack_weights_plan(self._plan, src.data_ptr(), self._pack_table.data_ptr(), self._packed_buf.data_ptr(), st)
                 else:
-                    lib.pack_weights(self._flat.data_ptr(), self._pack_table.data_ptr(), n, self._packed_buf.data_ptr(), st)
+                    lib.pack_weights(src.data_ptr(), self._pack_table.data_ptr(), n, self._packed_buf.data_ptr(), st)
         return self._packed_buf
 
     def _ordered_params(self):

@@ -42,6 +42,14 @@ def frequency_bands_cpu(num_encoding_functions, log_sampling=True):
     return torch.linspace(2.0 ** 0.0, 2.0 ** (num_encoding_functions - 1), num_encoding_functions, dtype=torch.float32)
 
 
+def encoding_window_weights(alpha, num_encoding_functions):
+    """BARF's coarse-to-fine window over the frequency bands of an encoding: w_k = (1 - cos(pi clamp(alpha - k, 0, 1))) / 2 for
+    k = 0 .. num_encoding_functions - 1, evaluated in fp64 (Python floats); the caller rounds once to fp32.  alpha >= the number of
+    bands: every band open (1.0); alpha <= 0: only the raw input passes (the include_input columns are never windowed)."""
+    import math
+    return [0.5 * (1.0 - math.cos(math.pi * min(max(float(alpha) - k, 0.0), 1.0))) for k in range(int(num_encoding_functions))]
+
+
 def _freqs(n, log_sampling, device):
     key = ("freq", n, bool(log_sampling), str(device))
     if key not in _CONST_CACHE:

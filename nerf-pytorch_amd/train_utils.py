@@ -116,7 +116,10 @@ class _FusedRender(torch.autograd.Function):
                            linspace01(nf, dev).data_ptr() if nf > 0 else None, C.byref(rr), 0, 0, C.byref(out),
                            ws.data_ptr(), wsb, 2 if training else 0, st)  # (2: this node's backward shares one set of backward buffers)
         # (the ray gradient multiplies by the weights of THIS forward: keep copies only if it will be asked for)
-        flats = (model_c._flat.clone(), model_f._flat.clone() if nf > 0 else None) if (training and rays_grad) else None
+        # (... of the nets as they ran: theta_eff under an encoding window)
+        flats = (model_c._theta_eff(copy=True), model_f._theta_eff(copy=True) if nf > 0 else None) if (training and rays_grad) else None
+        # (the window is schedule state of the model: the node's backward windows its gradients as its forward was windowed)
+        ctx.windows = (model_c._window_w, model_f._window_w if nf > 0 else None)
         ctx.keep = (rays, model_c, model_f, cfg, rand, ws, wsb, packed_c, packed_f, training, flats)
         # (the backward data flow is an option of the PLAN, and what this forward left in the workspace -- the general stash, nothing, the
         # register-image stash -- depends on it: the node's backward runs in the mode its forward ran in, whatever
@@ -183,6 +186,9 @@ class _FusedRender(torch.autograd.Function):
                 for plan, was, cur in pins:
                     if was != cur:
                         lib.plan_set_bwd_compaction(plan, cur)
+        model_c._window_grads(gpc, ctx.windows[0])
+        if nf > 0:
+            model_f._window_grads(gpf, ctx.windows[1])
         grads = model_c._split_flat(gpc) + (model_f._split_flat(gpf) if nf > 0 else ())
         return (g_rays,) + (None,) * 6 + grads
 
