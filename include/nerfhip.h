@@ -399,6 +399,22 @@ int nerfhip_render_bwd_rays(nerfhip_plan_t plan_coarse, nerfhip_plan_t plan_fine
                             float* g_params_coarse, float* g_params_fine, int parts, const float* params_coarse,
                             const float* params_fine, void* tmp, int64_t tmp_bytes, float* g_rays, nerfhip_stream_t stream);
 
+/* d(loss)/d(rays) ALONE, for frozen nets (camera localisation against a trained field): nerfhip_render_bwd_rays' contract -- parts,
+ * NERFHIP_PART_SHARED_BWD, the first pass that runs overwrites g_rays and the second accumulates, params_* = the flat vectors the
+ * packed images were made from (theta_eff under an encoding window) -- without g_params: no parameter gradient is computed or
+ * stored (no weight-gradient launch, no reduction).  Per pass: compositing backward, the plan's list / recomputation and its
+ * data-gradient chain (fused 64-wide modes run as mode 2), then the input-gradient GEMM and the positional encoding's backward in one
+ * MFMA kernel and a per-ray sum (nh_raygrad.h).  tmp: dev scratch of nerfhip_render_grad_rays_tmp_bytes (16-byte aligned).  A sample's
+ * contribution depends only on that sample, so plans in mode 0, 1 and 2 give the same bits.  n_rays == 0: nothing is launched. */
+int64_t nerfhip_render_grad_rays_tmp_bytes(nerfhip_plan_t plan_coarse, nerfhip_plan_t plan_fine, const nerfhip_render_cfg* cfg,
+                                           int64_t n_rays);
+int nerfhip_render_grad_rays(nerfhip_plan_t plan_coarse, nerfhip_plan_t plan_fine, const nerfhip_render_cfg* cfg,
+                             const float* rays, int64_t n_rays, const float* packed_coarse, const float* packed_fine,
+                             const nerfhip_render_rand* rnd, uint64_t seed, uint64_t ray_offset,
+                             const nerfhip_render_cotangents* g, void* workspace, int64_t workspace_bytes, int parts,
+                             const float* params_coarse, const float* params_fine, void* tmp, int64_t tmp_bytes, float* g_rays,
+                             nerfhip_stream_t stream);
+
 /* ---- loss + optimiser (train_nerf.py:244-270) ------------------------------------------------------------------ */
 /* mse_loss(rgb_coarse, target) + mse_loss(rgb_fine, target) and its cotangents; loss_out: dev float[3] =
  * {coarse_mse, fine_mse, sum}.  target rows have target_stride floats (RGB or RGBA; only [:3] is used). */

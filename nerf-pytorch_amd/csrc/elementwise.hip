@@ -19,13 +19,14 @@ void nh_set_error(const char* fmt, ...) {
 extern "C" const char* nerfhip_last_error(void) { return g_err; }
 extern "C" int nerfhip_version(void) {
 #ifdef NH_DIAG  // (make variant: an A/B or diagnostic build -- nh_diag.h; the Python package refuses it)
-    return 108 + NH_DIAG_VERSION_FLAG;
+    return 109 + NH_DIAG_VERSION_FLAG;
 #else
-    return 108;  // (102: round 6 -- the compacted backward's three entry points; 103: + the fused backward modes 3 / 4 of 64-wide nets; 104: + mode 5;
+    return 109;  // (102: round 6 -- the compacted backward's three entry points; 103: + the fused backward modes 3 / 4 of 64-wide nets; 104: + mode 5;
                  // 105: + the pose VJP, nerfhip_pose_grad_tmp_bytes / nerfhip_ray_bundle_bwd / nerfhip_select_rays_bwd;
                  // 106: + batches over a stack of views, nerfhip_select_rays_views / _views_bwd / nerfhip_pose_grad_views_tmp_bytes;
                  // 107: + the camera table, nerfhip_pose_table_fwd / nerfhip_pose_table_bwd;
-                 // 108: + the encoding window, nerfhip_plan_window_index / nerfhip_window_params / nerfhip_window_grads)
+                 // 108: + the encoding window, nerfhip_plan_window_index / nerfhip_window_params / nerfhip_window_grads;
+                 // 109: + the frozen ray gradient, nerfhip_render_grad_rays / nerfhip_render_grad_rays_tmp_bytes)
 #endif
 }
 extern "C" int nerfhip_is_emulated(void) {

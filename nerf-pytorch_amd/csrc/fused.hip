@@ -3,6 +3,7 @@
 //   compositing, and the matching backward.  Nothing of size (N*S, 90) or (N*S, 256) is materialised for inference;
 //   a training forward additionally writes the activation stash the weight-gradient GEMM consumes.
 #include "nh_mlp.h"
+#include "nh_raygrad.h"
 
 namespace {
 
@@ -152,6 +153,33 @@ int backward_pass(const Call& c, const Pass& q, void* tmp, int64_t tmp_bytes, fl
     return nh_ray_grad(c.rays, c.cfg->ray_stride, c.n, q.in.z, q.in.S, (const float*)tmp, p->Dx, p->Dd, p->cfg.include_input_xyz ? 1 : 0,
                        (p->view && p->cfg.include_input_dir) ? 1 : 0, p->cfg.num_encoding_fn_xyz, p->view ? p->cfg.num_encoding_fn_dir : 0,
                        p->freqs_xyz, p->freqs_dir, g_norm, g_rays, accumulate, c.stream);
+}
+
+// The frozen form of backward_pass (nerfhip_render_grad_rays): compositing backward -> list / recomputation / data gradient
+// (nh_mlp_backward_data: no weight gradient, no reduce, none of the weight gradient's bookkeeping) -> per-sample point and view
+// gradients on the MFMAs (nh_raygrad.h) -> their sum per ray, overwriting g_rays or accumulating into it
+int grad_rays_pass(const Call& c, const Pass& q, void* tmp, int64_t tmp_bytes, float* g_rays, int accumulate) {
+    nerfhip_plan* p = q.plan;
+    const int64_t M = c.n * q.in.S;
+    float* g_raw = (float*)(c.ws + q.w.g_raw);
+    float* scratch = (float*)(c.ws + q.w.scratch);
+    float* g_norm = (float*)(c.ws + q.w.gnorm);
+    const int64_t need = nh_point_grad_tmp_bytes(p, M);
+    NH_REQUIRE(q.params && tmp && tmp_bytes >= need, "render_grad_rays: the ray gradient needs the flat parameters and %lld bytes of tmp",
+               (long long)need);
+    int rc = nh_volume_render_bwd((const float*)(c.ws + q.w.raw), q.in.z, c.rays + 3, c.cfg->ray_stride, c.n, q.in.S, c.cfg->noise_std,
+                                  q.noise, c.seed, q.rng_stream, c.ray_offset, c.cfg->white_background, q.g_rgb, q.g_depth, q.g_acc, nullptr,
+                                  g_raw, g_norm, c.stream);
+    if (rc) return rc;
+    NhBwdData d;
+    rc = nh_mlp_backward_data(p, q.packed, &q.in, g_raw, M, (float*)(c.ws + q.w.stash), scratch, q.w.scratch_bytes, true, false, c.stream, &d);
+    if (rc) return rc;
+    // (need_images: nh_bwd_flow resolves no fused flow, so the data-gradient chain has just written the images read below)
+    NH_REQUIRE(!d.f.fused, "render_grad_rays: the fused backward leaves no d(pre-activation) images");
+    rc = nh_point_grad(p, q.params, M, scratch, d.cx, c.rays, c.cfg->ray_stride, q.in.z, q.in.S, (float*)tmp, c.stream);
+    if (rc) return rc;
+    return nh_ray_grad_sum(c.rays, c.cfg->ray_stride, c.n, q.in.z, q.in.S, (p->view && p->Dd > 0) ? 1 : 0, (const float*)tmp, g_norm, g_rays,
+                           accumulate, c.stream);
 }
 
 }  // namespace
@@ -310,4 +338,60 @@ extern "C" int nerfhip_render_bwd(nerfhip_plan_t pc, nerfhip_plan_t pf, const ne
     return nerfhip_render_bwd_parts(pc, pf, cfg, rays, n, packed_c, packed_f, rnd, seed, ray_offset, &g, workspace,
                                     workspace_bytes, g_params_c, g_params_f,
                                     NERFHIP_PART_COARSE | NERFHIP_PART_FINE | NERFHIP_PART_SHARED_BWD, stream);
+}
+
+extern "C" int64_t nerfhip_render_grad_rays_tmp_bytes(nerfhip_plan_t pc, nerfhip_plan_t pf, const nerfhip_render_cfg* cfg,
+                                                      int64_t n) {
+    if (check_cfg(pc, pf, cfg) != NERFHIP_OK || n < 0) return -1;
+    int64_t b = nh_point_grad_tmp_bytes(pc, n * cfg->num_coarse);
+    if (cfg->num_fine > 0) {
+        const int64_t f = nh_point_grad_tmp_bytes(pf, n * (cfg->num_coarse + cfg->num_fine));
+        if (f > b) b = f;
+    }
+    return b;
+}
+
+// nerfhip_render_bwd_rays for frozen nets: d(loss)/d(rays) alone -- no parameter gradient is computed, stored or applied
+extern "C" int nerfhip_render_grad_rays(nerfhip_plan_t pc, nerfhip_plan_t pf, const nerfhip_render_cfg* cfg, const float* rays,
+                                        int64_t n, const float* packed_c, const float* packed_f, const nerfhip_render_rand* rnd,
+                                        uint64_t seed, uint64_t ray_offset, const nerfhip_render_cotangents* g, void* workspace,
+                                        int64_t workspace_bytes, int parts, const float* params_c, const float* params_f, void* tmp,
+                                        int64_t tmp_bytes, float* g_rays, nerfhip_stream_t stream) {
+    int rc = check_cfg(pc, pf, cfg);
+    if (rc) return rc;
+    NH_REQUIRE(n >= 0, "render_grad_rays: bad arguments");
+    if (n == 0) return NERFHIP_OK;
+    NH_REQUIRE(rays && packed_c && g && workspace, "render_grad_rays: bad arguments");
+    NH_REQUIRE(g_rays, "render_grad_rays: g_rays is NULL");
+    NH_REQUIRE(tmp, "render_grad_rays: tmp is NULL");
+    const int shared = parts & NERFHIP_PART_SHARED_BWD;
+    parts &= ~NERFHIP_PART_SHARED_BWD;
+    NH_REQUIRE(parts >= 1 && parts <= 3, "render_grad_rays: parts must be a combination of NERFHIP_PART_COARSE | NERFHIP_PART_FINE");
+    const bool fine_runs = cfg->num_fine > 0 && (parts & NERFHIP_PART_FINE), coarse_runs = (parts & NERFHIP_PART_COARSE) != 0;
+    NH_REQUIRE((!coarse_runs || params_c) && (!fine_runs || params_f), "render_grad_rays: the flat parameters (params) are NULL");
+    NH_REQUIRE((!coarse_runs || nh_prec_level(pc->precision) != 1) && (!fine_runs || nh_prec_level(pf->precision) != 1),
+               "render_grad_rays: an f16x3 plan is inference-only");
+    const Workspace w = layout(pc, pf, cfg, n, shared ? 2 : 1);
+    NH_REQUIRE(workspace_bytes >= w.total, "render_grad_rays: workspace too small (%lld < %lld)", (long long)workspace_bytes,
+               (long long)w.total);
+    const Call c = {cfg, rays, n, seed, ray_offset, (char*)workspace, stream};
+    int wrote_rays = 0;  // the first pass that runs overwrites g_rays, the second accumulates
+    if (fine_runs) {
+        NH_REQUIRE(packed_f && (g->g_rgb_fine || g->g_acc_fine || g->g_depth_fine), "render_grad_rays: fine arguments missing");
+        Pass fine = net_pass(c, true, pf, packed_f, rnd, w);
+        fine.g_rgb = g->g_rgb_fine, fine.g_depth = g->g_depth_fine, fine.g_acc = g->g_acc_fine;
+        fine.params = params_f;
+        rc = grad_rays_pass(c, fine, tmp, tmp_bytes, g_rays, wrote_rays);
+        if (rc) return rc;
+        wrote_rays = 1;
+    }
+    if (coarse_runs) {
+        NH_REQUIRE(g->g_rgb_coarse || g->g_acc_coarse || g->g_depth_coarse, "render_grad_rays: coarse arguments missing");
+        Pass coarse = net_pass(c, false, pc, packed_c, rnd, w);
+        coarse.g_rgb = g->g_rgb_coarse, coarse.g_depth = g->g_depth_coarse, coarse.g_acc = g->g_acc_coarse;
+        coarse.params = params_c;
+        rc = grad_rays_pass(c, coarse, tmp, tmp_bytes, g_rays, wrote_rays);
+        if (rc) return rc;
+    }
+    return NERFHIP_OK;
 }

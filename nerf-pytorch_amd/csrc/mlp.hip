@@ -1,7 +1,8 @@
 // mlp.hip -- host side of the FlexibleNeRFModel kernels (nerf/models.py:185-256): argument checks and the launch
 // sequences  forward = k_mlp_fwd16 (mlp16.hip),  backward = k_mlp_dgrad16 (mlp16.hip) -> k_wgrad -> k_wgrad_reduce
 // (wgrad.hip), and the C-ABI entry points nerfhip_mlp_fwd / nerfhip_mlp_bwd; plus the gradient w.r.t. the encoded input
-// (nerfhip_mlp_bwd_input: off the hot path -- the render path never differentiates its encodings).
+// (nerfhip_mlp_bwd_input: the scalar form, one thread per sample and encoded column -- what the TRAINABLE ray gradient,
+// nerfhip_render_bwd_rays, still runs; the frozen one, nerfhip_render_grad_rays, takes the MFMA kernel of nh_raygrad.h instead).
 // Which of those sequences a plan's backward is (compacted, recomputing, the fused kernel of mlp64r.hip) and what its training forward
 // leaves in the stash for it: nh_bwd_flow, below -- the training forward, the backward and the input gradient all ask it.
 #include <stdlib.h>
@@ -153,9 +154,13 @@ int nh_mlp_forward_training(nerfhip_plan* p, const float* packed, const NhMlpInp
     return mlp_forward_any(p, packed, in, M, out, f.recompute ? nullptr : stash, stream, nullptr);
 }
 
-int nh_mlp_backward(nerfhip_plan* p, const float* packed, const NhMlpInput* in, const float* g_out, int64_t M, float* stash,
-                    float* scratch, int64_t scratch_bytes, float* g_params, bool need_images, nerfhip_stream_t stream) {
-    NH_REQUIRE(p && packed && g_out && stash && scratch && g_params && M > 0, "mlp_bwd: bad arguments");
+// What both backwards share -- the list, the optional recomputation, the data gradient: everything up to (not including) the weight
+// gradient.  Leaves in `d` the flow it resolved and the list its kernels walked (d->cx: NULL for a dense backward).  A fused flow
+// (mlp64r.hip) has no data-gradient launch of its own: it returns after the list, and the caller runs the one kernel.
+// want_amax: the region maxima only the fp16 weight gradient reads are recorded (d->amax / d->bmax), else not.
+int nh_mlp_backward_data(nerfhip_plan* p, const float* packed, const NhMlpInput* in, const float* g_out, int64_t M, float* stash,
+                         float* scratch, int64_t scratch_bytes, bool need_images, bool want_amax, nerfhip_stream_t stream, NhBwdData* d) {
+    NH_REQUIRE(p && packed && g_out && stash && scratch && d && M > 0, "mlp_bwd: bad arguments");
     NH_REQUIRE(nh_prec_level(p->precision) != 1, "mlp_bwd: an f16x3 plan is inference-only");
     NH_REQUIRE(scratch_bytes >= nh_mlp_bwd_scratch_bytes(p, M), "mlp_bwd: scratch too small (%lld < %lld)",
                (long long)scratch_bytes, (long long)nh_mlp_bwd_scratch_bytes(p, M));
@@ -163,49 +168,56 @@ int nh_mlp_backward(nerfhip_plan* p, const float* packed, const NhMlpInput* in, 
     const int64_t nt = nh_ceil_div(M, 128) * 4;
     const bool bdg = nh_prec_level(p->precision) >= 3;
     int rc = NERFHIP_OK;
+    d->f = f;
+    d->cx = nullptr;
+    d->amax = nullptr;
+    d->bmax = nullptr;
     // compacted backward: list the samples whose d(raw output) row is not all zero; every kernel below then walks that list
-    NhCompact cview;
-    const NhCompact* cx = nullptr;
     if (f.list) {
-        cview = nh_compact_view((int*)(scratch + compact_word_offset(p, nt)), nt * 32);
-        rc = nh_compact_build(g_out, M, cview, stream);
+        d->cview = nh_compact_view((int*)(scratch + compact_word_offset(p, nt)), nt * 32);
+        rc = nh_compact_build(g_out, M, d->cview, stream);
         if (rc) return rc;
-        cx = &cview;
+        d->cx = &d->cview;
     }
-    // the fused backward (mlp64r.hip): data gradient and weight gradient in one kernel, over the forward's register-image stash or
-    // recomputing the forward
-    if (f.fused)
-        return nh_mlp64r_backward(p, packed, *in, g_out, M, scratch + fused_partial_offset(p, nt), g_params, cx,
-                                  f.reg_image ? stash : nullptr, stream);
+    if (f.fused) return NERFHIP_OK;
     if (f.recompute) {
         // ... and the forward is run again for the listed samples only: their activation rows and ReLU masks, in list order (the
         // fp16-piece forward also records the stash's region maxima again, behind the stash as every training forward does)
-        NH_REQUIRE(cx, "mlp_bwd: a recomputing backward needs the compacted list");
-        rc = mlp_forward_any(p, packed, *in, M, nullptr, stash, stream, cx);
+        NH_REQUIRE(d->cx, "mlp_bwd: a recomputing backward needs the compacted list");
+        rc = mlp_forward_any(p, packed, *in, M, nullptr, stash, stream, d->cx);
         if (rc) return rc;
-        cview.stash_in_list_order = true;
+        d->cview.stash_in_list_order = true;
     }
     // fp16 plans whose large weight-gradient blocks run on the fp16 MFMAs: the producers record per-region maxima (behind the
     // stash: the forward's; behind this scratch: the data-gradient launch's), from which k_wgrad_f16x3 takes its scales
-    unsigned* amax = nullptr;
-    const unsigned* bmax = nullptr;
-    if (!p->bjobs.empty()) {
-        amax = (unsigned*)(scratch + gscale_word_offset(p, nt));
-        bmax = (const unsigned*)(stash + nh_stash_floats(p, nt));
-        rc = nh_zero_words(amax, NH_RMAX_WORDS, stream);
+    if (want_amax && !p->bjobs.empty()) {
+        d->amax = (unsigned*)(scratch + gscale_word_offset(p, nt));
+        d->bmax = (const unsigned*)(stash + nh_stash_floats(p, nt));
+        rc = nh_zero_words(d->amax, NH_RMAX_WORDS, stream);
         if (rc) return rc;
     }
-    if (bdg)
-        rc = nh_mlp_dgrad_f16w(p, packed, g_out, M, stash, scratch, amax, cx, stream);
-    else
-        rc = nh_mlp16_dgrad(p, packed, g_out, M, stash, scratch, cx, stream);
+    if (bdg) return nh_mlp_dgrad_f16w(p, packed, g_out, M, stash, scratch, d->amax, d->cx, stream);
+    return nh_mlp16_dgrad(p, packed, g_out, M, stash, scratch, d->cx, stream);
+}
+
+int nh_mlp_backward(nerfhip_plan* p, const float* packed, const NhMlpInput* in, const float* g_out, int64_t M, float* stash,
+                    float* scratch, int64_t scratch_bytes, float* g_params, bool need_images, nerfhip_stream_t stream) {
+    NH_REQUIRE(g_params, "mlp_bwd: bad arguments");
+    NhBwdData d;
+    int rc = nh_mlp_backward_data(p, packed, in, g_out, M, stash, scratch, scratch_bytes, need_images, true, stream, &d);
     if (rc) return rc;
+    const int64_t nt = nh_ceil_div(M, 128) * 4;
+    // the fused backward (mlp64r.hip): data gradient and weight gradient in one kernel, over the forward's register-image stash or
+    // recomputing the forward
+    if (d.f.fused)
+        return nh_mlp64r_backward(p, packed, *in, g_out, M, scratch + fused_partial_offset(p, nt), g_params, d.cx,
+                                  d.f.reg_image ? stash : nullptr, stream);
     float* const partial = scratch + (size_t)nt * (size_t)p->grad.total_rows * 32;
-    rc = nh_wgrad(p, nt, stash, scratch, partial, g_params, nullptr, cx, stream);
+    rc = nh_wgrad(p, nt, stash, scratch, partial, g_params, nullptr, d.cx, stream);
     if (rc) return rc;
     // (level 4: the large blocks, behind the fp32 kernel's partials)
     float* const partial_b = partial + nh_wgrad_partial_floats(p, nt);
-    return nh_wgrad_f16(p, nt, stash, scratch, partial_b, g_params, amax, bmax, cx, stream);
+    return nh_wgrad_f16(p, nt, stash, scratch, partial_b, g_params, d.amax, d.bmax, d.cx, stream);
 }
 
 extern "C" int nerfhip_plan_set_bwd_compaction(nerfhip_plan_t plan, int on) {

@@ -50,6 +50,18 @@ int nh_mlp_forward_training(nerfhip_plan* p, const float* packed, const NhMlpInp
 // render's own), or NULL: `stash` is the caller's general stash and is only read
 int nh_mlp_backward(nerfhip_plan* p, const float* packed, const NhMlpInput* in, const float* g_out, int64_t M, float* stash,
                     float* scratch, int64_t scratch_bytes, float* g_params, bool need_images, nerfhip_stream_t stream);
+// list + optional recomputation + data gradient: what nh_mlp_backward and the frozen ray-gradient pass (fused.hip) share.  d: the
+// flow it resolved, the list its kernels walked (cx == NULL: dense; the d(pre-activation) images are then in sample order), the region
+// maxima (want_amax: what only the fp16 weight gradient reads).  A fused flow returns after the list: the caller runs the one kernel.
+struct NhBwdData {
+    NhBwdFlow f;
+    NhCompact cview;
+    const NhCompact* cx;
+    unsigned* amax;
+    const unsigned* bmax;
+};
+int nh_mlp_backward_data(nerfhip_plan* p, const float* packed, const NhMlpInput* in, const float* g_out, int64_t M, float* stash,
+                         float* scratch, int64_t scratch_bytes, bool need_images, bool want_amax, nerfhip_stream_t stream, NhBwdData* d);
 int64_t nh_mlp_bwd_scratch_bytes(nerfhip_plan* p, int64_t M);
 
 // mlp16.hip: the forward / data-gradient chain on v_mfma_f32_16x16x4_f32, two waves per SIMD

@@ -44,6 +44,7 @@ class TrainEngine:
         self.lr, self.betas, self.eps = lr, betas, eps
         self.seed = seed
         self.step_count = 0
+        self.localize_count = 0   # localisation steps run (localize_on_image / localize_on_views): keys their selections and draws
         self.pg = process_group
         if world_size is None:
             world_size = torch.distributed.get_world_size(process_group) if torch.distributed.is_initialized() else 1
@@ -179,12 +180,14 @@ class TrainEngine:
         nets' backward chains may run at the same time on two streams)."""
         if getattr(self, "_rg_n", -1) != n:
             plan_f = self.mf._plan if self.mf is not None else None
-            tb = self.lib.render_bwd_rays_tmp_bytes(self.mc._plan, plan_f, C.byref(self.cfg), n)
+            # (one tmp serves both forms of the step: the trainable one's and the frozen one's, whichever is larger)
+            tb = max(self.lib.render_bwd_rays_tmp_bytes(self.mc._plan, plan_f, C.byref(self.cfg), n),
+                     self.lib.render_grad_rays_tmp_bytes(self.mc._plan, plan_f, C.byref(self.cfg), n))
             if tb < 0:
                 raise L.NerfHipError(self.lib.last_error().decode())
             mk = lambda *s: torch.empty(s, dtype=torch.float32, device=self.dev)  # noqa: E731
             self.ray_grad_coarse = mk(n, self.stride) if self.mf is not None else None
-            self._rg_tmp = (mk(tb // 4 + 1), mk(tb // 4 + 1) if self.mf is not None else None, tb)
+            self._rg_tmp = (mk(tb // 4 + 4), mk(tb // 4 + 4) if self.mf is not None else None, tb)
             self._rg_n = n
         return self.ray_grad_coarse, self._rg_tmp
 
@@ -193,7 +196,7 @@ class TrainEngine:
             raise NotImplementedError("TrainEngine: %s with world size %d is not implemented (the pose / ray gradient of a "
                                       "data-parallel step would need its own all-reduce); run it with one rank" % (what, self.world))
 
-    def forward_backward(self, rays, target, ray_offset=0, global_rays=None, draws=None, ray_grad=None):
+    def forward_backward(self, rays, target, ray_offset=0, global_rays=None, draws=None, ray_grad=None, frozen=False, step=None):
         """rays: (n, 8|11) packed rows on the device; target: (n, >=3), row stride free (an RGBA image's [..., :3] view
         works).  Leaves the summed-over-this-rank gradient in self.grad and {coarse_mse, fine_mse, sum} in self.loss
         (device); with world > 1 the gradient all-reduces are in flight when this returns (optimizer_step waits).
@@ -207,8 +210,15 @@ class TrainEngine:
         render backward with the ray gradient, nerfhip_render_bwd_rays; fused 64-wide backward modes run as mode 2 there).
         Its two parts land in two buffers: the fine net's in `ray_grad`, the coarse net's in the engine-owned
         `self.ray_grad_coarse` (a net with num_fine == 0: the whole of it in `ray_grad`); d(loss)/d(rays) is their sum, and
-        train_utils.select_training_rays_bwd / step_on_image(pose_grad=...) add them row by row.  One rank only."""
+        train_utils.select_training_rays_bwd / step_on_image(pose_grad=...) add them row by row.  One rank only.
+        frozen: True (needs ray_grad): the nets are left alone -- the backward is nerfhip_render_grad_rays, d(loss)/d(rays) without any
+        parameter gradient: self.grad is not touched, no gradient is windowed or all-reduced; same streams, same two buffers.
+        step: the counter the in-kernel draws are keyed by (default: step_count; the localisation steps pass localize_count).
+        TrainEngine(backward="auto") is a policy of the training backward (its thresholds weigh the weight gradient's cost): a frozen
+        step leaves each net in the mode its last training step chose and counts nothing in backward_modes_used."""
         self._check_inputs(rays, target)
+        if frozen and ray_grad is None:
+            raise RuntimeError("TrainEngine: forward_backward(frozen=True) computes the ray gradient alone: pass ray_grad=...")
         if ray_grad is not None:
             self._no_pose_grad_across_ranks("ray_grad")
             if (not isinstance(ray_grad, torch.Tensor) or ray_grad.device != self.dev or ray_grad.dtype != torch.float32
@@ -217,7 +227,7 @@ class TrainEngine:
                                    % (tuple(rays.shape), self.dev))
         lib, n = self.lib, rays.shape[0]
         gscale = 1.0 if global_rays is None else float(n) * self.world / float(global_rays)
-        if self.backward == "auto":
+        if self.backward == "auto" and not frozen:
             self._choose_backward_modes()
         if self._set_window():   # (optimizer_step packed for this step already; only a step_count or schedule changed by hand gets here)
             self.repack()
@@ -228,7 +238,7 @@ class TrainEngine:
         out = L.RenderOut(b["rgb_c"].data_ptr(), b["disp_c"].data_ptr(), b["acc_c"].data_ptr(), None,
                           b["rgb_f"].data_ptr() if nf > 0 else None, b["disp_f"].data_ptr() if nf > 0 else None,
                           b["acc_f"].data_ptr() if nf > 0 else None, None)
-        seed = self.seed + self.step_count * 0x9E3779B97F4A7C15 & 0xFFFFFFFFFFFFFFFF
+        seed = self.seed + (self.step_count if step is None else step) * 0x9E3779B97F4A7C15 & 0xFFFFFFFFFFFFFFFF
         pf = self.packed_f.data_ptr() if nf > 0 else None
         gc = self.grad[:self.nc_params]
         gf = self.grad[self.nc_params:] if nf > 0 else None
@@ -249,6 +259,7 @@ class TrainEngine:
         bwd_head = (self.mc._plan, plan_f, C.byref(self.cfg), rays.data_ptr(), n, self.packed_c.data_ptr(), pf, rr, seed,
                     ray_offset)
         bwd_tail = (self._ws.data_ptr(), self._wsb, gc.data_ptr(), gf.data_ptr() if gf is not None else None)
+        ws_tail = bwd_tail[:2]
         if ray_grad is not None:
             g_rays_c, (tmp_c, tmp_f, tmpb) = self._ray_grad_bufs(n)
             if g_rays_c is None:
@@ -266,6 +277,10 @@ class TrainEngine:
             def coarse_backward(stream_handle):
                 lib.mse_loss_fwd_bwd(b["rgb_c"].data_ptr(), None, target.data_ptr(), tstride, n, gscale, b["g_c"].data_ptr(),
                                      None, self._loss_c.data_ptr(), stream_handle)
+                if frozen:
+                    lib.render_grad_rays(*bwd_head, C.byref(cot_c), *ws_tail, L.PART_COARSE, pc_flat, pf_flat, tmp_c.data_ptr(), tmpb,
+                                         g_rays_c.data_ptr(), stream_handle)
+                    return
                 if ray_grad is None:
                     lib.render_bwd_parts(*bwd_head, C.byref(cot_c), *bwd_tail, L.PART_COARSE, stream_handle)
                 else:
@@ -283,25 +298,29 @@ class TrainEngine:
                 lib.render_fwd_parts(*fwd_args, L.PART_FINE, st)
                 lib.mse_loss_fwd_bwd(b["rgb_f"].data_ptr(), None, target.data_ptr(), tstride, n, gscale, b["g_f"].data_ptr(),
                                      None, self._loss_f.data_ptr(), st)
-                if ray_grad is None:
+                if frozen:
+                    lib.render_grad_rays(*bwd_head, C.byref(cot_f), *ws_tail, L.PART_FINE, pc_flat, pf_flat, tmp_f.data_ptr(), tmpb,
+                                         ray_grad.data_ptr(), st)
+                elif ray_grad is None:
                     lib.render_bwd_parts(*bwd_head, C.byref(cot_f), *bwd_tail, L.PART_FINE, st)
                 else:
                     lib.render_bwd_rays(*bwd_head, C.byref(cot_f), *bwd_tail, L.PART_FINE, pc_flat, pf_flat, tmp_f.data_ptr(), tmpb,
                                         ray_grad.data_ptr(), st)
-                self.mf._window_grads(gf, self.mf._window_w, st)
-                if self._reduce:  # in flight while the coarse backward computes
+                if not frozen:
+                    self.mf._window_grads(gf, self.mf._window_w, st)
+                if self._reduce and not frozen:  # in flight while the coarse backward computes
                     self._pending.append(allreduce_gradients(gf, self.pg, async_op=True, single_rank=True))
             if two:
                 main.wait_event(e2)
             else:
                 coarse_backward(st)
-            if self._reduce:
+            if self._reduce and not frozen:
                 self._pending.append(allreduce_gradients(gc, self.pg, async_op=True, single_rank=True))
             if nf > 0:
                 torch.stack((self._loss_c[0], self._loss_f[0], self._loss_c[0] + self._loss_f[0]), out=self.loss)
             else:
                 self.loss.copy_(self._loss_c)
-            if self.backward == "auto":   # ({kept, total} of every net that ran over a list in the step just issued)
+            if self.backward == "auto" and not frozen:   # ({kept, total} of every net that ran over a list in the step just issued)
                 self._stats.request(((name, self._stats_words(name)) for name, m in self._nets if m.backward_compaction in BM.BUILDS_LIST), main)
 
     # ---- backward="auto" (the policy and its thresholds: backward_mode.choose) ----------------------------------------------------
@@ -448,6 +467,46 @@ class TrainEngine:
         land in the table's own buffer and are pulled back to its twists, the nets take their Adam step and the twists theirs (the
         table's own lr).  All of it on the main stream after the two streams joined; no host synchronisation.  One rank only."""
         from .train_utils import select_training_rays_views, select_training_rays_views_bwd
+        # cameras.poses() -> selection -> forward_backward with the ray gradient -> the per-view pose VJP into cameras.g_poses ->
+        # cameras.backward() -> the nets' optimizer_step -> cameras.step()
+        poses, pose_grads = self._resolve_cameras(poses, pose_grads, cameras)
+        return self._step_on_selection(
+            lambda **kw: select_training_rays_views(height, width, focal_length, poses, images, options=options, **kw),
+            lambda used, g, g2: select_training_rays_views_bwd(height, width, focal_length, poses, used, g, options, g2, out=pose_grads),
+            pose_grads, num_random_rays, lr, global_rays, cameras)
+
+    def localize_on_image(self, image, pose, height, width, focal_length, options, num_random_rays, pose_grad):
+        """step_on_image(pose_grad=...) for FROZEN nets (camera localisation against a trained field): the same selection, forward and
+        pose VJP, with the render backward w.r.t. the rays alone (forward_backward(frozen=True)) and no optimizer step.  Nothing of
+        the nets or their optimiser moves -- flat_params, exp_avg, exp_avg_sq, grad, the packed images and step_count are what they
+        were, bit for bit --; the selection and the in-kernel draws are keyed by `localize_count`, which advances instead.
+        pose_grad: a contiguous float32 (3, 4) tensor on the engine's device, overwritten with d(loss)/d(pose[:3, :4]).  One rank only."""
+        from .train_utils import select_training_rays, select_training_rays_bwd
+        self._no_pose_grad_across_ranks("localize_on_image")
+        self._check_pose_grads("pose_grad", pose_grad, (3, 4))
+        return self._step_on_selection(
+            lambda **kw: select_training_rays(height, width, focal_length, pose, image, options=options, **kw),
+            lambda used, g, g2: select_training_rays_bwd(height, width, focal_length, pose, used, g, options, g2, out=pose_grad),
+            pose_grad, num_random_rays, None, None, frozen=True)
+
+    def localize_on_views(self, images, poses, height, width, focal_length, options, num_random_rays, pose_grads=None, cameras=None):
+        """step_on_views for FROZEN nets (see localize_on_image): with pose_grads (V, 3, 4) the step writes d(loss)/d(poses[v, :3, :4])
+        of every view; with cameras=T (then poses must be None and pose_grads must not be given) the table composes its poses, takes
+        the gradients in its own buffer, pulls them back to its twists (T.backward()) and steps them (T.step()) -- the nets stay put.
+        One rank only."""
+        from .train_utils import select_training_rays_views, select_training_rays_views_bwd
+        self._no_pose_grad_across_ranks("localize_on_views")
+        if cameras is None and pose_grads is None:
+            raise RuntimeError("TrainEngine: localize_on_views needs pose_grads=... or cameras=...")
+        poses, pose_grads = self._resolve_cameras(poses, pose_grads, cameras)
+        return self._step_on_selection(
+            lambda **kw: select_training_rays_views(height, width, focal_length, poses, images, options=options, **kw),
+            lambda used, g, g2: select_training_rays_views_bwd(height, width, focal_length, poses, used, g, options, g2, out=pose_grads),
+            pose_grads, num_random_rays, None, None, cameras, frozen=True)
+
+    def _resolve_cameras(self, poses, pose_grads, cameras):
+        """(poses, pose_grads) of a step over views: the caller's, checked; or, with cameras=T, the table's composed poses and its own
+        gradient buffer (then `poses` must be None and `pose_grads` must not be given).  One rank only where a pose gradient is asked."""
         if cameras is not None:
             if poses is not None:
                 raise RuntimeError("TrainEngine: with cameras=... the poses come from the table: pass poses=None")
@@ -456,16 +515,11 @@ class TrainEngine:
             self._no_pose_grad_across_ranks("cameras")
             if cameras.dev != self.dev:
                 raise RuntimeError("TrainEngine: the camera table lives on %s, the engine on %s" % (cameras.dev, self.dev))
-            # cameras.poses() -> selection -> forward_backward with the ray gradient -> the per-view pose VJP into cameras.g_poses ->
-            # cameras.backward() -> the nets' optimizer_step -> cameras.step()
-            poses, pose_grads = cameras.poses(), cameras.g_poses
-        elif pose_grads is not None:
+            return cameras.poses(), cameras.g_poses
+        if pose_grads is not None:
             self._no_pose_grad_across_ranks("pose_grads")
             self._check_pose_grads("pose_grads", pose_grads, (poses.shape[0], 3, 4))
-        return self._step_on_selection(
-            lambda **kw: select_training_rays_views(height, width, focal_length, poses, images, options=options, **kw),
-            lambda used, g, g2: select_training_rays_views_bwd(height, width, focal_length, poses, used, g, options, g2, out=pose_grads),
-            pose_grads, num_random_rays, lr, global_rays, cameras)
+        return poses, pose_grads
 
     def _check_pose_grads(self, name, g, shape):
         if (not isinstance(g, torch.Tensor) or g.device != self.dev or g.dtype != torch.float32 or tuple(g.shape) != shape
@@ -473,12 +527,13 @@ class TrainEngine:
             raise RuntimeError("TrainEngine: %s must be a contiguous float32 (%s) tensor on %s"
                                % (name, ", ".join(str(d) for d in shape), self.dev))
 
-    def _step_on_selection(self, select, vjp, pose_grads, num_random_rays, lr, global_rays, cameras=None):
+    def _step_on_selection(self, select, vjp, pose_grads, num_random_rays, lr, global_rays, cameras=None, frozen=False):
         """What step_on_image and step_on_views share: this rank's slice of the step's permutation, `select(num_random_rays=, seed=,
         step=, first=)` -> (rays, target, select indices), then `step`; or, with `pose_grads` (the buffer `vjp` fills),
         forward_backward with the ray gradient, `vjp(select indices, ray gradient, coarse ray gradient)` on the main stream after
         the two streams joined, optimizer_step.  `cameras` (the table whose poses and gradient buffer the callables use): its
-        backward() follows the VJP, its step() the nets' Adam."""
+        backward() follows the VJP, its step() the nets' Adam.  frozen (localize_on_*): the ray gradient alone, no optimizer_step;
+        keyed by localize_count, which advances."""
         from .parallel import shard_bounds
         if global_rays is None:
             n = int(num_random_rays)
@@ -489,17 +544,21 @@ class TrainEngine:
         if pose_grads is None:
             rays, target, _ = select(num_random_rays=n, seed=self.seed, step=self.step_count, first=first)
             return self.step(rays, target, ray_offset=first, lr=lr, global_rays=global_rays)
+        count = self.localize_count if frozen else self.step_count
         with torch.no_grad():
-            rays, target, used = select(num_random_rays=n, seed=self.seed, step=self.step_count, first=first)
+            rays, target, used = select(num_random_rays=n, seed=self.seed, step=count, first=first)
         if getattr(self, "_ray_grad_n", -1) != n:
             self._ray_grad = torch.empty((n, self.stride), dtype=torch.float32, device=self.dev)
             self._ray_grad_n = n
-        self.forward_backward(rays, target, first, global_rays, None, self._ray_grad)
+        self.forward_backward(rays, target, first, global_rays, None, self._ray_grad, frozen, count)
         with torch.cuda.device(self.dev):
             vjp(used, self._ray_grad, self.ray_grad_coarse)
         if cameras is not None:
             cameras.backward()
-        self.optimizer_step(lr)
+        if frozen:
+            self.localize_count += 1
+        else:
+            self.optimizer_step(lr)
         if cameras is not None:
             cameras.step()
         return self.loss

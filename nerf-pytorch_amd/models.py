@@ -232,6 +232,21 @@ class FlexibleNeRFModel(torch.nn.Module):
         self._stats, self._auto_calls = (BM.StatsReader(("net",)) if choice == "auto" else None), 0
         return self
 
+    frozen = False   # set_frozen: a render backward w.r.t. the ray batch alone (not part of state_dict)
+
+    def set_frozen(self, on=True):
+        """Frozen model (off by default; a switch of the object like set_backward_compaction, not saved in state_dict): when BOTH nets
+        of a fused render are frozen and the ray batch requires grad -- camera localisation against a trained field, BARF's test-pose
+        optimisation --, the render's backward computes d(loss)/d(rays) alone (nerfhip_render_grad_rays: no weight gradient is
+        computed or stored, the ray gradient runs on the MFMA kernel of csrc/nh_raygrad.h) and every parameter's gradient is None.
+        A frozen model must not have a parameter that requires grad (`for p in model.parameters(): p.requires_grad_(False)` first):
+        the render raises RuntimeError otherwise.  An autograd node keeps the flag of its forward.  The plan's backward mode holds as
+        for every render backward that must leave the d(pre-activation) images (fused 64-wide modes run as "recompute");
+        set_backward_compaction("auto") is a policy of the TRAINING backward: a frozen backward requests no statistics, so an "auto"
+        model keeps the mode its last training backward chose until it trains again."""
+        self.frozen = bool(on)
+        return self
+
     def _apply_backward(self, choice):
         """Puts the CURRENT plan into the mode `choice` stands for, whatever set_backward_compaction was asked (TrainEngine(backward=
         "auto") sets its steps' modes here).  None (never asked) and "auto" start from the fused one-kernel backward where the plan has

@@ -125,6 +125,10 @@ class _FusedRender(torch.autograd.Function):
         # register-image stash -- depends on it: the node's backward runs in the mode its forward ran in, whatever
         # set_backward_compaction was called with in between)
         ctx.bwd_modes = (lib.plan_bwd_compaction(plan_c), lib.plan_bwd_compaction(plan_f) if plan_f is not None else 0) if training else None
+        # (... and with the frozen flag of its forward: set_frozen on both nets and a ray batch that wants a gradient -> the backward is
+        # the ray gradient alone, nerfhip_render_grad_rays)
+        ctx.frozen = bool(training and rays_grad and model_c.frozen and (nf == 0 or model_f.frozen))
+        ctx.n_params = len(params)
         ctx.mark_non_differentiable(bufs["disp_coarse"], bufs["disp_fine"])
         return tuple(bufs[k] for k in names)
 
@@ -144,6 +148,8 @@ class _FusedRender(torch.autograd.Function):
             parts |= L.PART_COARSE
         if nf > 0 and any(k is not None for k in keep[3:]):
             parts |= L.PART_FINE
+        if ctx.frozen:
+            return (_FusedRender._frozen_backward(ctx, keep, parts),) + (None,) * (6 + ctx.n_params)
         gpc = torch.zeros(model_c.num_flat_params, dtype=torch.float32, device=dev)
         gpf = torch.zeros(model_f.num_flat_params, dtype=torch.float32, device=dev) if nf > 0 else None
         g_rays = torch.zeros_like(rays) if flats is not None else None
@@ -192,6 +198,38 @@ class _FusedRender(torch.autograd.Function):
         grads = model_c._split_flat(gpc) + (model_f._split_flat(gpf) if nf > 0 else ())
         return (g_rays,) + (None,) * 6 + grads
 
+    @staticmethod
+    def _frozen_backward(ctx, keep, parts):
+        """d(loss)/d(rays) of a node whose nets were frozen at its forward: no parameter gradient exists anywhere."""
+        lib = L.get_lib()
+        rays, model_c, model_f, cfg, rand, ws, wsb, packed_c, packed_f, training, flats = ctx.keep
+        n, nf = rays.shape[0], cfg.num_fine
+        g_rays = torch.zeros_like(rays)
+        if not parts:
+            return g_rays
+        cot = L.RenderCotangents(*[None if k is None else k.data_ptr() for k in keep])
+        rr = L.RenderRand(*[None if r is None else r.data_ptr() for r in rand])
+        plan_f = model_f._plan if nf > 0 else None
+        tmpb = lib.render_grad_rays_tmp_bytes(model_c._plan, plan_f, C.byref(cfg), n)
+        if tmpb < 0:
+            raise L.NerfHipError(lib.last_error().decode())
+        tmp = torch.empty(tmpb // 4 + 4, dtype=torch.float32, device=rays.device)
+        pins = [(p, was, lib.plan_bwd_compaction(p)) for p, was in zip((model_c._plan, plan_f), ctx.bwd_modes) if p is not None]
+        for plan, was, cur in pins:
+            if was != cur:
+                lib.plan_set_bwd_compaction(plan, was)
+        try:
+            with L.launch_on(rays, ws, tmp, *[k for k in keep if k is not None]) as st:
+                lib.render_grad_rays(model_c._plan, plan_f, C.byref(cfg), rays.data_ptr(), n, packed_c.data_ptr(),
+                                     packed_f.data_ptr() if nf > 0 else None, C.byref(rr), 0, 0, C.byref(cot), ws.data_ptr(), wsb,
+                                     parts | L.PART_SHARED_BWD, flats[0].data_ptr(), flats[1].data_ptr() if flats[1] is not None else None,
+                                     tmp.data_ptr(), tmpb, g_rays.data_ptr(), st)
+        finally:
+            for plan, was, cur in pins:
+                if was != cur:
+                    lib.plan_set_bwd_compaction(plan, cur)
+        return g_rays
+
 
 def _predict_fused(ray_batch, model_coarse, model_fine, opts):
     rays_grad = bool(ray_batch.requires_grad and torch.is_grad_enabled())
@@ -209,6 +247,10 @@ def _predict_fused(ray_batch, model_coarse, model_fine, opts):
     cfg_tuple = (nc, nf, bool(perturb), bool(opts.lindisp), bool(opts.white_background), float(noise_std))
     pc = model_coarse._ordered_params()
     pf = model_fine._ordered_params() if nf > 0 else []
+    for m, ps in ((model_coarse, pc), (model_fine, pf)):
+        if ps and m.frozen and any(p.requires_grad for p in ps):
+            raise RuntimeError("a frozen model (set_frozen) has a parameter that requires grad: freeze the parameters "
+                               "(p.requires_grad_(False)) or call set_frozen(False)")
     training = torch.is_grad_enabled() and (rays_grad or any(p.requires_grad for p in pc + pf))
     outs = _FusedRender.apply(rays, model_coarse, model_fine if nf > 0 else None, cfg_tuple,
                               (t_rand, noise_c, u, noise_f), training, rays_grad, *pc, *pf)
