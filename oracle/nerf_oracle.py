@@ -273,8 +273,8 @@ def mlp_relu_margin(params, x, cfg, per_layer=False):
     return allp.abs().min(dim=-1).values / (allp.abs().max(dim=-1).values + 1e-30)
 
 
-def run_network(params, pts, rays, cfg, chunksize=None):
-    """nerf/train_utils.py:8-25: encode points (+ per-ray view directions broadcast over samples), run the MLP."""
+def encode_points(pts, rays, cfg):
+    """nerf/train_utils.py:10-17: the MLP's input rows -- encoded points (+ per-ray view directions broadcast over samples)."""
     flat = pts.reshape(-1, 3)
     emb = positional_encoding(flat, cfg["num_encoding_fn_xyz"], cfg.get("include_input_xyz", True),
                               cfg.get("log_sampling_xyz", True))
@@ -283,6 +283,12 @@ def run_network(params, pts, rays, cfg, chunksize=None):
         emb_d = positional_encoding(dirs, cfg["num_encoding_fn_dir"], cfg.get("include_input_dir", True),
                                     cfg.get("log_sampling_dir", True))
         emb = torch.cat((emb, emb_d), dim=-1)
+    return emb
+
+
+def run_network(params, pts, rays, cfg, chunksize=None):
+    """nerf/train_utils.py:8-25: encode points (+ per-ray view directions broadcast over samples), run the MLP."""
+    emb = encode_points(pts, rays, cfg)
     if chunksize is None:
         out = mlp_forward(params, emb, cfg)
     else:
@@ -317,6 +323,30 @@ def render_rays(rays, params_c, params_f, cfg_c, cfg_f, opt, rand=None, chunksiz
                                                          rand.get("noise_fine"), opt.get("white_background", False))
         out.update(rgb_fine=rgb_f, disp_fine=disp_f, acc_fine=acc_f, depth_fine=depth_f, z_samples=z_samples, z_fine=z_f,
                    raw_fine=raw_f)
+    return out
+
+
+def render_at_depths(rays, z_coarse, z_fine, params_c, params_f, cfg_c, cfg_f, opt, rand=None, want_margin=False):
+    """render_rays with both passes' depths GIVEN (constants of the rays: no stratified draw, no sampler in the graph) -- the teacher-forced
+    twin of the two passes above: pts = ro + rd * z (nerf/train_utils.py:67,107), run_network, volume_render.  z_coarse: (N, num_coarse),
+    z_fine: (N, num_coarse + num_fine).  want_margin: + 'relu_margin', per ray the smallest mlp_relu_margin over all its samples of both
+    passes."""
+    rand = rand or {}
+    ro, rd = rays[..., :3], rays[..., 3:6]
+    out, margin = {}, None
+    for tag, z, par, cfg in (("coarse", z_coarse, params_c, cfg_c), ("fine", z_fine, params_f, cfg_f)):
+        pts = ro[..., None, :] + rd[..., None, :] * z[..., :, None]
+        raw = run_network(par, pts, rays, cfg)
+        rgb, disp, acc, w, depth = volume_render(raw, z, rd, opt.get("noise_std", 0.0), rand.get("noise_" + tag),
+                                                 opt.get("white_background", False))
+        out.update({"rgb_" + tag: rgb, "disp_" + tag: disp, "acc_" + tag: acc, "depth_" + tag: depth, "weights_" + tag: w,
+                    "raw_" + tag: raw})
+        if want_margin:
+            with torch.no_grad():
+                m = mlp_relu_margin(par, encode_points(pts, rays, cfg), cfg).reshape(z.shape).min(dim=-1).values
+            margin = m if margin is None else torch.minimum(margin, m)
+    if want_margin:
+        out["relu_margin"] = margin
     return out
 
 

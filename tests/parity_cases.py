@@ -985,8 +985,12 @@ def case_ray_grad(b, cfg, n=24, nc=16, nf=16, seed=61, white=False, noise=0.0, c
     got = out["g_rays"]
     # (near / far, columns 6 and 7, are constants of the ray here; the oracle's autograd also differentiates the depths)
     rec = {}
+    # (not vacuous, from the reference alone: most rays have a gradient -- with none the medians below are 0 <= 2e-6 whatever the kernel gives)
+    live = float(np.any(ref64[:, 0:3] != 0.0, axis=1).mean())
+    assert np.isfinite(ref64).all() and live >= 0.9, "%.2f of the rays have a gradient in the fp64 reference" % live
     for lo, hi, what in ((0, 3, "origin"), (3, 6, "direction")) + (((8, 11, "viewdirs"),) if view else ()):
-        scale = float(np.abs(ref64[:, lo:hi]).max()) + 1e-30
+        scale = float(np.abs(ref64[:, lo:hi]).max())
+        assert scale > 0.0, "the fp64 reference has no %s gradient" % what
         e_hip = np.abs(got[:, lo:hi] - ref[:, lo:hi]).max(axis=1) / scale            # kernel vs the oracle's fp32 autograd
         e_yard = np.abs(ref[:, lo:hi] - ref64[:, lo:hi]).max(axis=1) / scale         # the oracle's fp32 vs its fp64 autograd
         rec[what] = dict(hip_median=float(np.median(e_hip)), yard_median=float(np.median(e_yard)), hip_over=int((e_hip > 2e-3).sum()),

@@ -22,7 +22,7 @@ CASES = [
     ("wide2x320", 40, 16, 16, False, 0, {}),                                     # two 256-row regions, the second one padded
     ("odd5x99_skip2", 40, 16, 16, False, 0, {}),                                 # 99 of 128 units: a masked last chunk
     ("L12_4x128", 100, 32, 32, False, 0, {}),                                    # extended encoding registers (112 / 64 slots), resident
-    ("L16_Ld6_8x256", 64, 32, 32, False, 0, {}),                                 # 261 KB of weight slices: streamed term by term, dense
+    ("L16_Ld6_8x256", 64, 32, 32, False, 0, dict(noise=0.2)),                    # 261 KB of weight slices: streamed term by term, dense
     ("L16_Ld6_8x256", 50, 24, 16, True, 0, dict(noise=0.2)),                     # ... and over a list; ragged last tile
     ("llff4x64_skip3_L6", 12, 8, 8, "fused_stash", 0, {}),                       # runs as mode 2; S = 8 and 16: several rays per wave tile
     ("llff4x64_skip3_L6", 333, 24, 16, "fused_stash", 0, {}),                    # S = 24 and 40: no multiples of 16, a ragged last tile
@@ -30,6 +30,34 @@ CASES = [
     ("default4x128", 1, 16, 16, True, 0, {}),
 ]
 IDS = ["%s-n%d-%d+%d-%s-p%d" % c[:6] for c in CASES]
+# teacher-forced on the kernels' own depths: (..., all six cotangents?).  The smallest shapes that still cross every tile edge; the sigma
+# noise is what gives the nets whose initial densities are not positive something to render (every ray a gradient); the 256- and 512-wide
+# nets at 8 + 8 samples so that the ReLU filter (every sample of a ray decided) leaves more than half of the rays
+TF_CASES = [
+    ("default4x128", 200, 16, 16, False, 0, {}, True),                           # 3200 / 6400 rows: 25 / 50 tiles; g_acc_*, g_depth_* drive g_norm
+    ("default4x128", 200, 16, 16, False, PC.F16X3_TRAIN, {}, False),
+    ("northstar8x256", 96, 8, 8, False, 0, dict(noise=0.2), True),               # two xyz terms, resident
+    ("novw3x64_skip1", 100, 16, 16, False, 0, dict(white=True, noise=0.5), False),   # 8-column rays, every layer a skip layer
+    ("noinput_linear", 100, 16, 16, False, 0, dict(noise=1.0), False),           # qin = -1 twice; 3 L = 15 / 9: half-filled last quads; linear bands
+    ("narrow3x40", 100, 24, 16, True, 0, {}, False),                             # nu = 40 / 20: masked chunks in both kinds of term; S = 24 / 40 over a list
+    ("Ld5_4x128_skip2", 100, 16, 16, False, 0, {}, False),                       # 3 Ld = 15 alone asks for the extended registers
+    ("L11_novw3x64_skip1", 100, 16, 16, False, 0, dict(noise=0.5), False),       # 3 L = 33: odd, extended, no direction term
+    ("L12_Ld10_2x512", 48, 8, 8, False, 0, dict(noise=0.5), False),              # two 256-unit terms per tensor, Ld at its limit
+    ("wide3x512_skip2", 48, 8, 8, True, 0, dict(noise=0.5), False),              # ... with a skip layer, over a list
+    ("L16_Ld6_8x256", 96, 8, 8, False, 0, dict(noise=0.2), False),               # streamed weight slices, dense
+    ("L16_Ld6_8x256", 96, 8, 8, "recompute", 0, dict(noise=0.2), False),         # ... and over a list
+    ("odd5x99_skip2", 64, 16, 16, False, 0, {}, False),                          # 99 of 128 units
+    ("wide2x320", 64, 8, 8, False, 0, {}, False),                                # two regions, the second one padded
+    ("one_layer", 64, 16, 16, False, 0, dict(noise=0.5), False),                 # layer1 and the direction layer alone
+    ("llff4x64_skip3_L6", 333, 24, 16, "fused_stash", 0, {}, False),             # runs as mode 2; ragged last tile
+    ("default4x128", 1, 16, 16, True, 0, {}, False),
+]
+TF_IDS = ["%s-n%d-%d+%d-%s-p%d" % c[:6] + ("-allcot" if c[7] else "") for c in TF_CASES]
+
+
+@pytest.mark.parametrize("name,n,nc,nf,mode,precision,kw,allcot", TF_CASES, ids=TF_IDS)
+def test_both_ray_gradient_chains_match_fp64_on_their_own_depths_ray_for_ray(gpu, name, n, nc, nf, mode, precision, kw, allcot):
+    LC.case_teacher_forced(gpu, name, n, nc, nf, mode, precision, allcot, floor=LC.DECIDED_GPU, **kw)
 
 
 @pytest.mark.parametrize("name,n,nc,nf,mode,precision,kw", CASES, ids=IDS)

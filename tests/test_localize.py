@@ -14,7 +14,7 @@ CASES = [
     ("wide2x320", 6, 8, 8, False, 0, {}),
     ("odd5x99_skip2", 6, 8, 8, False, 0, {}),
     ("L12_4x128", 8, 8, 8, False, 0, {}),
-    ("L16_Ld6_8x256", 5, 8, 8, False, 0, {}),
+    ("L16_Ld6_8x256", 5, 8, 8, False, 0, dict(noise=0.2)),
     ("L16_Ld6_8x256", 11, 8, 16, True, 0, dict(noise=0.2)),
     ("llff4x64_skip3_L6", 12, 8, 8, "fused_stash", 0, {}),
     ("llff4x64_skip3_L6", 7, 24, 16, "fused_stash", 0, {}),
@@ -22,6 +22,33 @@ CASES = [
     ("default4x128", 1, 8, 8, True, 0, {}),
 ]
 IDS = ["%s-n%d-%d+%d-%s-p%d" % c[:6] for c in CASES]
+# teacher-forced on the kernels' own depths: (..., all six cotangents?) -- tests/test_gpu_localize.py's table at ray counts the emulator
+# walks in seconds (what each row exercises is written there)
+TF_CASES = [
+    ("default4x128", 12, 8, 8, False, 0, {}, True),
+    ("default4x128", 12, 8, 8, False, PC.F16X3_TRAIN, {}, False),
+    ("northstar8x256", 8, 8, 8, False, 0, dict(noise=0.2), True),
+    ("novw3x64_skip1", 10, 16, 16, False, 0, dict(white=True, noise=0.5), False),
+    ("noinput_linear", 10, 8, 8, False, 0, dict(noise=1.0), False),
+    ("narrow3x40", 9, 24, 16, True, 0, {}, False),
+    ("Ld5_4x128_skip2", 10, 8, 8, False, 0, {}, False),
+    ("L11_novw3x64_skip1", 10, 8, 8, False, 0, dict(noise=0.5), False),
+    ("L12_Ld10_2x512", 6, 8, 8, False, 0, dict(noise=0.5), False),
+    ("wide3x512_skip2", 6, 8, 8, True, 0, dict(noise=0.5), False),
+    ("L16_Ld6_8x256", 8, 8, 8, False, 0, dict(noise=0.2), False),
+    ("L16_Ld6_8x256", 8, 8, 8, "recompute", 0, dict(noise=0.2), False),
+    ("odd5x99_skip2", 8, 8, 8, False, 0, {}, False),
+    ("wide2x320", 6, 8, 8, False, 0, {}, False),
+    ("one_layer", 8, 8, 8, False, 0, dict(noise=0.5), False),
+    ("llff4x64_skip3_L6", 7, 24, 16, "fused_stash", 0, {}, False),
+    ("default4x128", 1, 8, 8, True, 0, {}, False),
+]
+TF_IDS = ["%s-n%d-%d+%d-%s-p%d" % c[:6] + ("-allcot" if c[7] else "") for c in TF_CASES]
+
+
+@pytest.mark.parametrize("name,n,nc,nf,mode,precision,kw,allcot", TF_CASES, ids=TF_IDS)
+def test_both_ray_gradient_chains_match_fp64_on_their_own_depths_ray_for_ray(emu, name, n, nc, nf, mode, precision, kw, allcot):
+    LC.case_teacher_forced(emu, name, n, nc, nf, mode, precision, allcot, floor=LC.DECIDED_EMU, **kw)
 
 
 @pytest.mark.parametrize("name,n,nc,nf,mode,precision,kw", CASES, ids=IDS)

@@ -109,6 +109,21 @@ TOL = {
                                            "maximum (one moved fine sample flips ReLU branches: any two fp32 evaluations are ~1e-3 apart on 48-200 rays) -- "
                                            "a sanity cap, NOT the parity claim: that is the teacher-forced `tf.grad.filtered` (1e-4) at full size and "
                                            "`unit.mlp_bwd` (2e-5) on the kernels, and `e2e.grad_fine.yardstick` where the batch is large enough for statistics"),
+    # ---- d(loss)/d(rays), teacher-forced on the kernels' own depths (tests/localize_cases.py::case_teacher_forced) ----------------------
+    "unit.ray_grad.tf_fp64_yardstick": (dict(mul=2.0, add=2e-6),
+                                        "both ray-gradient chains (nerfhip_render_grad_rays, nerfhip_render_bwd_rays) against the oracle's fp64 autograd "
+                                        "on the depths the kernels' own forward produced (constants: no sampler between the two), per column block of "
+                                        "max|g|: the LARGEST error over the rays whose ReLU branches round-off cannot decide (`unit.mlp_bwd`'s margin, in "
+                                        "fp64, at every sample of the ray) is no more than the oracle's own fp32 run's largest over the same rays, x 2 -- "
+                                        "what `e2e.yardstick.*` and `e2e.grad_fine.yardstick` allow two fp32 evaluations that do not share their rounding -- "
+                                        "+ 2e-6, the floor of the end-to-end ray-gradient cases.  The yardstick is the reference's error on identical "
+                                        "inputs, never a measurement of the kernels (on the wave emulator their ratio to it came out at 0.97-1.10 over "
+                                        "twelve geometries)"),
+    "unit.ray_grad.new_vs_old": (dict(mul=1.0, add=2e-6),
+                                 "nerfhip_render_grad_rays against nerfhip_render_bwd_rays over one forward, the largest difference over ALL rays "
+                                 "(no filter: the two read the same d(pre-activation) images and so share every ReLU branch; they differ in summation "
+                                 "order and in the grouping of the encoding's VJP), of the same max|g|: within the oracle's own fp32 error on the "
+                                 "decided rays + the same floor (measured on the emulator: 5e-8 - 4.4e-7)"),
 }
 
 # arithmetic -> {name: value}.  MUST hold no entry for the fp32-grade arithmetics (asserted on the CPU).
