@@ -490,7 +490,8 @@ int nerfhip_select_rays_bwd(const nerfhip_select_cfg* cfg, const float* c2w, int
  * above).  poses: dev, the pose of view v starts at poses + v * pose_view_stride floats, row-major with row stride
  * pose_ld >= 4 (a contiguous [V, 4, 4] or [V, 3, 4] table, or a strided slice of a larger one; pose_view_stride >=
  * 2 * pose_ld + 4 when num_views > 1); images: dev [V, H, W, channels] or NULL.  Height, width, focal, near / far, NDC and
- * viewdirs come from cfg and are shared by all views.  select_inds: dev int64 [n] global indices in [0, V * H * W), or NULL:
+ * viewdirs come from cfg and are shared by all views (intrinsics that live on the device, fx != fy or an off-centre principal
+ * point: the `intr` forms below).  select_inds: dev int64 [n] global indices in [0, V * H * W), or NULL:
  * positions cfg->first .. + n - 1 of the keyed permutation of [0, V * H * W) (ranks take disjoint slices, as above).
  * Row i equals, bit for bit, the row nerfhip_select_rays writes for (poses[v], images[v], select_inds = {k}); with
  * num_views == 1 the whole call equals nerfhip_select_rays.  Limits: 1 <= num_views <= NERFHIP_MAX_VIEWS,
@@ -511,6 +512,48 @@ int64_t nerfhip_pose_grad_views_tmp_bytes(int64_t n, int num_views);
 int nerfhip_select_rays_views_bwd(const nerfhip_select_cfg* cfg, int num_views, const float* poses, int64_t pose_view_stride,
                                   int pose_ld, const int64_t* inds, int64_t n, const float* g_rays, const float* g_rays_2,
                                   int g_rays_stride, void* tmp, int64_t tmp_bytes, float* g_poses, nerfhip_stream_t stream);
+
+/* ---- learned intrinsics: fx, fy, cx, cy on the device, with their gradient (NeRF--, a COLMAP focal that is a few per cent off) -----
+ * intr: dev float[4] = (fx, fy, cx, cy) in pixels, shared by all views of a call.  Pixel (row, col) has the camera direction
+ *     dc = ((col - cx) / fx, -(row - cy) / fy, -1),
+ * the arithmetic of the scalar forms operation for operation: intr = (focal, focal, (float)(W * 0.5), (float)(H * 0.5)) gives their
+ * bits.  NDC: the five constants stay those of cfg, fixed on the host, and do NOT follow intr -- ndc_rays is a fixed projective change
+ * of coordinates of the space the nets live in, any (cw, ch) is a valid one, and moving it during training would move the scene
+ * under the nets.  So intr enters through the pin-hole direction only and d(loss)/d(intr) is defined through that path only; a caller
+ * who wants the NDC box to follow a learned focal rebuilds cfg on the host at a time of their choosing.  cfg->focal is not read.
+ *
+ * nerfhip_select_rays_views reading intr in place of cfg->focal (num_views == 1: the single-view form).  One launch, the same kernel. */
+int nerfhip_select_rays_views_intr(const nerfhip_select_cfg* cfg, const float* intr, int num_views, const float* poses,
+                                   int64_t pose_view_stride, int pose_ld, const float* images, const int64_t* select_inds, int64_t n,
+                                   float* rays, float* target, int64_t* inds_out, nerfhip_stream_t stream);
+/* Its VJP w.r.t. the poses and the intrinsics.  g_poses: dev float [V][3][4], g_intr: dev float [4]; either may be NULL, not both;
+ * each one given is written completely (n == 0: exact zeros).  g_poses: nerfhip_select_rays_views_bwd's three launches with dc taken
+ * from intr.  g_intr: with g_d the cotangent of the pre-NDC direction (after the NDC backward, the viewdir normalisation's backward
+ * and the g_rays + g_rays_2 add) and g_dc[k] = sum_c g_d[c] c2w[c][k], ray i adds
+ *     g_fx += -g_dc[0] dc[0] / fx,   g_fy += -g_dc[1] dc[1] / fy,   g_cx += -g_dc[0] / fx,   g_cy += g_dc[1] / fy,
+ * summed over all n rays, whatever their view, along the single-view tree of nerfhip_select_rays_bwd in batch order (G(n) partials
+ * of four sums, then one workgroup; each ray reads the pose of its own view inds[i] / (H W)): two more launches, no grouping, no
+ * atomics, a result that depends on n and the batch order only and is bit-reproducible.  An index outside [0, V H W) is dropped by
+ * both outputs.  Either output has the same bits whether the other one is asked or not.  tmp: dev scratch of
+ * nerfhip_intr_grad_views_tmp_bytes(n, num_views) bytes (-1 where nerfhip_pose_grad_views_tmp_bytes is). */
+int64_t nerfhip_intr_grad_views_tmp_bytes(int64_t n, int num_views);
+int nerfhip_select_rays_views_intr_bwd(const nerfhip_select_cfg* cfg, const float* intr, int num_views, const float* poses,
+                                       int64_t pose_view_stride, int pose_ld, const int64_t* inds, int64_t n, const float* g_rays,
+                                       const float* g_rays_2, int g_rays_stride, void* tmp, int64_t tmp_bytes, float* g_poses,
+                                       float* g_intr, nerfhip_stream_t stream);
+/* nerfhip_ray_bundle from intr (evaluation under learned intrinsics).  Forward only.  One launch, the same kernel. */
+int nerfhip_ray_bundle_intr(int height, int width, const float* intr, const float* c2w, int c2w_ld, const int64_t* pixels, int64_t n,
+                            float* ray_origins, float* ray_directions, nerfhip_stream_t stream);
+/* The parametrisation Adam steps (q: dev float[4], base: dev float[4] = fx0 fy0 cx0 cy0, intr: dev float[4]):
+ *     fx = fx0 exp(q0),   fy = fy0 exp(q1) -- fy0 exp(q0) when tie_focal --,   cx = cx0 + q2,   cy = cy0 + q3.
+ * The log-focal keeps the focal positive and makes Adam's step scale-free.  fp64 between the fp32 inputs and outputs; q = 0 gives
+ * base bit for bit.  One thread, one launch. */
+int nerfhip_intrinsics_fwd(const float* q, const float* base, int tie_focal, float* intr, nerfhip_stream_t stream);
+/* Its pull-back: g_q0 = g_fx fx (+ g_fy fy when tied), g_q1 = g_fy fy (0 when tied), g_q2 = g_cx, g_q3 = g_cy.  mask: dev, one byte
+ * per entry of q, or NULL = every entry learned: an entry whose byte is 0 gets an exact zero (with Adam it never moves).  g_q: dev
+ * float[4], written completely.  The step is nerfhip_adam_step on the four floats.  One launch. */
+int nerfhip_intrinsics_bwd(const float* q, const float* base, int tie_focal, const float* g_intr, const unsigned char* mask,
+                           float* g_q, nerfhip_stream_t stream);
 
 /* ---- camera table: one se(3) twist per view composed onto a base pose (the parametrisation pose refinement steps) --------
  * poses[v] = base[v] * Exp(xi[v]): a camera-frame perturbation.  xi: dev float [V][6] = [w (3), v (3)]; Exp is the full SE(3)

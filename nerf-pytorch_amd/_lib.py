@@ -149,6 +149,14 @@ _PROTOS = {
     "nerfhip_pose_grad_views_tmp_bytes": (c_i64, [c_i64, C.c_int]),
     "nerfhip_select_rays_views_bwd": (C.c_int, [C.POINTER(SelectCfg), C.c_int, c_f, c_i64, C.c_int, c_f, c_i64, c_f, c_f, C.c_int,
                                                 c_f, c_i64, c_f, c_f]),
+    "nerfhip_select_rays_views_intr": (C.c_int, [C.POINTER(SelectCfg), c_f, C.c_int, c_f, c_i64, C.c_int, c_f, c_f, c_i64, c_f, c_f,
+                                                 c_f, c_f]),
+    "nerfhip_intr_grad_views_tmp_bytes": (c_i64, [c_i64, C.c_int]),
+    "nerfhip_select_rays_views_intr_bwd": (C.c_int, [C.POINTER(SelectCfg), c_f, C.c_int, c_f, c_i64, C.c_int, c_f, c_i64, c_f, c_f,
+                                                     C.c_int, c_f, c_i64, c_f, c_f, c_f]),
+    "nerfhip_ray_bundle_intr": (C.c_int, [C.c_int, C.c_int, c_f, c_f, C.c_int, c_f, c_i64, c_f, c_f, c_f]),
+    "nerfhip_intrinsics_fwd": (C.c_int, [c_f, c_f, C.c_int, c_f, c_f]),
+    "nerfhip_intrinsics_bwd": (C.c_int, [c_f, c_f, C.c_int, c_f, c_f, c_f, c_f]),
     "nerfhip_pose_table_fwd": (C.c_int, [c_f, c_f, c_i64, C.c_int, C.c_int, c_f, c_f]),
     "nerfhip_pose_table_bwd": (C.c_int, [c_f, c_f, c_i64, C.c_int, C.c_int, c_f, c_f, c_f, c_f]),
     "nerfhip_plan_window_index": (C.c_int, [C.c_void_p, C.c_void_p]),

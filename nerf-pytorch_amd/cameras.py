@@ -8,6 +8,8 @@ d(loss)/d(poses) back to the twists (nerfhip_pose_table_bwd), and the twists are
 * ``se3_poses(xi, base)`` -- the drop-in form: an autograd node when `xi` requires grad, the same launch otherwise.
 * ``CameraTable`` -- owns the twists, their Adam state and every buffer; ``TrainEngine.step_on_views(cameras=table)`` runs the joint
   field-and-camera step with no host work besides launches.
+* ``Intrinsics`` -- the shared intrinsics (fx, fy, cx, cy) on the device, their log-focal parametrisation and its Adam state;
+  ``TrainEngine.step_on_views(intrinsics=...)`` learns them next to the field and the poses.
 """
 import torch
 
@@ -137,6 +139,92 @@ class CameraTable:
             t = getattr(self, k)
             if tuple(state[k].shape) != tuple(t.shape):
                 raise RuntimeError("CameraTable.load_state_dict: %s has shape %s, the table holds %s"
+                                   % (k, tuple(state[k].shape), tuple(t.shape)))
+            t.copy_(state[k])
+        self.step_count = int(state["step"])
+
+
+_LEARN = {"focal": (True, (1, 0, 0, 0)), "focal_xy": (False, (1, 1, 0, 0)), "all": (False, (1, 1, 1, 1)), (): (False, (0, 0, 0, 0))}
+
+
+class Intrinsics:
+    """The shared intrinsics (fx, fy, cx, cy) of a capture under refinement, resident on the device, with the Adam state of their
+    parametrisation q: fx = fx0 exp(q0), fy = fy0 exp(q1) (exp(q0) when the focals are tied), cx = cx0 + q2, cy = cy0 + q3 -- the
+    log-focal keeps the focal positive and makes Adam's step a relative one.  Every buffer is allocated here once; values(),
+    backward() and step() are one launch each on the current stream of the device, with no host synchronisation, so a learned
+    focal is never read back inside a step.
+
+    focal: one number (fx = fy = focal, cx = float32(width / 2), cy = float32(height / 2): the camera of the scalar path, whose
+    bits values() then gives while q is zero), or the four numbers (fx, fy, cx, cy).  learn: "focal" (one focal: fx and fy tied,
+    the principal point fixed), "focal_xy" (fx and fy apart), "all", or () (nothing moves).  An entry that is not learned gets an
+    exact zero gradient, so its q stays where it is.  The NDC constants of a forward-facing scene are fixed by the caller's
+    `focal_length` and do not follow these values."""
+
+    def __init__(self, height, width, focal, learn="focal", lr=1e-3, betas=(0.9, 0.999), eps=1e-8, device=None):
+        key = tuple(learn) if isinstance(learn, (list, tuple)) else learn
+        if key not in _LEARN:
+            raise RuntimeError('Intrinsics: learn must be "focal", "focal_xy", "all" or () (got %r)' % (learn,))
+        self.dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.dev.type != "cuda":
+            raise RuntimeError("Intrinsics lives on a CUDA (HIP) device (nerf_pytorch_amd has no CPU path)")
+        try:
+            four = [float(v) for v in focal]
+        except TypeError:
+            f = float(focal)
+            four = [f, f, float(torch.tensor(int(width) * 0.5, dtype=torch.float32)), float(torch.tensor(int(height) * 0.5, dtype=torch.float32))]
+        if len(four) != 4 or not (four[0] > 0 and four[1] > 0):
+            raise RuntimeError("Intrinsics: focal must be one positive number or (fx, fy, cx, cy) with positive focals (got %r)" % (focal,))
+        self.lib = L.get_lib()
+        self.height, self.width = int(height), int(width)
+        self.learn = key
+        self.tie_focal, mask = _LEARN[key]
+        self.lr, self.betas, self.eps = lr, betas, eps
+        self.step_count = 0
+        mk = lambda: torch.zeros(4, dtype=torch.float32, device=self.dev)  # noqa: E731
+        self.base = torch.tensor(four, dtype=torch.float32).to(self.dev)
+        self.mask = torch.tensor(mask, dtype=torch.uint8).to(self.dev)
+        self.q, self.exp_avg, self.exp_avg_sq, self.g_q, self.g_intr = mk(), mk(), mk(), mk(), mk()
+        self._values = self.base.clone()
+
+    def values(self):
+        """Evaluates (fx, fy, cx, cy) into the object's own buffer of 4 and returns it (overwritten by the next call): the
+        `intrinsics` of select_training_rays / get_ray_bundle / render_pose_rows."""
+        with L.launch_on(self.q, self.base, self._values) as st:
+            self.lib.intrinsics_fwd(self.q.data_ptr(), self.base.data_ptr(), int(self.tie_focal), self._values.data_ptr(), st)
+        return self._values
+
+    def backward(self, g_intr=None):
+        """d(loss)/d(q) (the object's own buffer) from d(loss)/d(fx, fy, cx, cy): `g_intr`, a contiguous float32 device tensor of
+        4, or None for the object's own `g_intr` buffer (the one a step with intrinsics=... fills)."""
+        g = self.g_intr if g_intr is None else g_intr
+        if (not isinstance(g, torch.Tensor) or g.device != self.dev or g.dtype != torch.float32 or tuple(g.shape) != (4,)
+                or not g.is_contiguous()):
+            raise RuntimeError("Intrinsics: g_intr must be a contiguous float32 (4) tensor on %s" % self.dev)
+        with L.launch_on(self.q, self.base, g, self.mask, self.g_q) as st:
+            self.lib.intrinsics_bwd(self.q.data_ptr(), self.base.data_ptr(), int(self.tie_focal), g.data_ptr(), self.mask.data_ptr(),
+                                    self.g_q.data_ptr(), st)
+        return self.g_q
+
+    def step(self, lr=None):
+        """One Adam step of q on the gradient the last backward() left."""
+        self.step_count += 1
+        b1, b2 = self.betas
+        with L.launch_on(self.q, self.g_q) as st:
+            self.lib.adam_step(self.q.data_ptr(), self.g_q.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), 4,
+                               self.lr if lr is None else lr, b1, b2, self.eps, self.step_count, 1.0, st)
+
+    def state_dict(self):
+        return dict(q=self.q.clone(), exp_avg=self.exp_avg.clone(), exp_avg_sq=self.exp_avg_sq.clone(), step=self.step_count,
+                    base=self.base.clone(), learn=self.learn)
+
+    def load_state_dict(self, state):
+        if "learn" in state and (tuple(state["learn"]) if isinstance(state["learn"], (list, tuple)) else state["learn"]) != self.learn:
+            raise RuntimeError("Intrinsics.load_state_dict: the state was saved with learn=%r, this object has learn=%r"
+                               % (state["learn"], self.learn))
+        for k in ("q", "exp_avg", "exp_avg_sq", "base"):
+            t = getattr(self, k)
+            if tuple(state[k].shape) != tuple(t.shape):
+                raise RuntimeError("Intrinsics.load_state_dict: %s has shape %s, the object holds %s"
                                    % (k, tuple(state[k].shape), tuple(t.shape)))
             t.copy_(state[k])
         self.step_count = int(state["step"])

@@ -79,9 +79,10 @@ extern "C" int nerfhip_select_indices(uint64_t seed, uint64_t step, int64_t popu
 // Image branch, population V * H * W: global index g = v * (H * W) + k addresses view v and the reference's flat select index
 // k of that view.  Pose of view v: poses + v * view_stride, row stride ld; image of view v: targets + v * H * W * channels.
 // Intrinsics, near / far, NDC and viewdirs are shared by all views.  One view (nerfhip_select_rays; the views entry point
-// at V = 1): g is k itself, nothing is divided out.
-NH_KERNEL void k_select_rays(nerfhip_select_cfg s, NhNdc ndc, const float* __restrict__ poses, int64_t view_stride, int ld,
-                             int num_views, const float* __restrict__ cached_o, const float* __restrict__ cached_d,
+// at V = 1): g is k itself, nothing is divided out.  intr (device, fx fy cx cy; nerfhip_select_rays_views_intr) replaces the
+// camera of (s.height, s.width, s.focal) in the pin-hole direction -- and nowhere else: the NDC constants stay ndc's.
+NH_KERNEL void k_select_rays(nerfhip_select_cfg s, NhNdc ndc, const float* __restrict__ intr, const float* __restrict__ poses,
+                             int64_t view_stride, int ld, int num_views, const float* __restrict__ cached_o, const float* __restrict__ cached_d,
                              const float* __restrict__ targets, uint64_t population,
                              const int64_t* __restrict__ inds_in, int64_t n, float* __restrict__ rays,
                              float* __restrict__ target_out, int64_t* __restrict__ inds_out) {
@@ -107,7 +108,9 @@ NH_KERNEL void k_select_rays(nerfhip_select_cfg s, NhNdc ndc, const float* __res
         // coords = stack(meshgrid_xy(arange(H), arange(W)), -1).reshape(-1, 2): entry k is (k % H, k / H), used as
         // (row, col) -- train_nerf.py:214-225
         int64_t row = k % s.height, col = k / s.height;
-        nh_pinhole_ray(s.height, s.width, s.focal, poses + view * view_stride, ld, row, col, o, d);
+        float f[4];
+        nh_intrinsics(intr, s.height, s.width, s.focal, f);
+        nh_pinhole_ray(f, poses + view * view_stride, ld, row, col, o, d);
         pix = base + row * s.width + col;
     } else {
 #pragma unroll
@@ -130,8 +133,8 @@ static NhNdc ndc_of(const nerfhip_select_cfg* cfg) {
 }
 
 // the checks and the launch of the three selection entry points (`what`: the entry point, for the messages)
-static int select_launch(const char* what, const nerfhip_select_cfg* cfg, int num_views, const float* poses, int64_t view_stride,
-                         int ld, const float* co, const float* cd, const float* targets, int64_t population, const int64_t* inds,
+static int select_launch(const char* what, const nerfhip_select_cfg* cfg, const float* intr, int num_views, const float* poses,
+                         int64_t view_stride, int ld, const float* co, const float* cd, const float* targets, int64_t population, const int64_t* inds,
                          int64_t n, float* rays, float* target_out, int64_t* inds_out, nerfhip_stream_t stream) {
     NH_REQUIRE(cfg && n >= 0 && (n == 0 || rays), "%s: bad arguments", what);
     NH_REQUIRE(!targets || (target_out && cfg->channels >= 1 && cfg->channels <= 4), "%s: bad target arguments", what);
@@ -139,7 +142,7 @@ static int select_launch(const char* what, const nerfhip_select_cfg* cfg, int nu
     NH_REQUIRE(inds || (cfg->first >= 0 && cfg->first + n <= population),
                "%s: first + n exceeds the population (sampling is without replacement)", what);
     if (n == 0) return NERFHIP_OK;
-    NH_LAUNCH(k_select_rays, nh_ceil_div(n, 256), 256, 0, stream, *cfg, ndc_of(cfg), poses, view_stride, ld, num_views, co, cd,
+    NH_LAUNCH(k_select_rays, nh_ceil_div(n, 256), 256, 0, stream, *cfg, ndc_of(cfg), intr, poses, view_stride, ld, num_views, co, cd,
               targets, (uint64_t)population, inds, n, rays, target_out, inds_out);
     return nh_launch_status(what);
 }
@@ -168,7 +171,7 @@ extern "C" int nerfhip_select_rays(const nerfhip_select_cfg* cfg, const float* c
                                    const int64_t* select_inds, int64_t n, float* rays, float* target,
                                    int64_t* inds_out, nerfhip_stream_t stream) {
     NH_REQUIRE(cfg && c2w && c2w_ld >= 4 && cfg->height > 0 && cfg->width > 0, "select_rays: bad arguments");
-    return select_launch("select_rays", cfg, 1, c2w, 0, c2w_ld, nullptr, nullptr, image, (int64_t)cfg->height * cfg->width,
+    return select_launch("select_rays", cfg, nullptr, 1, c2w, 0, c2w_ld, nullptr, nullptr, image, (int64_t)cfg->height * cfg->width,
                          select_inds, n, rays, target, inds_out, stream);
 }
 
@@ -177,7 +180,7 @@ extern "C" int nerfhip_select_cached_rays(const nerfhip_select_cfg* cfg, const f
                                           const int64_t* select_inds, int64_t n, float* rays, float* target,
                                           int64_t* inds_out, nerfhip_stream_t stream) {
     NH_REQUIRE(cfg && ray_origins && ray_directions, "select_cached_rays: bad arguments");
-    return select_launch("select_cached_rays", cfg, 0, nullptr, 0, 0, ray_origins, ray_directions, targets, population,
+    return select_launch("select_cached_rays", cfg, nullptr, 0, nullptr, 0, 0, ray_origins, ray_directions, targets, population,
                          select_inds, n, rays, target, inds_out, stream);
 }
 
@@ -186,7 +189,19 @@ extern "C" int nerfhip_select_rays_views(const nerfhip_select_cfg* cfg, int num_
                                          int64_t n, float* rays, float* target, int64_t* inds_out, nerfhip_stream_t stream) {
     int rc = views_check(cfg, num_views, poses, pose_view_stride, pose_ld, "select_rays_views");
     if (rc) return rc;
-    return select_launch("select_rays_views", cfg, num_views, poses, pose_view_stride, pose_ld, nullptr, nullptr, images,
+    return select_launch("select_rays_views", cfg, nullptr, num_views, poses, pose_view_stride, pose_ld, nullptr, nullptr, images,
+                         (int64_t)num_views * cfg->height * cfg->width, select_inds, n, rays, target, inds_out, stream);
+}
+
+extern "C" int nerfhip_select_rays_views_intr(const nerfhip_select_cfg* cfg, const float* intr, int num_views, const float* poses,
+                                              int64_t pose_view_stride, int pose_ld, const float* images,
+                                              const int64_t* select_inds, int64_t n, float* rays, float* target, int64_t* inds_out,
+                                              nerfhip_stream_t stream) {
+    const char* what = "select_rays_views_intr";
+    NH_REQUIRE(intr, "%s: intr must not be NULL", what);
+    int rc = views_check(cfg, num_views, poses, pose_view_stride, pose_ld, what);
+    if (rc) return rc;
+    return select_launch(what, cfg, intr, num_views, poses, pose_view_stride, pose_ld, nullptr, nullptr, images,
                          (int64_t)num_views * cfg->height * cfg->width, select_inds, n, rays, target, inds_out, stream);
 }
 
@@ -212,6 +227,7 @@ constexpr int64_t pv_wgs(int64_t n) {
 struct PoseVjpArgs {
     nerfhip_select_cfg s;
     NhNdc ndc;
+    const float* intr;        // select form: the device intrinsics (fx fy cx cy), or NULL: the camera of (s.height, s.width, s.focal)
     int select;               // 1: select form (row k % height, col k / height; packing / NDC backward); 0: bundle form
     const float* c2w;         // select form only (the pre-NDC ray)
     int ld;
@@ -233,17 +249,20 @@ PoseVjpArgs select_vjp_args(const nerfhip_select_cfg* cfg, const float* c2w, int
     return a;
 }
 
-// this ray's 12 terms: t[c * 4 + k] = g_d[c] dc[k] (k < 3), t[c * 4 + 3] = g_o[c]
+// this ray's camera direction dc under the intrinsics f, and the cotangents go / gd of its pre-NDC origin / direction
 // (ray i of the batch, k: its select index / linear pixel id)
-NH_DEVICE void pose_vjp_ray_at(const PoseVjpArgs& a, int64_t i, int64_t k, float* t) {
+// c2w: the ray's pose (select form only)
+NH_DEVICE void pose_vjp_ray_cot(const PoseVjpArgs& a, const float* f, const float* __restrict__ c2w, int64_t i, int64_t k, float* dc,
+                                float* go, float* gd) {
     int64_t row, col;
     if (a.select) {
         row = k % a.s.height, col = k / a.s.height;  // (k_select_rays)
     } else {
         row = k / a.s.width, col = k % a.s.width;    // (k_ray_bundle)
     }
-    float dc[3], go[3] = {0.f, 0.f, 0.f}, gd[3] = {0.f, 0.f, 0.f};
-    nh_pinhole_cam(a.s.height, a.s.width, a.s.focal, row, col, dc);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) go[c] = 0.f, gd[c] = 0.f;
+    nh_pinhole_cam(f[0], f[1], f[2], f[3], row, col, dc);
     if (a.select) {
         const float* ga = a.g_a + i * a.g_stride;
         const float* gb = a.g_b ? a.g_b + i * a.g_stride : nullptr;
@@ -251,7 +270,7 @@ NH_DEVICE void pose_vjp_ray_at(const PoseVjpArgs& a, int64_t i, int64_t k, float
         const int cols = a.s.use_viewdirs ? 11 : 8;
         for (int c = 0; c < cols; ++c) gr[c] = gb ? ga[c] + gb[c] : ga[c];  // (columns 6, 7: near / far carry no gradient)
         float o[3], d[3];
-        nh_pinhole_ray(a.s.height, a.s.width, a.s.focal, a.c2w, a.ld, row, col, o, d);
+        nh_pinhole_ray(f, c2w, a.ld, row, col, o, d);
         if (a.s.ndc) {
             nh_ndc_ray_vjp(a.ndc, o, d, gr, gr + 3, go, gd);
         } else {
@@ -273,6 +292,12 @@ NH_DEVICE void pose_vjp_ray_at(const PoseVjpArgs& a, int64_t i, int64_t k, float
             if (a.g_b) gd[c] = a.g_b[i * 3 + c];
         }
     }
+}
+// this ray's 12 terms: t[c * 4 + k] = g_d[c] dc[k] (k < 3), t[c * 4 + 3] = g_o[c]
+NH_DEVICE void pose_vjp_ray_at(const PoseVjpArgs& a, int64_t i, int64_t k, float* t) {
+    float f[4], dc[3], go[3], gd[3];
+    nh_intrinsics(a.intr, a.s.height, a.s.width, a.s.focal, f);
+    pose_vjp_ray_cot(a, f, a.c2w, i, k, dc, go, gd);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         t[c * 4 + 0] = gd[c] * dc[0];
@@ -283,17 +308,19 @@ NH_DEVICE void pose_vjp_ray_at(const PoseVjpArgs& a, int64_t i, int64_t k, float
 }
 NH_DEVICE void pose_vjp_ray(const PoseVjpArgs& a, int64_t i, float* t) { pose_vjp_ray_at(a, i, a.inds ? a.inds[i] : i, t); }
 
-// the 12 sums of a workgroup from its threads' sums: xor butterfly per wave, then the 4 waves in wave order -> dst[12]
-NH_DEVICE void pv_block_sum(float* acc, float (*s_part)[12], float* dst) {
+// the NS sums of a workgroup from its threads' sums: xor butterfly per wave, then the 4 waves in wave order -> dst[NS]
+// (NS = 12: a pose; NS = 4: the intrinsics)
+template <int NS>
+NH_DEVICE void pv_block_sum(float* acc, float (*s_part)[NS], float* dst) {
 #pragma unroll
-    for (int j = 0; j < 12; ++j) acc[j] = nh_wave_sum(acc[j]);
+    for (int j = 0; j < NS; ++j) acc[j] = nh_wave_sum(acc[j]);
     const int wave = nh_wave_in_block();
     if (nh_lane() == 0) {
 #pragma unroll
-        for (int j = 0; j < 12; ++j) s_part[wave][j] = acc[j];
+        for (int j = 0; j < NS; ++j) s_part[wave][j] = acc[j];
     }
     nh_block_sync();
-    if (threadIdx.x < 12) {
+    if (threadIdx.x < NS) {
         float v = s_part[0][threadIdx.x];
         for (int w = 1; w < PV_THREADS / 64; ++w) v += s_part[w][threadIdx.x];
         dst[threadIdx.x] = v;
@@ -312,20 +339,22 @@ NH_KERNEL void k_pose_vjp_part(PoseVjpArgs a) {
 #pragma unroll
         for (int j = 0; j < 12; ++j) acc[j] += t[j];
     }
-    pv_block_sum(acc, s_part, a.tmp + (int64_t)blockIdx.x * 12);
+    pv_block_sum<12>(acc, s_part, a.tmp + (int64_t)blockIdx.x * 12);
 }
 
-// workgroup `view` sums its partials part[slot0 .. slot0 + wgs - 1][12] into g[view][12].  Single view (cnt == NULL): one
+// workgroup `view` (NS waves) sums its partials part[slot0 .. slot0 + wgs - 1][NS] into g[view][NS].  Single view (cnt == NULL): one
 // workgroup, the first `wgs` partials.  Views: the G(cnt[view]) partials from slot off[view] / 256 + view (k_pose_views_part).
+// (profile names: the pose instantiation keeps "k_pose_vjp_sum", the one the existing records and scripts filter on; <4> is "k_intr_vjp_sum")
+template <int NS>
 NH_KERNEL void k_pose_vjp_sum(const float* __restrict__ part, int wgs, const int* __restrict__ cnt, const int* __restrict__ off,
                               float* __restrict__ g) {
     const int j = nh_wave_in_block(), lane = nh_lane(), view = (int)blockIdx.x;
     int64_t slot0 = 0;
     if (cnt) wgs = (int)pv_wgs(cnt[view]), slot0 = off[view] / PV_THREADS + view;
     float v = 0.0f;
-    for (int q = lane; q < wgs; q += 64) v += part[(slot0 + q) * 12 + j];
+    for (int q = lane; q < wgs; q += 64) v += part[(slot0 + q) * NS + j];
     v = nh_wave_sum(v);
-    if (lane == 0) g[(int64_t)view * 12 + j] = v;
+    if (lane == 0) g[(int64_t)view * NS + j] = v;
 }
 
 int pose_vjp_launch(const PoseVjpArgs& a, int64_t tmp_bytes, float* g_c2w, nerfhip_stream_t stream, const char* what) {
@@ -337,7 +366,7 @@ int pose_vjp_launch(const PoseVjpArgs& a, int64_t tmp_bytes, float* g_c2w, nerfh
         int rc = nh_launch_status(what);
         if (rc) return rc;
     }
-    NH_LAUNCH(k_pose_vjp_sum, 1, 12 * 64, 0, stream, (const float*)a.tmp, (int)wgs, (const int*)nullptr, (const int*)nullptr,
+    NH_LAUNCH_NAMED("k_pose_vjp_sum", k_pose_vjp_sum<12>, 1, 12 * 64, 0, stream, (const float*)a.tmp, (int)wgs, (const int*)nullptr, (const int*)nullptr,
               g_c2w);  // (n == 0: zeros)
     return nh_launch_status(what);
 }
@@ -446,12 +475,99 @@ NH_KERNEL void k_pose_views_part(PoseViewsArgs p) {
 #pragma unroll
         for (int j = 0; j < 12; ++j) acc[j] += t[j];
     }
-    pv_block_sum(acc, s_part, p.a.tmp + (int64_t)w * 12);
+    pv_block_sum<12>(acc, s_part, p.a.tmp + (int64_t)w * 12);
 }
 
 int64_t pv_views_words(int64_t n, int num_views, int64_t* slots) {
     *slots = n / PV_THREADS + num_views;
     return *slots * 12 + 2 * (int64_t)num_views + n;
+}
+
+// ---- the VJP w.r.t. the shared intrinsics (fx, fy, cx, cy) -------------------------------------------------------------------------
+// dc = ((col - cx) / fx, -(row - cy) / fy, -1) and d = R dc: with g_dc[k] = sum_c g_d[c] R[c][k] (g_d: pose_vjp_ray_cot's, the cotangent
+// of the pre-NDC direction), ray i contributes
+//     g_fx += -g_dc[0] dc[0] / fx,   g_fy += -g_dc[1] dc[1] / fy,   g_cx += -g_dc[0] / fx,   g_cy += g_dc[1] / fy.
+// The intrinsics enter through the pin-hole direction only: the NDC constants are those of cfg and carry no gradient.  The intrinsics
+// are shared by the views, so this is ONE sum over all n rays in batch order -- the single-view tree above (k_pose_vjp_part's loop,
+// pv_block_sum<4>, k_pose_vjp_sum<4>) with four sums in place of twelve; each ray reads the pose of its own view, inds[i] / (H W).  No
+// grouping, no atomics: the order depends on n only.  An index outside [0, V H W) contributes nothing (as it belongs to no view above).
+NH_KERNEL void k_intr_vjp_part(PoseViewsArgs p, float* __restrict__ part) {
+    NH_SHARED float s_part[PV_THREADS / 64][4];
+    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f}, f[4];
+    nh_intrinsics(p.a.intr, p.a.s.height, p.a.s.width, p.a.s.focal, f);
+    const int64_t population = (int64_t)p.num_views * p.hw;
+    const int64_t step = (int64_t)gridDim.x * PV_THREADS;
+    for (int64_t i = (int64_t)blockIdx.x * PV_THREADS + threadIdx.x; i < p.a.n; i += step) {
+        const int64_t g = p.a.inds[i];
+        if (g < 0 || g >= population) continue;
+        const int64_t view = p.num_views > 1 ? g / p.hw : 0;
+        const float* __restrict__ c2w = p.a.c2w + view * p.view_stride;
+        float dc[3], go[3], gd[3], gdc[2];
+        pose_vjp_ray_cot(p.a, f, c2w, i, g - view * p.hw, dc, go, gd);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            float v = gd[0] * c2w[k];
+            v = v + gd[1] * c2w[p.a.ld + k];
+            v = v + gd[2] * c2w[2 * p.a.ld + k];
+            gdc[k] = v;
+        }
+        acc[0] += -(gdc[0] * dc[0]) / f[0];
+        acc[1] += -(gdc[1] * dc[1]) / f[1];
+        acc[2] += -gdc[0] / f[0];
+        acc[3] += gdc[1] / f[1];
+    }
+    pv_block_sum<4>(acc, s_part, part + (int64_t)blockIdx.x * 4);
+}
+
+// both forms of the views VJP: g_poses (the three launches above) and / or g_intr (two launches); intr == NULL: cfg's camera
+int views_bwd(const char* what, const nerfhip_select_cfg* cfg, const float* intr, int num_views, const float* poses,
+              int64_t pose_view_stride, int pose_ld, const int64_t* inds, int64_t n, const float* g_rays, const float* g_rays_2,
+              int g_rays_stride, void* tmp, int64_t need, int64_t tmp_bytes, const char* need_name, float* g_poses, float* g_intr,
+              nerfhip_stream_t stream) {
+    int rc = views_check(cfg, num_views, poses, pose_view_stride, pose_ld, what);
+    if (rc) return rc;
+    NH_REQUIRE(n >= 0 && n < ((int64_t)1 << 31) && (n == 0 || (inds && g_rays)), "%s: bad arguments", what);
+    NH_REQUIRE(g_rays_stride >= (cfg->use_viewdirs ? 11 : 8), "%s: g_rays_stride must cover the %d columns of a ray row", what,
+               cfg->use_viewdirs ? 11 : 8);
+    NH_REQUIRE(tmp_bytes >= need && (need == 0 || tmp), "%s: tmp must hold %s(n, num_views) = %lld bytes", what, need_name,
+               (long long)need);
+    PoseViewsArgs p;
+    memset(&p, 0, sizeof(p));
+    int64_t slots = 0, words = 0;
+    if (n > 0) {
+        words = pv_views_words(n, num_views, &slots);
+        p.a = select_vjp_args(cfg, poses, pose_ld, inds, n, g_rays, g_rays_2, g_rays_stride, tmp);
+        p.a.intr = intr;
+        p.num_views = num_views, p.view_stride = pose_view_stride, p.hw = (int64_t)cfg->height * cfg->width;
+        p.cnt = (int*)tmp + slots * 12, p.off = p.cnt + num_views, p.list = p.off + num_views;
+    }
+    if (g_poses) {
+        if (n > 0) {
+            NH_LAUNCH(k_pose_views_group, num_views, PV_THREADS, 0, stream, p);
+            rc = nh_launch_status(what);
+            if (rc) return rc;
+            NH_LAUNCH(k_pose_views_part, slots, PV_THREADS, 0, stream, p);
+            rc = nh_launch_status(what);
+            if (rc) return rc;
+        }
+        NH_LAUNCH_NAMED("k_pose_vjp_sum", k_pose_vjp_sum<12>, num_views, 12 * 64, 0, stream, (const float*)p.a.tmp, 0, (const int*)p.cnt, (const int*)p.off,
+                  g_poses);  // (n == 0: cnt is NULL, zeros)
+        rc = nh_launch_status(what);
+        if (rc) return rc;
+    }
+    if (g_intr) {
+        float* part = n > 0 ? (float*)tmp + words : nullptr;  // [G(n)][4], behind the pose VJP's words
+        const int64_t wgs = pv_wgs(n);
+        if (wgs > 0) {
+            NH_LAUNCH(k_intr_vjp_part, wgs, PV_THREADS, 0, stream, p, part);
+            rc = nh_launch_status(what);
+            if (rc) return rc;
+        }
+        NH_LAUNCH_NAMED("k_intr_vjp_sum", k_pose_vjp_sum<4>, 1, 4 * 64, 0, stream, (const float*)part, (int)wgs, (const int*)nullptr, (const int*)nullptr,
+                  g_intr);  // (n == 0: zeros)
+        rc = nh_launch_status(what);
+    }
+    return rc;
 }
 
 }  // namespace
@@ -462,37 +578,32 @@ extern "C" int64_t nerfhip_pose_grad_views_tmp_bytes(int64_t n, int num_views) {
     return n == 0 ? 0 : pv_views_words(n, num_views, &slots) * (int64_t)sizeof(float);
 }
 
+extern "C" int64_t nerfhip_intr_grad_views_tmp_bytes(int64_t n, int num_views) {
+    const int64_t b = nerfhip_pose_grad_views_tmp_bytes(n, num_views);
+    return b < 0 ? -1 : b + pv_wgs(n) * 4 * (int64_t)sizeof(float);
+}
+
+extern "C" int nerfhip_select_rays_views_intr_bwd(const nerfhip_select_cfg* cfg, const float* intr, int num_views, const float* poses,
+                                                  int64_t pose_view_stride, int pose_ld, const int64_t* inds, int64_t n,
+                                                  const float* g_rays, const float* g_rays_2, int g_rays_stride, void* tmp,
+                                                  int64_t tmp_bytes, float* g_poses, float* g_intr, nerfhip_stream_t stream) {
+    const char* what = "select_rays_views_intr_bwd";
+    NH_REQUIRE(intr, "%s: intr must not be NULL", what);
+    NH_REQUIRE(g_poses || g_intr, "%s: g_poses and g_intr must not both be NULL", what);
+    return views_bwd(what, cfg, intr, num_views, poses, pose_view_stride, pose_ld, inds, n, g_rays, g_rays_2, g_rays_stride, tmp,
+                     nerfhip_intr_grad_views_tmp_bytes(n, num_views), tmp_bytes, "nerfhip_intr_grad_views_tmp_bytes", g_poses, g_intr,
+                     stream);
+}
+
 extern "C" int nerfhip_select_rays_views_bwd(const nerfhip_select_cfg* cfg, int num_views, const float* poses,
                                              int64_t pose_view_stride, int pose_ld, const int64_t* inds, int64_t n,
                                              const float* g_rays, const float* g_rays_2, int g_rays_stride, void* tmp,
                                              int64_t tmp_bytes, float* g_poses, nerfhip_stream_t stream) {
     const char* what = "select_rays_views_bwd";
-    int rc = views_check(cfg, num_views, poses, pose_view_stride, pose_ld, what);
-    if (rc) return rc;
-    NH_REQUIRE(n >= 0 && n < ((int64_t)1 << 31) && g_poses && (n == 0 || (inds && g_rays)), "%s: bad arguments", what);
-    NH_REQUIRE(g_rays_stride >= (cfg->use_viewdirs ? 11 : 8), "%s: g_rays_stride must cover the %d columns of a ray row", what,
-               cfg->use_viewdirs ? 11 : 8);
-    const int64_t need = nerfhip_pose_grad_views_tmp_bytes(n, num_views);
-    NH_REQUIRE(tmp_bytes >= need && (need == 0 || tmp),
-               "%s: tmp must hold nerfhip_pose_grad_views_tmp_bytes(n, num_views) = %lld bytes", what, (long long)need);
-    PoseViewsArgs p;
-    memset(&p, 0, sizeof(p));
-    if (n > 0) {
-        int64_t slots;
-        pv_views_words(n, num_views, &slots);
-        p.a = select_vjp_args(cfg, poses, pose_ld, inds, n, g_rays, g_rays_2, g_rays_stride, tmp);
-        p.num_views = num_views, p.view_stride = pose_view_stride, p.hw = (int64_t)cfg->height * cfg->width;
-        p.cnt = (int*)tmp + slots * 12, p.off = p.cnt + num_views, p.list = p.off + num_views;
-        NH_LAUNCH(k_pose_views_group, num_views, PV_THREADS, 0, stream, p);
-        rc = nh_launch_status(what);
-        if (rc) return rc;
-        NH_LAUNCH(k_pose_views_part, slots, PV_THREADS, 0, stream, p);
-        rc = nh_launch_status(what);
-        if (rc) return rc;
-    }
-    NH_LAUNCH(k_pose_vjp_sum, num_views, 12 * 64, 0, stream, (const float*)p.a.tmp, 0, (const int*)p.cnt, (const int*)p.off,
-              g_poses);  // (n == 0: cnt is NULL, zeros)
-    return nh_launch_status(what);
+    NH_REQUIRE(g_poses, "%s: bad arguments", what);
+    return views_bwd(what, cfg, nullptr, num_views, poses, pose_view_stride, pose_ld, inds, n, g_rays, g_rays_2, g_rays_stride, tmp,
+                     nerfhip_pose_grad_views_tmp_bytes(n, num_views), tmp_bytes, "nerfhip_pose_grad_views_tmp_bytes", g_poses, nullptr,
+                     stream);
 }
 
 extern "C" int64_t nerfhip_pose_grad_tmp_bytes(int64_t n) { return n < 0 ? -1 : pv_wgs(n) * 12 * (int64_t)sizeof(float); }

@@ -19,14 +19,16 @@ void nh_set_error(const char* fmt, ...) {
 extern "C" const char* nerfhip_last_error(void) { return g_err; }
 extern "C" int nerfhip_version(void) {
 #ifdef NH_DIAG  // (make variant: an A/B or diagnostic build -- nh_diag.h; the Python package refuses it)
-    return 109 + NH_DIAG_VERSION_FLAG;
+    return 110 + NH_DIAG_VERSION_FLAG;
 #else
-    return 109;  // (102: round 6 -- the compacted backward's three entry points; 103: + the fused backward modes 3 / 4 of 64-wide nets; 104: + mode 5;
+    return 110;  // (102: round 6 -- the compacted backward's three entry points; 103: + the fused backward modes 3 / 4 of 64-wide nets; 104: + mode 5;
                  // 105: + the pose VJP, nerfhip_pose_grad_tmp_bytes / nerfhip_ray_bundle_bwd / nerfhip_select_rays_bwd;
                  // 106: + batches over a stack of views, nerfhip_select_rays_views / _views_bwd / nerfhip_pose_grad_views_tmp_bytes;
                  // 107: + the camera table, nerfhip_pose_table_fwd / nerfhip_pose_table_bwd;
                  // 108: + the encoding window, nerfhip_plan_window_index / nerfhip_window_params / nerfhip_window_grads;
-                 // 109: + the frozen ray gradient, nerfhip_render_grad_rays / nerfhip_render_grad_rays_tmp_bytes)
+                 // 109: + the frozen ray gradient, nerfhip_render_grad_rays / nerfhip_render_grad_rays_tmp_bytes;
+                 // 110: + device intrinsics, nerfhip_select_rays_views_intr / _intr_bwd / nerfhip_intr_grad_views_tmp_bytes /
+                 //      nerfhip_ray_bundle_intr / nerfhip_intrinsics_fwd / nerfhip_intrinsics_bwd)
 #endif
 }
 extern "C" int nerfhip_is_emulated(void) {
@@ -165,14 +167,16 @@ extern "C" int nerfhip_profile_report(char* buf, int64_t cap) {
 }
 
 // ---- K1 get_ray_bundle (nerf/nerf_helpers.py:67-110) ----------------------------------------------------------------
-NH_KERNEL void k_ray_bundle(int height, int width, float focal, const float* __restrict__ c2w, int ld,
+// intr (device, fx fy cx cy; nerfhip_ray_bundle_intr), or NULL: the camera of (height, width, focal)
+NH_KERNEL void k_ray_bundle(int height, int width, float focal, const float* __restrict__ intr, const float* __restrict__ c2w, int ld,
                             const int64_t* __restrict__ pixels, int64_t n, float* __restrict__ ro,
                             float* __restrict__ rd) {
     int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n) return;
     int64_t p = pixels ? pixels[idx] : idx;
-    float o[3], d[3];
-    nh_pinhole_ray(height, width, focal, c2w, ld, p / width, p % width, o, d);
+    float o[3], d[3], f[4];
+    nh_intrinsics(intr, height, width, focal, f);
+    nh_pinhole_ray(f, c2w, ld, p / width, p % width, o, d);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         rd[idx * 3 + c] = d[c];
@@ -187,9 +191,58 @@ extern "C" int nerfhip_ray_bundle(int height, int width, float focal, const floa
                "ray_bundle: bad arguments");
     NH_REQUIRE(pixels || n == (int64_t)height * width, "ray_bundle: n must be height*width when pixels is NULL");
     if (n == 0) return NERFHIP_OK;
-    NH_LAUNCH(k_ray_bundle, nh_ceil_div(n, 256), 256, 0, stream, height, width, focal, c2w, c2w_ld, pixels, n,
+    NH_LAUNCH(k_ray_bundle, nh_ceil_div(n, 256), 256, 0, stream, height, width, focal, (const float*)nullptr, c2w, c2w_ld, pixels, n,
               ray_origins, ray_directions);
     return nh_launch_status("ray_bundle");
+}
+
+extern "C" int nerfhip_ray_bundle_intr(int height, int width, const float* intr, const float* c2w, int c2w_ld, const int64_t* pixels,
+                                       int64_t n, float* ray_origins, float* ray_directions, nerfhip_stream_t stream) {
+    NH_REQUIRE(intr, "ray_bundle_intr: intr must not be NULL");
+    NH_REQUIRE(height > 0 && width > 0 && c2w && ray_origins && ray_directions && c2w_ld >= 4 && n >= 0,
+               "ray_bundle_intr: bad arguments");
+    NH_REQUIRE(pixels || n == (int64_t)height * width, "ray_bundle_intr: n must be height*width when pixels is NULL");
+    if (n == 0) return NERFHIP_OK;
+    NH_LAUNCH(k_ray_bundle, nh_ceil_div(n, 256), 256, 0, stream, height, width, 0.0f, intr, c2w, c2w_ld, pixels, n, ray_origins,
+              ray_directions);
+    return nh_launch_status("ray_bundle_intr");
+}
+
+// ---- the intrinsics' parametrisation (what Adam steps when the camera model is learned) -----------------------------------------
+// intr = (fx0 exp(q0), fy0 exp(q1) -- exp(q0) when tied --, cx0 + q2, cy0 + q3): the log-focal keeps the focal positive and makes
+// Adam's step a relative one.  One thread; fp64 between the fp32 inputs and outputs, so q = 0 gives base bit for bit
+// (exp(0.0) = 1.0 exactly).
+NH_KERNEL void k_intrinsics_fwd(const float* __restrict__ q, const float* __restrict__ base, int tie_focal, float* __restrict__ intr) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    intr[0] = (float)((double)base[0] * exp((double)q[0]));
+    intr[1] = (float)((double)base[1] * exp((double)q[tie_focal ? 0 : 1]));
+    intr[2] = (float)((double)base[2] + (double)q[2]);
+    intr[3] = (float)((double)base[3] + (double)q[3]);
+}
+// g_q from g_intr: d fx / d q0 = fx, d fy / d q1 (q0 when tied) = fy, d cx / d q2 = d cy / d q3 = 1; mask (one byte per entry of q,
+// or NULL = all on): a masked entry (byte 0) gets an exact zero, so Adam never moves it
+NH_KERNEL void k_intrinsics_bwd(const float* __restrict__ q, const float* __restrict__ base, int tie_focal,
+                                const float* __restrict__ g_intr, const unsigned char* __restrict__ mask, float* __restrict__ g_q) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const double fx = (double)base[0] * exp((double)q[0]);
+    const double fy = (double)base[1] * exp((double)q[tie_focal ? 0 : 1]);
+    const double gx = (double)g_intr[0] * fx, gy = (double)g_intr[1] * fy;
+    const float g[4] = {(float)(tie_focal ? gx + gy : gx), tie_focal ? 0.0f : (float)gy, g_intr[2], g_intr[3]};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) g_q[k] = (mask && !mask[k]) ? 0.0f : g[k];
+}
+
+extern "C" int nerfhip_intrinsics_fwd(const float* q, const float* base, int tie_focal, float* intr, nerfhip_stream_t stream) {
+    NH_REQUIRE(q && base && intr, "intrinsics_fwd: q, base and intr must not be NULL");
+    NH_LAUNCH(k_intrinsics_fwd, 1, 64, 0, stream, q, base, tie_focal, intr);
+    return nh_launch_status("intrinsics_fwd");
+}
+
+extern "C" int nerfhip_intrinsics_bwd(const float* q, const float* base, int tie_focal, const float* g_intr, const unsigned char* mask,
+                                      float* g_q, nerfhip_stream_t stream) {
+    NH_REQUIRE(q && base && g_intr && g_q, "intrinsics_bwd: q, base, g_intr and g_q must not be NULL");
+    NH_LAUNCH(k_intrinsics_bwd, 1, 64, 0, stream, q, base, tie_focal, g_intr, mask, g_q);
+    return nh_launch_status("intrinsics_bwd");
 }
 
 // ---- ndc_rays (nerf/nerf_helpers.py:170-197) -------------------------------------------------------------------------

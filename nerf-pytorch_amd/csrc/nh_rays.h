@@ -4,19 +4,30 @@
 #include "nh_device.h"
 
 // get_ray_bundle (nerf/nerf_helpers.py:67-110)
-// camera-space direction of pixel (row, col) of a height x width image: ((col - W/2)/f, -(row - H/2)/f, -1)
-NH_DEVICE void nh_pinhole_cam(int height, int width, float focal, int64_t row, int64_t col, float* dc) {
+// camera-space direction of pixel (row, col) under the intrinsics (fx, fy, cx, cy), in pixels: ((col - cx)/fx, -(row - cy)/fy, -1)
+NH_DEVICE void nh_pinhole_cam(float fx, float fy, float cx, float cy, int64_t row, int64_t col, float* dc) {
     float ii = (float)col;  // x
     float jj = (float)row;  // y
-    dc[0] = (ii - (float)(width * 0.5)) / focal;
-    dc[1] = -(jj - (float)(height * 0.5)) / focal;
+    dc[0] = (ii - cx) / fx;
+    dc[1] = -(jj - cy) / fy;
     dc[2] = -1.0f;
 }
+// the reference's camera: one focal, the principal point at the centre of a height x width image -- ((col - W/2)/f, -(row - H/2)/f, -1)
+NH_DEVICE void nh_pinhole_cam(int height, int width, float focal, int64_t row, int64_t col, float* dc) {
+    nh_pinhole_cam(focal, focal, (float)(width * 0.5), (float)(height * 0.5), row, col, dc);
+}
+// the four intrinsics of a call: intr (device, fx fy cx cy) when given, else the reference's camera of (height, width, focal)
+NH_DEVICE void nh_intrinsics(const float* __restrict__ intr, int height, int width, float focal, float* f) {
+    if (intr) {
+        f[0] = intr[0], f[1] = intr[1], f[2] = intr[2], f[3] = intr[3];
+    } else {
+        f[0] = focal, f[1] = focal, f[2] = (float)(width * 0.5), f[3] = (float)(height * 0.5);
+    }
+}
 // one pin-hole ray: d = c2w[:3, :3] dc, o = c2w[:3, 3]
-NH_DEVICE void nh_pinhole_ray(int height, int width, float focal, const float* __restrict__ c2w, int ld, int64_t row,
-                              int64_t col, float* o, float* d) {
+NH_DEVICE void nh_pinhole_ray(const float* f, const float* __restrict__ c2w, int ld, int64_t row, int64_t col, float* o, float* d) {
     float dc[3];
-    nh_pinhole_cam(height, width, focal, row, col, dc);
+    nh_pinhole_cam(f[0], f[1], f[2], f[3], row, col, dc);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         float v = dc[0] * c2w[c * ld + 0];
@@ -25,6 +36,12 @@ NH_DEVICE void nh_pinhole_ray(int height, int width, float focal, const float* _
         d[c] = v;
         o[c] = c2w[c * ld + 3];
     }
+}
+NH_DEVICE void nh_pinhole_ray(int height, int width, float focal, const float* __restrict__ c2w, int ld, int64_t row,
+                              int64_t col, float* o, float* d) {
+    float f[4];
+    nh_intrinsics(nullptr, height, width, focal, f);
+    nh_pinhole_ray(f, c2w, ld, row, col, o, d);
 }
 
 // ndc_rays (nerf/nerf_helpers.py:170-197)

@@ -431,7 +431,7 @@ class TrainEngine:
         return self.loss
 
     def step_on_image(self, image, pose, height, width, focal_length, options, num_random_rays, lr=None, global_rays=None,
-                      pose_grad=None):
+                      pose_grad=None, intrinsics=None):
         """One whole iteration of the reference's loop body (train_nerf.py:210-270) on a resident training image:
         on-device selection of this rank's distinct pixels (ranks take disjoint slices of one permutation keyed by
         (seed, iteration)), their rays and targets, then `step`.  No host work besides launches.
@@ -442,18 +442,23 @@ class TrainEngine:
         into it (pose refinement: the render backward with the ray gradient, then the pose VJP of the selection on the main
         stream after the two streams joined, nerfhip_select_rays_bwd; still no host synchronisation).  The engine's Adam
         updates the nets as usual (lr=0 freezes them); a pose parametrisation of one's own takes the gradient with
-        torch.autograd.backward(pose_expr[:3, :4], pose_grad).  One rank only."""
+        torch.autograd.backward(pose_expr[:3, :4], pose_grad).  One rank only.
+        intrinsics: None, or a cameras.Intrinsics on the engine's device: the rays are generated from its (fx, fy, cx, cy), read on
+        the device, and the step learns them -- see step_on_views.  `focal_length` must still be passed: it fixes the NDC constants."""
         from .train_utils import select_training_rays, select_training_rays_bwd
         if pose_grad is not None:
             self._no_pose_grad_across_ranks("pose_grad")
             self._check_pose_grads("pose_grad", pose_grad, (3, 4))
+        if intrinsics is not None:
+            return self._step_with_intrinsics(intrinsics, (height, width, focal_length, options), pose, image, False, pose_grad,
+                                              num_random_rays, lr, global_rays)
         return self._step_on_selection(
             lambda **kw: select_training_rays(height, width, focal_length, pose, image, options=options, **kw),
             lambda used, g, g2: select_training_rays_bwd(height, width, focal_length, pose, used, g, options, g2, out=pose_grad),
             pose_grad, num_random_rays, lr, global_rays)
 
     def step_on_views(self, images, poses, height, width, focal_length, options, num_random_rays, lr=None, global_rays=None,
-                      pose_grads=None, cameras=None):
+                      pose_grads=None, cameras=None, intrinsics=None):
         """step_on_image over a resident stack of views: this rank's rays are drawn from ALL of `images` (V, H, W, 3|4) with the
         rays of each generated from its own row of `poses` (V, >=3, 4) -- train_utils.select_training_rays_views --, then `step`.
         Same rank slicing (first = rank * n, or the shard_bounds slice of `global_rays`) over the permutation of V * H * W, same
@@ -465,40 +470,66 @@ class TrainEngine:
         cameras: None, or a cameras.CameraTable on the engine's device (then `poses` must be None and `pose_grads` must not be
         given): the joint field-and-camera step -- the table composes its poses, the batch is drawn from them, the pose gradients
         land in the table's own buffer and are pulled back to its twists, the nets take their Adam step and the twists theirs (the
-        table's own lr).  All of it on the main stream after the two streams joined; no host synchronisation.  One rank only."""
+        table's own lr).  All of it on the main stream after the two streams joined; no host synchronisation.  One rank only.
+        intrinsics: None, or a cameras.Intrinsics on the engine's device: the step learns the shared (fx, fy, cx, cy) next to the
+        field (and the poses, when asked) -- intrinsics.values() -> selection from them -> forward_backward with the ray gradient ->
+        ONE VJP call that fills the pose gradients (when asked) and intrinsics.g_intr -> cameras.backward() -> intrinsics.backward()
+        -> the nets' Adam -> cameras.step() -> intrinsics.step().  Allowed with neither pose_grads nor cameras (it turns the ray
+        gradient on).  `focal_length` must still be passed: it fixes the NDC constants, which do not follow the learned values.  One
+        rank only."""
         from .train_utils import select_training_rays_views, select_training_rays_views_bwd
         # cameras.poses() -> selection -> forward_backward with the ray gradient -> the per-view pose VJP into cameras.g_poses ->
         # cameras.backward() -> the nets' optimizer_step -> cameras.step()
+        if intrinsics is not None:   # (here, not in _step_with_intrinsics: I.values() is launched before cameras.poses(), the step's order)
+            values = self._intrinsics_values(intrinsics)
         poses, pose_grads = self._resolve_cameras(poses, pose_grads, cameras)
+        if intrinsics is not None:
+            return self._step_with_intrinsics(intrinsics, (height, width, focal_length, options), poses, images, True, pose_grads,
+                                              num_random_rays, lr, global_rays, cameras, values=values)
         return self._step_on_selection(
             lambda **kw: select_training_rays_views(height, width, focal_length, poses, images, options=options, **kw),
             lambda used, g, g2: select_training_rays_views_bwd(height, width, focal_length, poses, used, g, options, g2, out=pose_grads),
             pose_grads, num_random_rays, lr, global_rays, cameras)
 
-    def localize_on_image(self, image, pose, height, width, focal_length, options, num_random_rays, pose_grad):
+    def localize_on_image(self, image, pose, height, width, focal_length, options, num_random_rays, pose_grad=None, intrinsics=None):
         """step_on_image(pose_grad=...) for FROZEN nets (camera localisation against a trained field): the same selection, forward and
         pose VJP, with the render backward w.r.t. the rays alone (forward_backward(frozen=True)) and no optimizer step.  Nothing of
         the nets or their optimiser moves -- flat_params, exp_avg, exp_avg_sq, grad, the packed images and step_count are what they
         were, bit for bit --; the selection and the in-kernel draws are keyed by `localize_count`, which advances instead.
-        pose_grad: a contiguous float32 (3, 4) tensor on the engine's device, overwritten with d(loss)/d(pose[:3, :4]).  One rank only."""
+        pose_grad: a contiguous float32 (3, 4) tensor on the engine's device, overwritten with d(loss)/d(pose[:3, :4]).  One rank only.
+        intrinsics: None, or a cameras.Intrinsics (see step_on_views): its values are learned against the frozen field; then
+        pose_grad may be None."""
         from .train_utils import select_training_rays, select_training_rays_bwd
         self._no_pose_grad_across_ranks("localize_on_image")
-        self._check_pose_grads("pose_grad", pose_grad, (3, 4))
+        if pose_grad is None and intrinsics is None:
+            raise RuntimeError("TrainEngine: localize_on_image needs pose_grad=... or intrinsics=...")
+        if pose_grad is not None:
+            self._check_pose_grads("pose_grad", pose_grad, (3, 4))
+        if intrinsics is not None:
+            return self._step_with_intrinsics(intrinsics, (height, width, focal_length, options), pose, image, False, pose_grad,
+                                              num_random_rays, None, None, frozen=True)
         return self._step_on_selection(
             lambda **kw: select_training_rays(height, width, focal_length, pose, image, options=options, **kw),
             lambda used, g, g2: select_training_rays_bwd(height, width, focal_length, pose, used, g, options, g2, out=pose_grad),
             pose_grad, num_random_rays, None, None, frozen=True)
 
-    def localize_on_views(self, images, poses, height, width, focal_length, options, num_random_rays, pose_grads=None, cameras=None):
+    def localize_on_views(self, images, poses, height, width, focal_length, options, num_random_rays, pose_grads=None, cameras=None,
+                          intrinsics=None):
         """step_on_views for FROZEN nets (see localize_on_image): with pose_grads (V, 3, 4) the step writes d(loss)/d(poses[v, :3, :4])
         of every view; with cameras=T (then poses must be None and pose_grads must not be given) the table composes its poses, takes
         the gradients in its own buffer, pulls them back to its twists (T.backward()) and steps them (T.step()) -- the nets stay put.
-        One rank only."""
+        intrinsics: None, or a cameras.Intrinsics (see step_on_views): its values are learned against the frozen field, alone or
+        together with the poses.  One rank only."""
         from .train_utils import select_training_rays_views, select_training_rays_views_bwd
         self._no_pose_grad_across_ranks("localize_on_views")
-        if cameras is None and pose_grads is None:
-            raise RuntimeError("TrainEngine: localize_on_views needs pose_grads=... or cameras=...")
+        if cameras is None and pose_grads is None and intrinsics is None:
+            raise RuntimeError("TrainEngine: localize_on_views needs pose_grads=..., cameras=... or intrinsics=...")
+        if intrinsics is not None:   # (here, not in _step_with_intrinsics: I.values() is launched before cameras.poses(), the step's order)
+            values = self._intrinsics_values(intrinsics)
         poses, pose_grads = self._resolve_cameras(poses, pose_grads, cameras)
+        if intrinsics is not None:
+            return self._step_with_intrinsics(intrinsics, (height, width, focal_length, options), poses, images, True, pose_grads,
+                                              num_random_rays, None, None, cameras, frozen=True, values=values)
         return self._step_on_selection(
             lambda **kw: select_training_rays_views(height, width, focal_length, poses, images, options=options, **kw),
             lambda used, g, g2: select_training_rays_views_bwd(height, width, focal_length, poses, used, g, options, g2, out=pose_grads),
@@ -521,19 +552,47 @@ class TrainEngine:
             self._check_pose_grads("pose_grads", pose_grads, (poses.shape[0], 3, 4))
         return poses, pose_grads
 
+    def _intrinsics_values(self, intrinsics):
+        """The checks of intrinsics=I, then I.values() (one launch): the device vector the selection and its VJP read."""
+        from .cameras import Intrinsics
+        if not isinstance(intrinsics, Intrinsics):
+            raise RuntimeError("TrainEngine: intrinsics must be a cameras.Intrinsics (got %s)" % type(intrinsics).__name__)
+        self._no_pose_grad_across_ranks("intrinsics")
+        if intrinsics.dev != self.dev:
+            raise RuntimeError("TrainEngine: the intrinsics live on %s, the engine on %s" % (intrinsics.dev, self.dev))
+        return intrinsics.values()
+
+    def _step_with_intrinsics(self, intrinsics, scene, poses, images, views, pose_grads, num_random_rays, lr, global_rays,
+                              cameras=None, frozen=False, values=None):
+        """_step_on_selection with the rays generated from intrinsics.values() and ONE VJP call (nerfhip_select_rays_views_intr_bwd)
+        that fills `pose_grads` (when given) and intrinsics.g_intr.  scene: (height, width, focal_length, options)."""
+        from . import train_utils as T
+        height, width, focal_length, options = scene
+        k = self._intrinsics_values(intrinsics) if values is None else values
+        select = T.select_training_rays_views if views else T.select_training_rays
+        bwd = T.select_training_rays_views_bwd if views else T.select_training_rays_bwd
+        # (pose_grads None: the intrinsics alone -- no pose gradient is computed)
+        vjp = lambda used, g, g2: bwd(height, width, focal_length, poses, used, g, options, g2, out=pose_grads, intrinsics=k,  # noqa: E731
+                                      out_intrinsics=intrinsics.g_intr, want_poses=pose_grads is not None)
+        return self._step_on_selection(
+            lambda **kw: select(height, width, focal_length, poses, images, options=options, intrinsics=k, **kw),
+            vjp, pose_grads, num_random_rays, lr, global_rays, cameras, frozen, intrinsics)
+
     def _check_pose_grads(self, name, g, shape):
         if (not isinstance(g, torch.Tensor) or g.device != self.dev or g.dtype != torch.float32 or tuple(g.shape) != shape
                 or not g.is_contiguous()):
             raise RuntimeError("TrainEngine: %s must be a contiguous float32 (%s) tensor on %s"
                                % (name, ", ".join(str(d) for d in shape), self.dev))
 
-    def _step_on_selection(self, select, vjp, pose_grads, num_random_rays, lr, global_rays, cameras=None, frozen=False):
+    def _step_on_selection(self, select, vjp, pose_grads, num_random_rays, lr, global_rays, cameras=None, frozen=False,
+                           intrinsics=None):
         """What step_on_image and step_on_views share: this rank's slice of the step's permutation, `select(num_random_rays=, seed=,
         step=, first=)` -> (rays, target, select indices), then `step`; or, with `pose_grads` (the buffer `vjp` fills),
         forward_backward with the ray gradient, `vjp(select indices, ray gradient, coarse ray gradient)` on the main stream after
         the two streams joined, optimizer_step.  `cameras` (the table whose poses and gradient buffer the callables use): its
         backward() follows the VJP, its step() the nets' Adam.  frozen (localize_on_*): the ray gradient alone, no optimizer_step;
-        keyed by localize_count, which advances."""
+        keyed by localize_count, which advances.  `intrinsics` (the cameras.Intrinsics whose values and gradient buffer the callables
+        use; it turns the ray gradient on even without `pose_grads`): its backward() follows the cameras', its step() theirs."""
         from .parallel import shard_bounds
         if global_rays is None:
             n = int(num_random_rays)
@@ -541,7 +600,7 @@ class TrainEngine:
         else:
             first, hi = shard_bounds(int(global_rays), self.rank, self.world)
             n = hi - first
-        if pose_grads is None:
+        if pose_grads is None and intrinsics is None:
             rays, target, _ = select(num_random_rays=n, seed=self.seed, step=self.step_count, first=first)
             return self.step(rays, target, ray_offset=first, lr=lr, global_rays=global_rays)
         count = self.localize_count if frozen else self.step_count
@@ -555,12 +614,16 @@ class TrainEngine:
             vjp(used, self._ray_grad, self.ray_grad_coarse)
         if cameras is not None:
             cameras.backward()
+        if intrinsics is not None:
+            intrinsics.backward()
         if frozen:
             self.localize_count += 1
         else:
             self.optimizer_step(lr)
         if cameras is not None:
             cameras.step()
+        if intrinsics is not None:
+            intrinsics.step()
         return self.loss
 
     @staticmethod

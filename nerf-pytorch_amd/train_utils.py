@@ -380,19 +380,39 @@ def _pose_table(poses, views):
     return p if ok else p.contiguous()
 
 
-def _select_launch(cfg, poses, images, select_inds, n, views):
-    """nerfhip_select_rays (`poses` one pose, `images` one image) or, with a view axis, nerfhip_select_rays_views."""
+def _intr_vector(intrinsics, dev, what):
+    """The intrinsics (fx, fy, cx, cy) as the kernels read them: four contiguous float32 values on the poses' device."""
+    if (not isinstance(intrinsics, torch.Tensor) or intrinsics.dtype != torch.float32 or intrinsics.numel() != 4
+            or intrinsics.device != dev):
+        raise RuntimeError("%s: intrinsics must be a float32 tensor of 4 (fx, fy, cx, cy) on %s" % (what, dev))
+    return intrinsics.detach().reshape(4).contiguous()
+
+
+def _table_args(poses, views):
+    """(num_views, pointer, view stride, row stride) of a pose table; a single pose is the table of one view."""
+    if views:
+        return poses.shape[0], poses.data_ptr(), poses.stride(0), poses.stride(1)
+    return 1, poses.data_ptr(), 0, poses.stride(-2)
+
+
+def _select_launch(cfg, poses, images, select_inds, n, views, intr=None):
+    """nerfhip_select_rays (`poses` one pose, `images` one image) or, with a view axis, nerfhip_select_rays_views; with `intr` (the
+    device intrinsics) nerfhip_select_rays_views_intr in both cases."""
     dev = poses.device
     rays = torch.empty((n, 11 if cfg.use_viewdirs else 8), dtype=torch.float32, device=dev)
     target = torch.empty((n, cfg.channels), dtype=torch.float32, device=dev) if images is not None else None
     used = torch.empty((n,), dtype=torch.int64, device=dev)
     lib = L.get_lib()
-    table = (poses.shape[0], poses.data_ptr(), poses.stride(0), poses.stride(1)) if views else (poses.data_ptr(), poses.stride(-2))
-    with L.launch_on(poses, images, select_inds, rays) as st:
-        (lib.select_rays_views if views else lib.select_rays)(
-            C.byref(cfg), *table, images.data_ptr() if images is not None else None,
-            select_inds.data_ptr() if select_inds is not None else None, n, rays.data_ptr(),
-            target.data_ptr() if target is not None else None, used.data_ptr(), st)
+    if intr is not None:
+        fn, table = lib.select_rays_views_intr, (intr.data_ptr(),) + _table_args(poses, views)
+    elif views:
+        fn, table = lib.select_rays_views, (poses.shape[0], poses.data_ptr(), poses.stride(0), poses.stride(1))
+    else:
+        fn, table = lib.select_rays, (poses.data_ptr(), poses.stride(-2))
+    with L.launch_on(poses, images, select_inds, rays, intr) as st:
+        fn(C.byref(cfg), *table, images.data_ptr() if images is not None else None,
+           select_inds.data_ptr() if select_inds is not None else None, n, rays.data_ptr(),
+           target.data_ptr() if target is not None else None, used.data_ptr(), st)
     return rays, target, used
 
 
@@ -420,17 +440,42 @@ def _pose_vjp(cfg, poses, used, g_rays, g_rays_2, views, out=None):
     return out
 
 
+def _intr_vjp(cfg, intr, poses, used, g_rays, g_rays_2, views, want_poses=True, want_intr=True, out=None, out_intr=None):
+    """nerfhip_select_rays_views_intr_bwd on the current stream: (d(loss)/d(pose[:3, :4]) as _pose_vjp gives it, d(loss)/d(intr)
+    (4 float32)) of the rays the select call with `intr` made; an output that is not wanted is None."""
+    lib = L.get_lib()
+    n = used.numel()
+    nv = poses.shape[0] if views else 1
+    tb = lib.intr_grad_views_tmp_bytes(n, nv)
+    if tb < 0:
+        raise RuntimeError("select_training_rays_views: %d rays over %d views is outside the kernel's limits" % (n, nv))
+    tmp = torch.empty(tb // 4 + 1, dtype=torch.float32, device=poses.device)
+    if want_poses and out is None:
+        out = torch.empty((nv, 3, 4) if views else (3, 4), dtype=torch.float32, device=poses.device)
+    if want_intr and out_intr is None:
+        out_intr = torch.empty(4, dtype=torch.float32, device=poses.device)
+    gp, gi = (out if want_poses else None), (out_intr if want_intr else None)
+    with L.launch_on(poses, used, g_rays, g_rays_2, tmp, gp, gi, intr) as st:
+        lib.select_rays_views_intr_bwd(C.byref(cfg), intr.data_ptr(), *_table_args(poses, views), used.data_ptr(), n, g_rays.data_ptr(),
+                                       g_rays_2.data_ptr() if g_rays_2 is not None else None, g_rays.stride(0), tmp.data_ptr(), tb,
+                                       gp.data_ptr() if gp is not None else None, gi.data_ptr() if gi is not None else None, st)
+    return gp, gi
+
+
 class _SelectRays(torch.autograd.Function):
     """select_training_rays / select_training_rays_views with the pose VJP (nerfhip_select_rays_bwd / nerfhip_select_rays_views_bwd):
-    the gradient flows from the rays to the [:3, :4] entries of the pose (of every pose of the table); targets and select indices
-    carry none.  The forward issues exactly the launch of the plain call."""
+    the gradient flows from the rays to the [:3, :4] entries of the pose (of every pose of the table) and, with `intrinsics`, to
+    the four intrinsics (nerfhip_select_rays_views_intr_bwd: one call for both); targets and select indices carry none.  The
+    forward issues exactly the launch of the plain call."""
 
     @staticmethod
-    def forward(ctx, poses, cfg, images, select_inds, n, views):
+    def forward(ctx, poses, intrinsics, cfg, images, select_inds, n, views):
         p = _pose_table(poses, views)
-        rays, target, used = _select_launch(cfg, p, images, select_inds, n, views)
-        ctx.keep = (cfg, p, used, views)
+        k = None if intrinsics is None else _intr_vector(intrinsics, p.device, "select_training_rays")
+        rays, target, used = _select_launch(cfg, p, images, select_inds, n, views, k)
+        ctx.keep = (cfg, p, used, views, k)
         ctx.poses_shape = (poses.shape, poses.dtype)
+        ctx.intr_shape = None if intrinsics is None else intrinsics.shape
         ctx.mark_non_differentiable(*[t for t in (target, used) if t is not None])
         ctx.set_materialize_grads(False)
         return rays, target, used
@@ -438,26 +483,35 @@ class _SelectRays(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_rays, _g_target, _g_used):
         if g_rays is None:
-            return (None,) * 6
-        cfg, p, used, views = ctx.keep
-        g34 = _pose_vjp(cfg, p, used, g_rays.contiguous().float(), None, views)
-        shape, dtype = ctx.poses_shape
-        g = torch.zeros(shape, dtype=dtype, device=p.device)
-        g[..., :3, :4] = g34.to(dtype)
-        return g, None, None, None, None, None
+            return (None,) * 7
+        cfg, p, used, views, k = ctx.keep
+        g_rays = g_rays.contiguous().float()
+        gi = None
+        if k is None:
+            g34 = _pose_vjp(cfg, p, used, g_rays, None, views)
+        else:
+            g34, gi = _intr_vjp(cfg, k, p, used, g_rays, None, views, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+            gi = gi.reshape(ctx.intr_shape) if gi is not None else None
+        g = None
+        if g34 is not None:
+            shape, dtype = ctx.poses_shape
+            g = torch.zeros(shape, dtype=dtype, device=p.device)
+            g[..., :3, :4] = g34.to(dtype)
+        return g, gi, None, None, None, None, None
 
 
-def _select(cfg, poses, images, select_inds, n, views):
+def _select(cfg, poses, images, select_inds, n, views, intrinsics=None):
     if images is not None:
         images = images.detach().float().contiguous()
     if select_inds is not None:
         select_inds = torch.as_tensor(select_inds, dtype=torch.int64, device=poses.device).contiguous()
-    if torch.is_grad_enabled() and poses.requires_grad:
-        return _SelectRays.apply(poses, cfg, images, select_inds, n, views)
-    return _select_launch(cfg, _pose_table(poses, views), images, select_inds, n, views)
+    if torch.is_grad_enabled() and (poses.requires_grad or (intrinsics is not None and intrinsics.requires_grad)):
+        return _SelectRays.apply(poses, intrinsics, cfg, images, select_inds, n, views)
+    k = None if intrinsics is None else _intr_vector(intrinsics, poses.device, "select_training_rays")
+    return _select_launch(cfg, _pose_table(poses, views), images, select_inds, n, views, k)
 
 
-def _select_bwd(what, cfg, poses, select_inds, g_rays, g_rays_2, out, views):
+def _select_bwd(what, cfg, poses, select_inds, g_rays, g_rays_2, out, views, intrinsics=None, out_intrinsics=None, want_poses=True):
     """The checks of g_rays / g_rays_2 / out (`what`: the public function, for the messages), then the VJP."""
     for name, g in (("g_rays", g_rays), ("g_rays_2", g_rays_2)):
         if g is not None and (g.dtype != torch.float32 or g.dim() != 2 or g.stride(1) != 1
@@ -470,57 +524,81 @@ def _select_bwd(what, cfg, poses, select_inds, g_rays, g_rays_2, out, views):
     if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous()):
         raise RuntimeError("%s: out must be a contiguous float32 (%s) tensor" % (what, ", ".join(str(d) for d in shape)))
     used = torch.as_tensor(select_inds, dtype=torch.int64, device=poses.device).contiguous()
-    return _pose_vjp(cfg, p, used, g_rays, g_rays_2, views, out)
+    if not want_poses and (intrinsics is None or out is not None):
+        raise RuntimeError("%s: want_poses=False asks for the intrinsics' gradient alone: it needs intrinsics and excludes out" % what)
+    if intrinsics is None:
+        if out_intrinsics is not None:
+            raise RuntimeError("%s: out_intrinsics needs intrinsics" % what)
+        return _pose_vjp(cfg, p, used, g_rays, g_rays_2, views, out)
+    if out_intrinsics is not None and (out_intrinsics.dtype != torch.float32 or tuple(out_intrinsics.shape) != (4,)
+                                       or not out_intrinsics.is_contiguous() or out_intrinsics.device != p.device):
+        raise RuntimeError("%s: out_intrinsics must be a contiguous float32 (4) tensor on %s" % (what, p.device))
+    return _intr_vjp(cfg, _intr_vector(intrinsics, p.device, what), p, used, g_rays, g_rays_2, views, want_poses=want_poses, out=out,
+                     out_intr=out_intrinsics)
 
 
 def select_training_rays(height, width, focal_length, pose, image, num_random_rays, options, select_inds=None, seed=0,
-                         step=0, first=0):
+                         step=0, first=0, intrinsics=None):
     """The image branch of the training loop (train_nerf.py:210-227) fused with run_one_iter_of_nerf's ray packing
     (train_utils.py:143-168), in ONE launch: draws `num_random_rays` distinct pixels on the device (or takes the
     reference's `select_inds`, the flat indices it draws with np.random.choice), generates only those rays from `pose`
     (>= 3x4, device), and gathers their targets from `image` (H, W, 3|4).  Returns (rays (N, 8|11) -- feed them to
     predict_and_render_radiance or TrainEngine.step --, target (N, C), select_inds (N,)).
     With a `pose` that requires grad the rays are differentiable w.r.t. it (pose refinement, as the reference's torch
-    arithmetic is): the backward runs the pose VJP kernel (select_training_rays_bwd)."""
+    arithmetic is): the backward runs the pose VJP kernel (select_training_rays_bwd).
+    intrinsics: None, or a float32 device tensor (fx, fy, cx, cy) in pixels that replaces `focal_length` and the image centre in
+    the pin-hole direction ((col - cx) / fx, -(row - cy) / fy, -1) -- read on the device, so a learned focal is never read back
+    to the host.  `focal_length` still fixes the NDC constants, which do not follow `intrinsics`.  With `intrinsics` requiring
+    grad the rays are differentiable w.r.t. it as well."""
     channels = 3 if image is None else image.shape[-1]
     cfg = _select_cfg(height, width, focal_length, options, channels, seed, step, first)
-    return _select(cfg, pose, image, select_inds, int(num_random_rays), False)
+    return _select(cfg, pose, image, select_inds, int(num_random_rays), False, intrinsics)
 
 
-def select_training_rays_bwd(height, width, focal_length, pose, select_inds, g_rays, options, g_rays_2=None, out=None):
+def select_training_rays_bwd(height, width, focal_length, pose, select_inds, g_rays, options, g_rays_2=None, out=None,
+                             intrinsics=None, out_intrinsics=None, want_poses=True):
     """The pose VJP of select_training_rays without autograd: d(loss)/d(pose[:3, :4]) (3 x 4 float32 device tensor; written
     into `out` when given) of the rays select_training_rays(height, width, focal_length, pose, ..., options) made at
     `select_inds` (its third output), from d(loss)/d(rays) rows `g_rays` (+ `g_rays_2`, added row by row: e.g. the coarse and
-    the fine net's parts that TrainEngine.forward_backward(ray_grad=...) leaves).  Enqueued on the current stream."""
+    the fine net's parts that TrainEngine.forward_backward(ray_grad=...) leaves).  Enqueued on the current stream.
+    With `intrinsics` (those of the forward) the result is the pair (d(loss)/d(pose[:3, :4]), d(loss)/d(intrinsics) (4 float32;
+    written into `out_intrinsics` when given)), from one call; want_poses=False (with `intrinsics` only) leaves the pose gradient
+    out -- it is not computed, and the first entry of the pair is None."""
     cfg = _select_cfg(height, width, focal_length, options, 3, 0, 0, 0)
-    return _select_bwd("select_training_rays_bwd", cfg, pose, select_inds, g_rays, g_rays_2, out, False)
+    return _select_bwd("select_training_rays_bwd", cfg, pose, select_inds, g_rays, g_rays_2, out, False, intrinsics, out_intrinsics,
+                       want_poses)
 
 
 def select_training_rays_views(height, width, focal_length, poses, images, num_random_rays, options, select_inds=None, seed=0,
-                               step=0, first=0):
+                               step=0, first=0, intrinsics=None):
     """select_training_rays over a stack of views, in ONE launch: `num_random_rays` distinct (view, pixel) pairs drawn from all of
     `images` (V, H, W, 3|4; or None) with the rays of each generated from its own row of `poses` (V, >=3, 4; device; a strided
     slice of a larger table is read in place).  Intrinsics and options are shared by the views.  The indices (third output, and
     `select_inds` when given) are global: v * H * W + k, k the reference's flat select index in view v.  Returns (rays, target,
     select_inds) as select_training_rays does; every row equals the row that call makes for (poses[v], images[v], [k]).
     With `poses` requiring grad the rays are differentiable w.r.t. them: the backward runs the per-view pose VJP
-    (select_training_rays_views_bwd), so every view with a ray in the batch gets its gradient from one step."""
+    (select_training_rays_views_bwd), so every view with a ray in the batch gets its gradient from one step.
+    intrinsics: as for select_training_rays (one (fx, fy, cx, cy) for all views)."""
     channels = 3 if images is None else images.shape[-1]
     cfg = _select_cfg(height, width, focal_length, options, channels, seed, step, first)
     if images is not None and (images.dim() != 4 or images.shape[0] != poses.shape[0]
                                or tuple(images.shape[1:3]) != (cfg.height, cfg.width)):
         raise RuntimeError("select_training_rays_views: images must be (V, H, W, C) with V = %d, H = %d, W = %d (got %s)"
                            % (poses.shape[0], cfg.height, cfg.width, tuple(images.shape)))
-    return _select(cfg, poses, images, select_inds, int(num_random_rays), True)
+    return _select(cfg, poses, images, select_inds, int(num_random_rays), True, intrinsics)
 
 
-def select_training_rays_views_bwd(height, width, focal_length, poses, select_inds, g_rays, options, g_rays_2=None, out=None):
+def select_training_rays_views_bwd(height, width, focal_length, poses, select_inds, g_rays, options, g_rays_2=None, out=None,
+                                   intrinsics=None, out_intrinsics=None, want_poses=True):
     """The per-view pose VJP of select_training_rays_views without autograd: d(loss)/d(poses[:, :3, :4]) (V x 3 x 4 float32 device
     tensor; written into `out` when given) from d(loss)/d(rays) rows `g_rays` (+ `g_rays_2`, added row by row) at the global
     `select_inds` of the forward.  Entry v is bit-identical to select_training_rays_bwd on the rays of view v alone (in batch
-    order); a view without a ray gets zeros.  Enqueued on the current stream; no host synchronisation."""
+    order); a view without a ray gets zeros.  Enqueued on the current stream; no host synchronisation.
+    With `intrinsics` the result is the pair (pose gradients, d(loss)/d(intrinsics)), as for select_training_rays_bwd: the
+    intrinsics' gradient is one fixed-order sum over all rays of the batch, whatever their view; want_poses=False as there."""
     cfg = _select_cfg(height, width, focal_length, options, 3, 0, 0, 0)
-    return _select_bwd("select_training_rays_views_bwd", cfg, poses, select_inds, g_rays, g_rays_2, out, True)
+    return _select_bwd("select_training_rays_views_bwd", cfg, poses, select_inds, g_rays, g_rays_2, out, True, intrinsics,
+                       out_intrinsics, want_poses)
 
 
 def select_cached_training_rays(cache_dict, num_random_rays, options, select_inds=None, seed=0, step=0, first=0):
