@@ -72,7 +72,49 @@ def se3_poses(xi, base):
     return _compose(x, _base_table(base, x.shape[0]), torch.empty((x.shape[0], 3, 4), dtype=torch.float32, device=x.device))
 
 
-class CameraTable:
+def check_device_vector(t, shape, dev, what=None):
+    """Whether `t` is a contiguous float32 tensor of shape `shape` on `dev`; with `what` ("Owner: name") anything else raises."""
+    ok = (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == torch.float32 and tuple(t.shape) == tuple(shape)
+          and t.is_contiguous())
+    if not ok and what is not None:
+        raise RuntimeError("%s must be a contiguous float32 (%s) tensor on %s" % (what, ", ".join(str(d) for d in shape), dev))
+    return ok
+
+
+class _AdamVector:
+    """A learned device vector with its Adam state: the parameter `_param` ("xi" / "q"), its gradient buffer "g_" + _param, the two
+    moments, step_count, lr, betas, eps; the state dict holds the parameter, the moments, `base` and the step count."""
+
+    def _init_adam(self, shape, lr, betas, eps):
+        self.lr, self.betas, self.eps = lr, betas, eps
+        self.step_count = 0
+        self._state = (self._param, "exp_avg", "exp_avg_sq", "base")
+        for name in (self._param, "g_" + self._param, "exp_avg", "exp_avg_sq"):
+            setattr(self, name, torch.zeros(shape, dtype=torch.float32, device=self.dev))
+
+    def step(self, lr=None):
+        """One Adam step of the parameter on the gradient the last backward() left: the fused kernel the nets use."""
+        self.step_count += 1
+        b1, b2 = self.betas
+        p, g = getattr(self, self._param), getattr(self, "g_" + self._param)
+        with L.launch_on(p, g) as st:
+            self.lib.adam_step(p.data_ptr(), g.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), p.numel(),
+                               self.lr if lr is None else lr, b1, b2, self.eps, self.step_count, 1.0, st)
+
+    def state_dict(self):
+        return dict({k: getattr(self, k).clone() for k in self._state}, step=self.step_count)
+
+    def load_state_dict(self, state):
+        for k in self._state:
+            t = getattr(self, k)
+            if tuple(state[k].shape) != tuple(t.shape):
+                raise RuntimeError("%s.load_state_dict: %s has shape %s, %s holds %s"
+                                   % (type(self).__name__, k, tuple(state[k].shape), self._holder, tuple(t.shape)))
+            t.copy_(state[k])
+        self.step_count = int(state["step"])
+
+
+class CameraTable(_AdamVector):
     """The cameras of a capture under refinement: one twist per view on top of a fixed base pose, with the Adam state of the
     twists.  Every buffer is allocated here once; poses(), backward() and step() are one launch each on the current stream of the
     table's device, with no host synchronisation.
@@ -80,6 +122,7 @@ class CameraTable:
     base_poses: (V, >=3, 4) device tensor (copied).  active: None (every view is refined) or V booleans: an inactive view's
     gradient is exactly zero, so its twist stays where it is -- at zero its pose stays its base bit for bit (freezing one anchor
     view fixes the gauge of a joint refinement)."""
+    _param, _holder = "xi", "the table"
 
     def __init__(self, base_poses, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, active=None):
         if not isinstance(base_poses, torch.Tensor) or not base_poses.is_cuda:
@@ -90,11 +133,8 @@ class CameraTable:
         self.dev = base_poses.device
         self.base = base_poses.detach()[:, :3, :4].float().contiguous().clone()
         self.num_views = v = self.base.shape[0]
-        self.lr, self.betas, self.eps = lr, betas, eps
-        self.step_count = 0
-        mk = lambda *s: torch.zeros(s, dtype=torch.float32, device=self.dev)  # noqa: E731
-        self.xi, self.exp_avg, self.exp_avg_sq = mk(v, 6), mk(v, 6), mk(v, 6)
-        self.g_xi, self.g_poses, self._poses = mk(v, 6), mk(v, 3, 4), mk(v, 3, 4)
+        self._init_adam((v, 6), lr, betas, eps)
+        self.g_poses, self._poses = (torch.zeros((v, 3, 4), dtype=torch.float32, device=self.dev) for _ in range(2))
         self.active = None
         if active is not None:
             a = torch.as_tensor(active, device=self.dev)
@@ -110,18 +150,8 @@ class CameraTable:
         """d(loss)/d(xi) (the table's own (V, 6) buffer) from d(loss)/d(poses): `g_poses`, a contiguous float32 (V, 3, 4) device
         tensor, or None for the table's own `g_poses` buffer (the one step_on_views(cameras=...) fills)."""
         g = self.g_poses if g_poses is None else g_poses
-        if (not isinstance(g, torch.Tensor) or g.device != self.dev or g.dtype != torch.float32
-                or tuple(g.shape) != (self.num_views, 3, 4) or not g.is_contiguous()):
-            raise RuntimeError("CameraTable: g_poses must be a contiguous float32 (%d, 3, 4) tensor on %s" % (self.num_views, self.dev))
+        check_device_vector(g, (self.num_views, 3, 4), self.dev, "CameraTable: g_poses")
         return _pull_back(self.xi, self.base, g, self.active, self.g_xi)
-
-    def step(self, lr=None):
-        """One Adam step of the twists on the gradient the last backward() left."""
-        self.step_count += 1
-        b1, b2 = self.betas
-        with L.launch_on(self.xi, self.g_xi) as st:
-            self.lib.adam_step(self.xi.data_ptr(), self.g_xi.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                               self.xi.numel(), self.lr if lr is None else lr, b1, b2, self.eps, self.step_count, 1.0, st)
 
     def pose_matrices(self):
         """The current poses as a detached (V, 4, 4) tensor (bottom row 0 0 0 1), e.g. for saving."""
@@ -130,24 +160,11 @@ class CameraTable:
         out[:, 3, 3] = 1.0
         return out
 
-    def state_dict(self):
-        return dict(xi=self.xi.clone(), exp_avg=self.exp_avg.clone(), exp_avg_sq=self.exp_avg_sq.clone(), step=self.step_count,
-                    base=self.base.clone())
-
-    def load_state_dict(self, state):
-        for k in ("xi", "exp_avg", "exp_avg_sq", "base"):
-            t = getattr(self, k)
-            if tuple(state[k].shape) != tuple(t.shape):
-                raise RuntimeError("CameraTable.load_state_dict: %s has shape %s, the table holds %s"
-                                   % (k, tuple(state[k].shape), tuple(t.shape)))
-            t.copy_(state[k])
-        self.step_count = int(state["step"])
-
 
 _LEARN = {"focal": (True, (1, 0, 0, 0)), "focal_xy": (False, (1, 1, 0, 0)), "all": (False, (1, 1, 1, 1)), (): (False, (0, 0, 0, 0))}
 
 
-class Intrinsics:
+class Intrinsics(_AdamVector):
     """The shared intrinsics (fx, fy, cx, cy) of a capture under refinement, resident on the device, with the Adam state of their
     parametrisation q: fx = fx0 exp(q0), fy = fy0 exp(q1) (exp(q0) when the focals are tied), cx = cx0 + q2, cy = cy0 + q3 -- the
     log-focal keeps the focal positive and makes Adam's step a relative one.  Every buffer is allocated here once; values(),
@@ -159,6 +176,7 @@ class Intrinsics:
     the principal point fixed), "focal_xy" (fx and fy apart), "all", or () (nothing moves).  An entry that is not learned gets an
     exact zero gradient, so its q stays where it is.  The NDC constants of a forward-facing scene are fixed by the caller's
     `focal_length` and do not follow these values."""
+    _param, _holder = "q", "the object"
 
     def __init__(self, height, width, focal, learn="focal", lr=1e-3, betas=(0.9, 0.999), eps=1e-8, device=None):
         key = tuple(learn) if isinstance(learn, (list, tuple)) else learn
@@ -178,12 +196,10 @@ class Intrinsics:
         self.height, self.width = int(height), int(width)
         self.learn = key
         self.tie_focal, mask = _LEARN[key]
-        self.lr, self.betas, self.eps = lr, betas, eps
-        self.step_count = 0
-        mk = lambda: torch.zeros(4, dtype=torch.float32, device=self.dev)  # noqa: E731
+        self._init_adam((4,), lr, betas, eps)
         self.base = torch.tensor(four, dtype=torch.float32).to(self.dev)
         self.mask = torch.tensor(mask, dtype=torch.uint8).to(self.dev)
-        self.q, self.exp_avg, self.exp_avg_sq, self.g_q, self.g_intr = mk(), mk(), mk(), mk(), mk()
+        self.g_intr = torch.zeros(4, dtype=torch.float32, device=self.dev)
         self._values = self.base.clone()
 
     def values(self):
@@ -197,34 +213,17 @@ class Intrinsics:
         """d(loss)/d(q) (the object's own buffer) from d(loss)/d(fx, fy, cx, cy): `g_intr`, a contiguous float32 device tensor of
         4, or None for the object's own `g_intr` buffer (the one a step with intrinsics=... fills)."""
         g = self.g_intr if g_intr is None else g_intr
-        if (not isinstance(g, torch.Tensor) or g.device != self.dev or g.dtype != torch.float32 or tuple(g.shape) != (4,)
-                or not g.is_contiguous()):
-            raise RuntimeError("Intrinsics: g_intr must be a contiguous float32 (4) tensor on %s" % self.dev)
+        check_device_vector(g, (4,), self.dev, "Intrinsics: g_intr")
         with L.launch_on(self.q, self.base, g, self.mask, self.g_q) as st:
             self.lib.intrinsics_bwd(self.q.data_ptr(), self.base.data_ptr(), int(self.tie_focal), g.data_ptr(), self.mask.data_ptr(),
                                     self.g_q.data_ptr(), st)
         return self.g_q
 
-    def step(self, lr=None):
-        """One Adam step of q on the gradient the last backward() left."""
-        self.step_count += 1
-        b1, b2 = self.betas
-        with L.launch_on(self.q, self.g_q) as st:
-            self.lib.adam_step(self.q.data_ptr(), self.g_q.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), 4,
-                               self.lr if lr is None else lr, b1, b2, self.eps, self.step_count, 1.0, st)
-
     def state_dict(self):
-        return dict(q=self.q.clone(), exp_avg=self.exp_avg.clone(), exp_avg_sq=self.exp_avg_sq.clone(), step=self.step_count,
-                    base=self.base.clone(), learn=self.learn)
+        return dict(super().state_dict(), learn=self.learn)
 
     def load_state_dict(self, state):
         if "learn" in state and (tuple(state["learn"]) if isinstance(state["learn"], (list, tuple)) else state["learn"]) != self.learn:
             raise RuntimeError("Intrinsics.load_state_dict: the state was saved with learn=%r, this object has learn=%r"
                                % (state["learn"], self.learn))
-        for k in ("q", "exp_avg", "exp_avg_sq", "base"):
-            t = getattr(self, k)
-            if tuple(state[k].shape) != tuple(t.shape):
-                raise RuntimeError("Intrinsics.load_state_dict: %s has shape %s, the object holds %s"
-                                   % (k, tuple(state[k].shape), tuple(t.shape)))
-            t.copy_(state[k])
-        self.step_count = int(state["step"])
+        super().load_state_dict(state)

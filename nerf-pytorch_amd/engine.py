@@ -24,8 +24,10 @@ import torch
 
 from . import _lib as L
 from . import backward_mode as BM
+from . import train_utils as TU
+from .cameras import Intrinsics, check_device_vector
 from .nerf_helpers import linspace01
-from .parallel import allreduce_gradients
+from .parallel import allreduce_gradients, shard_bounds
 
 
 class TrainEngine:
@@ -77,7 +79,10 @@ class TrainEngine:
         self._ws = None
         self._ws_n = -1
         self._bufs = None
-        self.ray_grad_coarse = None   # the coarse net's part of d(loss)/d(rays) of a step with ray_grad (forward_backward)
+        # buffers of a step with a ray gradient, sized in _ray_grad_bufs: the coarse net's part of d(loss)/d(rays) (forward_backward),
+        # one backward tmp per net with its size in bytes, the step routine's own ray gradient (the fine net's part)
+        self.ray_grad_coarse = self._ray_grad = None
+        self._rg_tmp, self._rg_n, self._ray_grad_n = (None, None, 0), -1, -1
         # backward mode of the step: None -- whatever each model's set_backward_compaction says (default: dense); "dense" / "compact" /
         # "recompute" -- set on both models; "auto" -- chosen per net and per step from the zero-cotangent fraction the previous
         # compacted steps reported (read back asynchronously: no host synchronisation), see _choose_backward_modes
@@ -175,17 +180,19 @@ class TrainEngine:
             self._ev = (torch.cuda.Event(), torch.cuda.Event())
         return main, self._side
 
-    def _ray_grad_bufs(self, n):
-        """Engine-owned buffers of a step with a ray gradient: the coarse net's part of d(loss)/d(rays) and one tmp per net (the two
-        nets' backward chains may run at the same time on two streams)."""
-        if getattr(self, "_rg_n", -1) != n:
+    def _ray_grad_bufs(self, n, own=False):
+        """Engine-owned buffers of a step of `n` rays with a ray gradient: the coarse net's part of d(loss)/d(rays) and one tmp per net
+        (the two nets' backward chains may run at the same time on two streams); with `own`, the step routine's ray gradient as well."""
+        mk = lambda *s: torch.empty(s, dtype=torch.float32, device=self.dev)  # noqa: E731
+        if own and self._ray_grad_n != n:
+            self._ray_grad, self._ray_grad_n = mk(n, self.stride), n
+        if self._rg_n != n:
             plan_f = self.mf._plan if self.mf is not None else None
             # (one tmp serves both forms of the step: the trainable one's and the frozen one's, whichever is larger)
             tb = max(self.lib.render_bwd_rays_tmp_bytes(self.mc._plan, plan_f, C.byref(self.cfg), n),
                      self.lib.render_grad_rays_tmp_bytes(self.mc._plan, plan_f, C.byref(self.cfg), n))
             if tb < 0:
                 raise L.NerfHipError(self.lib.last_error().decode())
-            mk = lambda *s: torch.empty(s, dtype=torch.float32, device=self.dev)  # noqa: E731
             self.ray_grad_coarse = mk(n, self.stride) if self.mf is not None else None
             self._rg_tmp = (mk(tb // 4 + 4), mk(tb // 4 + 4) if self.mf is not None else None, tb)
             self._rg_n = n
@@ -221,8 +228,7 @@ class TrainEngine:
             raise RuntimeError("TrainEngine: forward_backward(frozen=True) computes the ray gradient alone: pass ray_grad=...")
         if ray_grad is not None:
             self._no_pose_grad_across_ranks("ray_grad")
-            if (not isinstance(ray_grad, torch.Tensor) or ray_grad.device != self.dev or ray_grad.dtype != torch.float32
-                    or tuple(ray_grad.shape) != tuple(rays.shape) or not ray_grad.is_contiguous()):
+            if not check_device_vector(ray_grad, rays.shape, self.dev):
                 raise RuntimeError("TrainEngine: ray_grad must be a contiguous float32 tensor of the rays' shape %s on %s"
                                    % (tuple(rays.shape), self.dev))
         lib, n = self.lib, rays.shape[0]
@@ -259,7 +265,7 @@ class TrainEngine:
         bwd_head = (self.mc._plan, plan_f, C.byref(self.cfg), rays.data_ptr(), n, self.packed_c.data_ptr(), pf, rr, seed,
                     ray_offset)
         bwd_tail = (self._ws.data_ptr(), self._wsb, gc.data_ptr(), gf.data_ptr() if gf is not None else None)
-        ws_tail = bwd_tail[:2]
+        tmp_c = tmp_f = g_rays_c = None
         if ray_grad is not None:
             g_rays_c, (tmp_c, tmp_f, tmpb) = self._ray_grad_bufs(n)
             if g_rays_c is None:
@@ -267,53 +273,45 @@ class TrainEngine:
             # (the flat vectors as the nets run: theta_eff under an encoding window, as the last repack left it)
             pc_flat = self.mc._theta_eff(refresh=False).data_ptr()
             pf_flat = self.mf._theta_eff(refresh=False).data_ptr() if nf > 0 else None
+
+        def net_pass(part, rgb, g_rgb, cot, loss, grad, model, tmp, g_rays, stream):
+            """One net's loss, then its backward in the step's form, then its window gradients (behind its backward, ahead of its
+            all-reduce), on `stream`."""
+            lib.mse_loss_fwd_bwd(rgb.data_ptr(), None, target.data_ptr(), tstride, n, gscale, g_rgb.data_ptr(), None, loss.data_ptr(), stream)
+            if ray_grad is None:
+                lib.render_bwd_parts(*bwd_head, C.byref(cot), *bwd_tail, part, stream)
+            else:
+                rays_tail = (part, pc_flat, pf_flat, tmp.data_ptr(), tmpb, g_rays.data_ptr(), stream)
+                if frozen:   # (no parameter gradient: the workspace alone, no gradient slices)
+                    lib.render_grad_rays(*bwd_head, C.byref(cot), *bwd_tail[:2], *rays_tail)
+                else:
+                    lib.render_bwd_rays(*bwd_head, C.byref(cot), *bwd_tail, *rays_tail)
+            if not frozen:
+                model._window_grads(grad, model._window_w, stream)
+
+        coarse = (L.PART_COARSE, b["rgb_c"], b["g_c"], cot_c, self._loss_c, gc, self.mc, tmp_c, g_rays_c)
+        fine = (L.PART_FINE, b["rgb_f"], b["g_f"], cot_f, self._loss_f, gf, self.mf, tmp_f, ray_grad)
         self._pending = []
         with torch.cuda.device(self.dev):
             main, side = self._streams()
             st = main.cuda_stream
             two = self.overlap and nf > 0
             lib.render_fwd_parts(*fwd_args, L.PART_COARSE, st)
-
-            def coarse_backward(stream_handle):
-                lib.mse_loss_fwd_bwd(b["rgb_c"].data_ptr(), None, target.data_ptr(), tstride, n, gscale, b["g_c"].data_ptr(),
-                                     None, self._loss_c.data_ptr(), stream_handle)
-                if frozen:
-                    lib.render_grad_rays(*bwd_head, C.byref(cot_c), *ws_tail, L.PART_COARSE, pc_flat, pf_flat, tmp_c.data_ptr(), tmpb,
-                                         g_rays_c.data_ptr(), stream_handle)
-                    return
-                if ray_grad is None:
-                    lib.render_bwd_parts(*bwd_head, C.byref(cot_c), *bwd_tail, L.PART_COARSE, stream_handle)
-                else:
-                    lib.render_bwd_rays(*bwd_head, C.byref(cot_c), *bwd_tail, L.PART_COARSE, pc_flat, pf_flat, tmp_c.data_ptr(),
-                                        tmpb, g_rays_c.data_ptr(), stream_handle)
-                self.mc._window_grads(gc, self.mc._window_w, stream_handle)   # (behind its backward, ahead of its all-reduce)
-
-            if two:
+            if two:   # the coarse net's pass next to the fine forward and backward
                 e1, e2 = self._ev
                 e1.record(main)
                 side.wait_event(e1)
-                coarse_backward(side.cuda_stream)
+                net_pass(*coarse, side.cuda_stream)
                 e2.record(side)
             if nf > 0:
                 lib.render_fwd_parts(*fwd_args, L.PART_FINE, st)
-                lib.mse_loss_fwd_bwd(b["rgb_f"].data_ptr(), None, target.data_ptr(), tstride, n, gscale, b["g_f"].data_ptr(),
-                                     None, self._loss_f.data_ptr(), st)
-                if frozen:
-                    lib.render_grad_rays(*bwd_head, C.byref(cot_f), *ws_tail, L.PART_FINE, pc_flat, pf_flat, tmp_f.data_ptr(), tmpb,
-                                         ray_grad.data_ptr(), st)
-                elif ray_grad is None:
-                    lib.render_bwd_parts(*bwd_head, C.byref(cot_f), *bwd_tail, L.PART_FINE, st)
-                else:
-                    lib.render_bwd_rays(*bwd_head, C.byref(cot_f), *bwd_tail, L.PART_FINE, pc_flat, pf_flat, tmp_f.data_ptr(), tmpb,
-                                        ray_grad.data_ptr(), st)
-                if not frozen:
-                    self.mf._window_grads(gf, self.mf._window_w, st)
+                net_pass(*fine, st)
                 if self._reduce and not frozen:  # in flight while the coarse backward computes
                     self._pending.append(allreduce_gradients(gf, self.pg, async_op=True, single_rank=True))
             if two:
                 main.wait_event(e2)
             else:
-                coarse_backward(st)
+                net_pass(*coarse, st)
             if self._reduce and not frozen:
                 self._pending.append(allreduce_gradients(gc, self.pg, async_op=True, single_rank=True))
             if nf > 0:
@@ -445,17 +443,11 @@ class TrainEngine:
         torch.autograd.backward(pose_expr[:3, :4], pose_grad).  One rank only.
         intrinsics: None, or a cameras.Intrinsics on the engine's device: the rays are generated from its (fx, fy, cx, cy), read on
         the device, and the step learns them -- see step_on_views.  `focal_length` must still be passed: it fixes the NDC constants."""
-        from .train_utils import select_training_rays, select_training_rays_bwd
         if pose_grad is not None:
             self._no_pose_grad_across_ranks("pose_grad")
             self._check_pose_grads("pose_grad", pose_grad, (3, 4))
-        if intrinsics is not None:
-            return self._step_with_intrinsics(intrinsics, (height, width, focal_length, options), pose, image, False, pose_grad,
-                                              num_random_rays, lr, global_rays)
-        return self._step_on_selection(
-            lambda **kw: select_training_rays(height, width, focal_length, pose, image, options=options, **kw),
-            lambda used, g, g2: select_training_rays_bwd(height, width, focal_length, pose, used, g, options, g2, out=pose_grad),
-            pose_grad, num_random_rays, lr, global_rays)
+        return self._step_on_selection((height, width, focal_length, options), pose, image, False, num_random_rays, lr, global_rays,
+                                       pose_grad, None, intrinsics, False)
 
     def step_on_views(self, images, poses, height, width, focal_length, options, num_random_rays, lr=None, global_rays=None,
                       pose_grads=None, cameras=None, intrinsics=None):
@@ -477,19 +469,8 @@ class TrainEngine:
         -> the nets' Adam -> cameras.step() -> intrinsics.step().  Allowed with neither pose_grads nor cameras (it turns the ray
         gradient on).  `focal_length` must still be passed: it fixes the NDC constants, which do not follow the learned values.  One
         rank only."""
-        from .train_utils import select_training_rays_views, select_training_rays_views_bwd
-        # cameras.poses() -> selection -> forward_backward with the ray gradient -> the per-view pose VJP into cameras.g_poses ->
-        # cameras.backward() -> the nets' optimizer_step -> cameras.step()
-        if intrinsics is not None:   # (here, not in _step_with_intrinsics: I.values() is launched before cameras.poses(), the step's order)
-            values = self._intrinsics_values(intrinsics)
-        poses, pose_grads = self._resolve_cameras(poses, pose_grads, cameras)
-        if intrinsics is not None:
-            return self._step_with_intrinsics(intrinsics, (height, width, focal_length, options), poses, images, True, pose_grads,
-                                              num_random_rays, lr, global_rays, cameras, values=values)
-        return self._step_on_selection(
-            lambda **kw: select_training_rays_views(height, width, focal_length, poses, images, options=options, **kw),
-            lambda used, g, g2: select_training_rays_views_bwd(height, width, focal_length, poses, used, g, options, g2, out=pose_grads),
-            pose_grads, num_random_rays, lr, global_rays, cameras)
+        return self._step_on_selection((height, width, focal_length, options), poses, images, True, num_random_rays, lr, global_rays,
+                                       pose_grads, cameras, intrinsics, False)
 
     def localize_on_image(self, image, pose, height, width, focal_length, options, num_random_rays, pose_grad=None, intrinsics=None):
         """step_on_image(pose_grad=...) for FROZEN nets (camera localisation against a trained field): the same selection, forward and
@@ -499,19 +480,13 @@ class TrainEngine:
         pose_grad: a contiguous float32 (3, 4) tensor on the engine's device, overwritten with d(loss)/d(pose[:3, :4]).  One rank only.
         intrinsics: None, or a cameras.Intrinsics (see step_on_views): its values are learned against the frozen field; then
         pose_grad may be None."""
-        from .train_utils import select_training_rays, select_training_rays_bwd
         self._no_pose_grad_across_ranks("localize_on_image")
         if pose_grad is None and intrinsics is None:
             raise RuntimeError("TrainEngine: localize_on_image needs pose_grad=... or intrinsics=...")
         if pose_grad is not None:
             self._check_pose_grads("pose_grad", pose_grad, (3, 4))
-        if intrinsics is not None:
-            return self._step_with_intrinsics(intrinsics, (height, width, focal_length, options), pose, image, False, pose_grad,
-                                              num_random_rays, None, None, frozen=True)
-        return self._step_on_selection(
-            lambda **kw: select_training_rays(height, width, focal_length, pose, image, options=options, **kw),
-            lambda used, g, g2: select_training_rays_bwd(height, width, focal_length, pose, used, g, options, g2, out=pose_grad),
-            pose_grad, num_random_rays, None, None, frozen=True)
+        return self._step_on_selection((height, width, focal_length, options), pose, image, False, num_random_rays, None, None,
+                                       pose_grad, None, intrinsics, True)
 
     def localize_on_views(self, images, poses, height, width, focal_length, options, num_random_rays, pose_grads=None, cameras=None,
                           intrinsics=None):
@@ -520,20 +495,11 @@ class TrainEngine:
         the gradients in its own buffer, pulls them back to its twists (T.backward()) and steps them (T.step()) -- the nets stay put.
         intrinsics: None, or a cameras.Intrinsics (see step_on_views): its values are learned against the frozen field, alone or
         together with the poses.  One rank only."""
-        from .train_utils import select_training_rays_views, select_training_rays_views_bwd
         self._no_pose_grad_across_ranks("localize_on_views")
         if cameras is None and pose_grads is None and intrinsics is None:
             raise RuntimeError("TrainEngine: localize_on_views needs pose_grads=..., cameras=... or intrinsics=...")
-        if intrinsics is not None:   # (here, not in _step_with_intrinsics: I.values() is launched before cameras.poses(), the step's order)
-            values = self._intrinsics_values(intrinsics)
-        poses, pose_grads = self._resolve_cameras(poses, pose_grads, cameras)
-        if intrinsics is not None:
-            return self._step_with_intrinsics(intrinsics, (height, width, focal_length, options), poses, images, True, pose_grads,
-                                              num_random_rays, None, None, cameras, frozen=True, values=values)
-        return self._step_on_selection(
-            lambda **kw: select_training_rays_views(height, width, focal_length, poses, images, options=options, **kw),
-            lambda used, g, g2: select_training_rays_views_bwd(height, width, focal_length, poses, used, g, options, g2, out=pose_grads),
-            pose_grads, num_random_rays, None, None, cameras, frozen=True)
+        return self._step_on_selection((height, width, focal_length, options), poses, images, True, num_random_rays, None, None,
+                                       pose_grads, cameras, intrinsics, True)
 
     def _resolve_cameras(self, poses, pose_grads, cameras):
         """(poses, pose_grads) of a step over views: the caller's, checked; or, with cameras=T, the table's composed poses and its own
@@ -552,66 +518,48 @@ class TrainEngine:
             self._check_pose_grads("pose_grads", pose_grads, (poses.shape[0], 3, 4))
         return poses, pose_grads
 
-    def _intrinsics_values(self, intrinsics):
-        """The checks of intrinsics=I, then I.values() (one launch): the device vector the selection and its VJP read."""
-        from .cameras import Intrinsics
-        if not isinstance(intrinsics, Intrinsics):
-            raise RuntimeError("TrainEngine: intrinsics must be a cameras.Intrinsics (got %s)" % type(intrinsics).__name__)
-        self._no_pose_grad_across_ranks("intrinsics")
-        if intrinsics.dev != self.dev:
-            raise RuntimeError("TrainEngine: the intrinsics live on %s, the engine on %s" % (intrinsics.dev, self.dev))
-        return intrinsics.values()
-
-    def _step_with_intrinsics(self, intrinsics, scene, poses, images, views, pose_grads, num_random_rays, lr, global_rays,
-                              cameras=None, frozen=False, values=None):
-        """_step_on_selection with the rays generated from intrinsics.values() and ONE VJP call (nerfhip_select_rays_views_intr_bwd)
-        that fills `pose_grads` (when given) and intrinsics.g_intr.  scene: (height, width, focal_length, options)."""
-        from . import train_utils as T
-        height, width, focal_length, options = scene
-        k = self._intrinsics_values(intrinsics) if values is None else values
-        select = T.select_training_rays_views if views else T.select_training_rays
-        bwd = T.select_training_rays_views_bwd if views else T.select_training_rays_bwd
-        # (pose_grads None: the intrinsics alone -- no pose gradient is computed)
-        vjp = lambda used, g, g2: bwd(height, width, focal_length, poses, used, g, options, g2, out=pose_grads, intrinsics=k,  # noqa: E731
-                                      out_intrinsics=intrinsics.g_intr, want_poses=pose_grads is not None)
-        return self._step_on_selection(
-            lambda **kw: select(height, width, focal_length, poses, images, options=options, intrinsics=k, **kw),
-            vjp, pose_grads, num_random_rays, lr, global_rays, cameras, frozen, intrinsics)
-
     def _check_pose_grads(self, name, g, shape):
-        if (not isinstance(g, torch.Tensor) or g.device != self.dev or g.dtype != torch.float32 or tuple(g.shape) != shape
-                or not g.is_contiguous()):
-            raise RuntimeError("TrainEngine: %s must be a contiguous float32 (%s) tensor on %s"
-                               % (name, ", ".join(str(d) for d in shape), self.dev))
+        check_device_vector(g, shape, self.dev, "TrainEngine: " + name)
 
-    def _step_on_selection(self, select, vjp, pose_grads, num_random_rays, lr, global_rays, cameras=None, frozen=False,
-                           intrinsics=None):
-        """What step_on_image and step_on_views share: this rank's slice of the step's permutation, `select(num_random_rays=, seed=,
-        step=, first=)` -> (rays, target, select indices), then `step`; or, with `pose_grads` (the buffer `vjp` fills),
-        forward_backward with the ray gradient, `vjp(select indices, ray gradient, coarse ray gradient)` on the main stream after
-        the two streams joined, optimizer_step.  `cameras` (the table whose poses and gradient buffer the callables use): its
-        backward() follows the VJP, its step() the nets' Adam.  frozen (localize_on_*): the ray gradient alone, no optimizer_step;
-        keyed by localize_count, which advances.  `intrinsics` (the cameras.Intrinsics whose values and gradient buffer the callables
-        use; it turns the ray gradient on even without `pose_grads`): its backward() follows the cameras', its step() theirs."""
-        from .parallel import shard_bounds
+    def _step_on_selection(self, scene, poses, images, views, num_random_rays, lr, global_rays, pose_grads, cameras, intrinsics, frozen):
+        """The step of step_on_image / step_on_views / localize_on_* behind their own argument checks.  scene: (height, width,
+        focal_length, options); views: whether `poses` / `images` carry a view axis.  In launch order: the checks of intrinsics=I, then
+        I.values(); cameras=T checked, T.poses() (_resolve_cameras); this rank's slice of the step's permutation; the selection; `step`
+        -- or, with any of pose_grads / cameras / intrinsics, forward_backward with the ray gradient, then on the main stream after
+        the two streams joined ONE VJP call that fills `pose_grads` (when asked) and I.g_intr, T.backward(), I.backward(),
+        optimizer_step, T.step(), I.step().  frozen (localize_on_*): the ray gradient alone and no optimizer_step; the selection and
+        the draws are keyed by localize_count, which advances.  Without intrinsics no intrinsics keyword is passed on: the step reaches
+        the entry points of the selection without them."""
+        height, width, focal_length, options = scene
+        kw, vjp_kw = {}, {}
+        if intrinsics is not None:
+            if not isinstance(intrinsics, Intrinsics):
+                raise RuntimeError("TrainEngine: intrinsics must be a cameras.Intrinsics (got %s)" % type(intrinsics).__name__)
+            self._no_pose_grad_across_ranks("intrinsics")
+            if intrinsics.dev != self.dev:
+                raise RuntimeError("TrainEngine: the intrinsics live on %s, the engine on %s" % (intrinsics.dev, self.dev))
+            kw = dict(intrinsics=intrinsics.values())
+        if views:
+            poses, pose_grads = self._resolve_cameras(poses, pose_grads, cameras)
+        if intrinsics is not None:   # (pose_grads None: the intrinsics alone -- no pose gradient is computed)
+            vjp_kw = dict(kw, out_intrinsics=intrinsics.g_intr, want_poses=pose_grads is not None)
         if global_rays is None:
             n = int(num_random_rays)
             first = self.rank * n
         else:
             first, hi = shard_bounds(int(global_rays), self.rank, self.world)
             n = hi - first
-        if pose_grads is None and intrinsics is None:
-            rays, target, _ = select(num_random_rays=n, seed=self.seed, step=self.step_count, first=first)
-            return self.step(rays, target, ray_offset=first, lr=lr, global_rays=global_rays)
+        select = TU.select_training_rays_views if views else TU.select_training_rays
         count = self.localize_count if frozen else self.step_count
         with torch.no_grad():
-            rays, target, used = select(num_random_rays=n, seed=self.seed, step=count, first=first)
-        if getattr(self, "_ray_grad_n", -1) != n:
-            self._ray_grad = torch.empty((n, self.stride), dtype=torch.float32, device=self.dev)
-            self._ray_grad_n = n
+            rays, target, used = select(height, width, focal_length, poses, images, n, options, seed=self.seed, step=count, first=first, **kw)
+        if pose_grads is None and intrinsics is None:
+            return self.step(rays, target, ray_offset=first, lr=lr, global_rays=global_rays)
+        self._ray_grad_bufs(n, own=True)
         self.forward_backward(rays, target, first, global_rays, None, self._ray_grad, frozen, count)
+        vjp = TU.select_training_rays_views_bwd if views else TU.select_training_rays_bwd
         with torch.cuda.device(self.dev):
-            vjp(used, self._ray_grad, self.ray_grad_coarse)
+            vjp(height, width, focal_length, poses, used, self._ray_grad, options, self.ray_grad_coarse, out=pose_grads, **vjp_kw)
         if cameras is not None:
             cameras.backward()
         if intrinsics is not None:

@@ -172,18 +172,24 @@ def _ray_bundle_launch(height, width, focal, c2w, pix, shape, intr=None):
     return ro, rd
 
 
+def _intr_vector(intrinsics, dev, what=None):
+    """The intrinsics (fx, fy, cx, cy) as the kernels read them: four contiguous float32 values on `dev`, the poses' device (`what`:
+    the calling function, leading the message)."""
+    if (not isinstance(intrinsics, torch.Tensor) or intrinsics.dtype != torch.float32 or intrinsics.numel() != 4
+            or intrinsics.device != dev):
+        raise RuntimeError("%sintrinsics must be a float32 tensor of 4 (fx, fy, cx, cy) on %s" % (what + ": " if what else "", dev))
+    return intrinsics.detach().reshape(4).contiguous()
+
+
 def _bundle_intrinsics(intrinsics, pose, c2w):
-    """The `intrinsics` argument of the bundle forms (forward only): four float32 values on the pose's device."""
+    """The `intrinsics` argument of the bundle forms (forward only): _intr_vector on the pose's device."""
     if intrinsics is None:
         return None
     if _wants_pose_grad(pose):
         raise RuntimeError("get_ray_bundle(intrinsics=...) is forward only: the bundle form has no VJP under device intrinsics, so a "
                            "pose that requires grad cannot be combined with it (select_training_rays(intrinsics=...) carries "
                            "both gradients)")
-    if (not isinstance(intrinsics, torch.Tensor) or intrinsics.dtype != torch.float32 or intrinsics.numel() != 4
-            or intrinsics.device != c2w.device):
-        raise RuntimeError("intrinsics must be a float32 tensor of 4 (fx, fy, cx, cy) on %s" % c2w.device)
-    return intrinsics.detach().reshape(4).contiguous()
+    return _intr_vector(intrinsics, c2w.device)
 
 
 def _wants_pose_grad(pose):

@@ -20,7 +20,7 @@ import torch
 from . import _lib as L
 from . import backward_mode as BM
 from .models import FlexibleNeRFModel
-from .nerf_helpers import EmbeddingFunction, get_minibatches, linspace01, ndc_rays, sample_pdf_2 as sample_pdf
+from .nerf_helpers import EmbeddingFunction, _intr_vector, get_minibatches, linspace01, ndc_rays, sample_pdf_2 as sample_pdf
 from .volume_rendering_utils import volume_render_radiance_field
 
 
@@ -380,19 +380,23 @@ def _pose_table(poses, views):
     return p if ok else p.contiguous()
 
 
-def _intr_vector(intrinsics, dev, what):
-    """The intrinsics (fx, fy, cx, cy) as the kernels read them: four contiguous float32 values on the poses' device."""
-    if (not isinstance(intrinsics, torch.Tensor) or intrinsics.dtype != torch.float32 or intrinsics.numel() != 4
-            or intrinsics.device != dev):
-        raise RuntimeError("%s: intrinsics must be a float32 tensor of 4 (fx, fy, cx, cy) on %s" % (what, dev))
-    return intrinsics.detach().reshape(4).contiguous()
+# (intrinsics?, a view axis?) -> the selection's entry point, its VJP's, the VJP's tmp-size function.  (The single view without
+# intrinsics keeps its own VJP: two launches where the views form at V = 1 issues three.)
+_SELECT_ENTRY = {(False, False): ("select_rays", "select_rays_bwd", "pose_grad_tmp_bytes"),
+                 (False, True): ("select_rays_views", "select_rays_views_bwd", "pose_grad_views_tmp_bytes"),
+                 (True, False): ("select_rays_views_intr", "select_rays_views_intr_bwd", "intr_grad_views_tmp_bytes"),
+                 (True, True): ("select_rays_views_intr", "select_rays_views_intr_bwd", "intr_grad_views_tmp_bytes")}
 
 
-def _table_args(poses, views):
-    """(num_views, pointer, view stride, row stride) of a pose table; a single pose is the table of one view."""
+def _table_args(poses, views, intr=None):
+    """The pose arguments of the entry points of _SELECT_ENTRY: (pointer, row stride) of the single pose, or -- with a view axis or
+    `intr`, whose pointer then leads -- the table (num_views, pointer, view stride, row stride); a single pose is the table of one view."""
+    if intr is None and not views:
+        return poses.data_ptr(), poses.stride(-2)
+    head = () if intr is None else (intr.data_ptr(),)
     if views:
-        return poses.shape[0], poses.data_ptr(), poses.stride(0), poses.stride(1)
-    return 1, poses.data_ptr(), 0, poses.stride(-2)
+        return head + (poses.shape[0], poses.data_ptr(), poses.stride(0), poses.stride(1))
+    return head + (1, poses.data_ptr(), 0, poses.stride(-2))
 
 
 def _select_launch(cfg, poses, images, select_inds, n, views, intr=None):
@@ -402,63 +406,36 @@ def _select_launch(cfg, poses, images, select_inds, n, views, intr=None):
     rays = torch.empty((n, 11 if cfg.use_viewdirs else 8), dtype=torch.float32, device=dev)
     target = torch.empty((n, cfg.channels), dtype=torch.float32, device=dev) if images is not None else None
     used = torch.empty((n,), dtype=torch.int64, device=dev)
-    lib = L.get_lib()
-    if intr is not None:
-        fn, table = lib.select_rays_views_intr, (intr.data_ptr(),) + _table_args(poses, views)
-    elif views:
-        fn, table = lib.select_rays_views, (poses.shape[0], poses.data_ptr(), poses.stride(0), poses.stride(1))
-    else:
-        fn, table = lib.select_rays, (poses.data_ptr(), poses.stride(-2))
+    fn = getattr(L.get_lib(), _SELECT_ENTRY[intr is not None, bool(views)][0])
     with L.launch_on(poses, images, select_inds, rays, intr) as st:
-        fn(C.byref(cfg), *table, images.data_ptr() if images is not None else None,
+        fn(C.byref(cfg), *_table_args(poses, views, intr), images.data_ptr() if images is not None else None,
            select_inds.data_ptr() if select_inds is not None else None, n, rays.data_ptr(),
            target.data_ptr() if target is not None else None, used.data_ptr(), st)
     return rays, target, used
 
 
-def _pose_vjp(cfg, poses, used, g_rays, g_rays_2, views, out=None):
-    """nerfhip_select_rays_bwd / nerfhip_select_rays_views_bwd on the current stream: d(loss)/d(pose[:3, :4]) (3 x 4 float32; with a
-    view axis V x 3 x 4) of the rays the select call with `cfg` / `poses` made at the select indices `used`, from d(loss)/d(rays)
-    rows g_rays (+ g_rays_2, added row by row)."""
+def _select_vjp(cfg, intr, poses, used, g_rays, g_rays_2, views, want_poses=True, want_intr=True, out=None, out_intr=None):
+    """The VJP entry point of _SELECT_ENTRY on the current stream: (d(loss)/d(pose[:3, :4]) (3 x 4 float32; with a view axis V x 3 x 4),
+    d(loss)/d(intr) (4 float32; None without `intr`)) of the rays the select call with `cfg` / `poses` / `intr` made at the select
+    indices `used`, from d(loss)/d(rays) rows g_rays (+ g_rays_2, added row by row).  With `intr` an output that is not wanted is
+    None and is not computed."""
     lib = L.get_lib()
-    n = used.numel()
-    if views:
-        nv = poses.shape[0]
-        tb = lib.pose_grad_views_tmp_bytes(n, nv)
-        if tb < 0:
-            raise RuntimeError("select_training_rays_views: %d rays over %d views is outside the kernel's limits" % (n, nv))
-        fn, table, shape = lib.select_rays_views_bwd, (nv, poses.data_ptr(), poses.stride(0), poses.stride(1)), (nv, 3, 4)
-    else:
-        tb = lib.pose_grad_tmp_bytes(n)
-        fn, table, shape = lib.select_rays_bwd, (poses.data_ptr(), poses.stride(-2)), (3, 4)
-    tmp = torch.empty(tb // 4 + 1, dtype=torch.float32, device=poses.device)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=poses.device)
-    with L.launch_on(poses, used, g_rays, g_rays_2, tmp, out) as st:
-        fn(C.byref(cfg), *table, used.data_ptr(), n, g_rays.data_ptr(), g_rays_2.data_ptr() if g_rays_2 is not None else None,
-           g_rays.stride(0), tmp.data_ptr(), tb, out.data_ptr(), st)
-    return out
-
-
-def _intr_vjp(cfg, intr, poses, used, g_rays, g_rays_2, views, want_poses=True, want_intr=True, out=None, out_intr=None):
-    """nerfhip_select_rays_views_intr_bwd on the current stream: (d(loss)/d(pose[:3, :4]) as _pose_vjp gives it, d(loss)/d(intr)
-    (4 float32)) of the rays the select call with `intr` made; an output that is not wanted is None."""
-    lib = L.get_lib()
-    n = used.numel()
-    nv = poses.shape[0] if views else 1
-    tb = lib.intr_grad_views_tmp_bytes(n, nv)
+    _, fn, tmp_fn = _SELECT_ENTRY[intr is not None, bool(views)]
+    n, nv = used.numel(), poses.shape[0] if views else 1
+    tb = getattr(lib, tmp_fn)(*((n, nv) if views or intr is not None else (n,)))
     if tb < 0:
         raise RuntimeError("select_training_rays_views: %d rays over %d views is outside the kernel's limits" % (n, nv))
-    tmp = torch.empty(tb // 4 + 1, dtype=torch.float32, device=poses.device)
-    if want_poses and out is None:
-        out = torch.empty((nv, 3, 4) if views else (3, 4), dtype=torch.float32, device=poses.device)
-    if want_intr and out_intr is None:
-        out_intr = torch.empty(4, dtype=torch.float32, device=poses.device)
-    gp, gi = (out if want_poses else None), (out_intr if want_intr else None)
+    mk = lambda *shape: torch.empty(shape, dtype=torch.float32, device=poses.device)  # noqa: E731
+    tmp = mk(tb // 4 + 1)
+    gp = gi = None
+    if intr is None or want_poses:
+        gp = out if out is not None else mk(*((nv, 3, 4) if views else (3, 4)))
+    if intr is not None and want_intr:
+        gi = out_intr if out_intr is not None else mk(4)
+    outs = (gp.data_ptr(),) if intr is None else (gp.data_ptr() if gp is not None else None, gi.data_ptr() if gi is not None else None)
     with L.launch_on(poses, used, g_rays, g_rays_2, tmp, gp, gi, intr) as st:
-        lib.select_rays_views_intr_bwd(C.byref(cfg), intr.data_ptr(), *_table_args(poses, views), used.data_ptr(), n, g_rays.data_ptr(),
-                                       g_rays_2.data_ptr() if g_rays_2 is not None else None, g_rays.stride(0), tmp.data_ptr(), tb,
-                                       gp.data_ptr() if gp is not None else None, gi.data_ptr() if gi is not None else None, st)
+        getattr(lib, fn)(C.byref(cfg), *_table_args(poses, views, intr), used.data_ptr(), n, g_rays.data_ptr(),
+                         g_rays_2.data_ptr() if g_rays_2 is not None else None, g_rays.stride(0), tmp.data_ptr(), tb, *outs, st)
     return gp, gi
 
 
@@ -486,12 +463,8 @@ class _SelectRays(torch.autograd.Function):
             return (None,) * 7
         cfg, p, used, views, k = ctx.keep
         g_rays = g_rays.contiguous().float()
-        gi = None
-        if k is None:
-            g34 = _pose_vjp(cfg, p, used, g_rays, None, views)
-        else:
-            g34, gi = _intr_vjp(cfg, k, p, used, g_rays, None, views, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
-            gi = gi.reshape(ctx.intr_shape) if gi is not None else None
+        g34, gi = _select_vjp(cfg, k, p, used, g_rays, None, views, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        gi = gi.reshape(ctx.intr_shape) if gi is not None else None
         g = None
         if g34 is not None:
             shape, dtype = ctx.poses_shape
@@ -529,12 +502,12 @@ def _select_bwd(what, cfg, poses, select_inds, g_rays, g_rays_2, out, views, int
     if intrinsics is None:
         if out_intrinsics is not None:
             raise RuntimeError("%s: out_intrinsics needs intrinsics" % what)
-        return _pose_vjp(cfg, p, used, g_rays, g_rays_2, views, out)
+        return _select_vjp(cfg, None, p, used, g_rays, g_rays_2, views, out=out)[0]
     if out_intrinsics is not None and (out_intrinsics.dtype != torch.float32 or tuple(out_intrinsics.shape) != (4,)
                                        or not out_intrinsics.is_contiguous() or out_intrinsics.device != p.device):
         raise RuntimeError("%s: out_intrinsics must be a contiguous float32 (4) tensor on %s" % (what, p.device))
-    return _intr_vjp(cfg, _intr_vector(intrinsics, p.device, what), p, used, g_rays, g_rays_2, views, want_poses=want_poses, out=out,
-                     out_intr=out_intrinsics)
+    return _select_vjp(cfg, _intr_vector(intrinsics, p.device, what), p, used, g_rays, g_rays_2, views, want_poses=want_poses, out=out,
+                       out_intr=out_intrinsics)
 
 
 def select_training_rays(height, width, focal_length, pose, image, num_random_rays, options, select_inds=None, seed=0,
