@@ -555,6 +555,52 @@ int nerfhip_intrinsics_fwd(const float* q, const float* base, int tie_focal, flo
 int nerfhip_intrinsics_bwd(const float* q, const float* base, int tie_focal, const float* g_intr, const unsigned char* mask,
                            float* g_q, nerfhip_stream_t stream);
 
+/* ---- lens distortion: k1, k2, p1, p2 on the device, with their gradient (COLMAP's OPENCV model; Self-Calibrating NeRF) --------------
+ * dist: dev float[4] = (k1, k2, p1, p2), shared by all views of a call.  RADIAL is p1 = p2 = 0, SIMPLE_RADIAL additionally k2 = 0.
+ * With (x, y) the UNDISTORTED normalised image point (y down), (xd, yd) = ((col - cx) / fx, (row - cy) / fy) the observed pixel,
+ * r2 = x^2 + y^2 and rad = 1 + k1 r2 + k2 r2^2:
+ *     xd = x rad + 2 p1 x y + p2 (r2 + 2 x^2),
+ *     yd = y rad + p1 (r2 + 2 y^2) + 2 p2 x y,                                   (xd, yd) = F(x, y; dist).
+ * A ray needs the inverse: F(x, y) = (xd, yd) is solved by Newton's iteration from (xd, yd) with the analytic 2 x 2 Jacobian J
+ * (symmetric for this model), NERFHIP_UNDISTORT_ITERS steps on every ray in fp32 -- no data-dependent exit, a ray's bits depend on
+ * its inputs only.  The camera direction is dc = (x, -y, -1); everything downstream is what the pin-hole forms do (rotation, NDC with
+ * cfg's fixed constants, packing, view directions).  dist = (0, 0, 0, 0) gives the rows of the form without dist bit for bit (J is
+ * exactly I, every residual exactly zero).
+ * Domain: the model is defined where det J >= 1/2 along the Newton path (moderate distortion over the image: e.g.
+ * (-0.25, 0.08, 5e-3, -4e-3) up to the normalised radius 1).  Outside it the outputs are unspecified; nothing checks for it.
+ * Gradient: by the implicit-function theorem at the solution, never through the iterations.  With g_dc = R^T g_d (g_d: the cotangent
+ * of the pre-NDC direction, as for g_intr above), g_xy = (g_dc[0], -g_dc[1]) and lambda = J^-T g_xy, ray i adds
+ *     g_k1 -= r2 (lambda . (x, y)),     g_k2 -= r2^2 (lambda . (x, y)),
+ *     g_p1 -= lambda0 2 x y + lambda1 (r2 + 2 y^2),     g_p2 -= lambda0 (r2 + 2 x^2) + lambda1 2 x y,
+ *     g_fx -= lambda0 xd / fx,   g_cx -= lambda0 / fx,   g_fy -= lambda1 yd / fy,   g_cy -= lambda1 / fy;
+ * the pose VJP is the pin-hole one on the undistorted dc. */
+#define NERFHIP_UNDISTORT_ITERS 8
+/* nerfhip_select_rays_views_intr with the extra pointer dist (not NULL).  intr == NULL: the scalar camera of cfg (focal, focal, W / 2,
+ * H / 2).  One launch, the same kernel. */
+int nerfhip_select_rays_views_dist(const nerfhip_select_cfg* cfg, const float* intr, const float* dist, int num_views,
+                                   const float* poses, int64_t pose_view_stride, int pose_ld, const float* images,
+                                   const int64_t* select_inds, int64_t n, float* rays, float* target, int64_t* inds_out,
+                                   nerfhip_stream_t stream);
+/* Its VJP w.r.t. the poses, the intrinsics and the distortion coefficients.  g_poses: dev float [V][3][4], g_intr: dev float [4],
+ * g_dist: dev float [4]; each may be NULL, not all three; each one given is written completely (n == 0: exact zeros) and has the same
+ * bits whether or not the others are asked.  g_poses, g_intr: as for nerfhip_select_rays_views_intr_bwd, on the undistorted dc.
+ * g_dist: ONE sum over all n rays in batch order along the single-view tree, exactly as g_intr is (G(n) partials of four sums, then
+ * one workgroup; two more launches; no atomics, no grouping; bit-reproducible); an index outside [0, V H W) is dropped.
+ * dist_mask: dev, one byte per coefficient, or NULL = all learned: an entry whose byte is 0 gets an exact zero (with Adam it never
+ * moves); the coefficients are stepped directly by nerfhip_adam_step.  dist = 0 gives the g_poses and g_intr of
+ * nerfhip_select_rays_views_intr_bwd bit for bit.  tmp: dev scratch of nerfhip_dist_grad_views_tmp_bytes(n, num_views) bytes (-1 where
+ * nerfhip_pose_grad_views_tmp_bytes is). */
+int64_t nerfhip_dist_grad_views_tmp_bytes(int64_t n, int num_views);
+int nerfhip_select_rays_views_dist_bwd(const nerfhip_select_cfg* cfg, const float* intr, const float* dist, int num_views,
+                                       const float* poses, int64_t pose_view_stride, int pose_ld, const int64_t* inds, int64_t n,
+                                       const float* g_rays, const float* g_rays_2, int g_rays_stride, void* tmp, int64_t tmp_bytes,
+                                       float* g_poses, float* g_intr, float* g_dist, const unsigned char* dist_mask,
+                                       nerfhip_stream_t stream);
+/* nerfhip_ray_bundle under dist (evaluation under a learned lens).  intr == NULL: the camera of (height, width, focal); else focal is
+ * not read.  Forward only.  One launch, the same kernel. */
+int nerfhip_ray_bundle_dist(int height, int width, float focal, const float* intr, const float* dist, const float* c2w, int c2w_ld,
+                            const int64_t* pixels, int64_t n, float* ray_origins, float* ray_directions, nerfhip_stream_t stream);
+
 /* ---- camera table: one se(3) twist per view composed onto a base pose (the parametrisation pose refinement steps) --------
  * poses[v] = base[v] * Exp(xi[v]): a camera-frame perturbation.  xi: dev float [V][6] = [w (3), v (3)]; Exp is the full SE(3)
  * exponential: R = I + A W + B W^2, t = (I + B W + C W^2) v with W = hat(w), th = |w|, A = sin th / th, B = (1 - cos th) / th^2,

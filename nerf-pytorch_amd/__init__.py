@@ -7,7 +7,7 @@ select_training_rays_views; their cameras as se(3) twists on base poses: cameras
 tree and the CLI scripts of the reference are out of scope.
 """
 from . import eval_utils, io_utils, models  # noqa: F401
-from .cameras import CameraTable, Intrinsics, se3_poses  # noqa: F401
+from .cameras import CameraTable, Distortion, Intrinsics, se3_poses  # noqa: F401
 from .cfg import AttrDict, make_options  # noqa: F401
 from .engine import TrainEngine  # noqa: F401
 from .models import FlexibleNeRFModel  # noqa: F401

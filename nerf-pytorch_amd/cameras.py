@@ -10,6 +10,8 @@ d(loss)/d(poses) back to the twists (nerfhip_pose_table_bwd), and the twists are
   field-and-camera step with no host work besides launches.
 * ``Intrinsics`` -- the shared intrinsics (fx, fy, cx, cy) on the device, their log-focal parametrisation and its Adam state;
   ``TrainEngine.step_on_views(intrinsics=...)`` learns them next to the field and the poses.
+* ``Distortion`` -- the shared lens distortion (k1, k2, p1, p2) on the device with its Adam state;
+  ``TrainEngine.step_on_views(distortion=...)`` learns it next to the field, the poses and the intrinsics.
 """
 import torch
 
@@ -82,8 +84,9 @@ def check_device_vector(t, shape, dev, what=None):
 
 
 class _AdamVector:
-    """A learned device vector with its Adam state: the parameter `_param` ("xi" / "q"), its gradient buffer "g_" + _param, the two
-    moments, step_count, lr, betas, eps; the state dict holds the parameter, the moments, `base` and the step count."""
+    """A learned device vector with its Adam state: the parameter `_param` ("xi" / "q" / "dist"), its gradient buffer "g_" + _param,
+    the two moments, step_count, lr, betas, eps; the state dict holds the parameter, the moments, `base` (where the vector is a
+    perturbation of one) and the step count."""
 
     def _init_adam(self, shape, lr, betas, eps):
         self.lr, self.betas, self.eps = lr, betas, eps
@@ -225,5 +228,50 @@ class Intrinsics(_AdamVector):
     def load_state_dict(self, state):
         if "learn" in state and (tuple(state["learn"]) if isinstance(state["learn"], (list, tuple)) else state["learn"]) != self.learn:
             raise RuntimeError("Intrinsics.load_state_dict: the state was saved with learn=%r, this object has learn=%r"
+                               % (state["learn"], self.learn))
+        super().load_state_dict(state)
+
+
+_LEARN_DIST = {"radial": (1, 1, 0, 0), "all": (1, 1, 1, 1), (): (0, 0, 0, 0)}
+
+
+class Distortion(_AdamVector):
+    """The shared lens distortion (k1, k2, p1, p2) of a capture under refinement (COLMAP's OPENCV model, include/nerfhip.h), resident
+    on the device, with its Adam state.  The coefficients are stepped directly -- there is no parametrisation between them and
+    Adam --: the selection's VJP writes d(loss)/d(k1, k2, p1, p2) into `g_dist` (an entry that is not learned gets an exact zero
+    there, so it stays where it is) and step() is the fused Adam kernel the nets use, on the four floats.  Every buffer is allocated
+    here once; no host synchronisation.
+
+    coeffs: the four starting values.  learn: "radial" (k1 and k2; the tangential p1 and p2 fixed), "all", or () (nothing moves)."""
+    _param, _holder = "dist", "the object"
+
+    def __init__(self, coeffs=(0.0, 0.0, 0.0, 0.0), learn="radial", lr=1e-3, betas=(0.9, 0.999), eps=1e-8, device=None):
+        key = tuple(learn) if isinstance(learn, (list, tuple)) else learn
+        if key not in _LEARN_DIST:
+            raise RuntimeError('Distortion: learn must be "radial", "all" or () (got %r)' % (learn,))
+        self.dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.dev.type != "cuda":
+            raise RuntimeError("Distortion lives on a CUDA (HIP) device (nerf_pytorch_amd has no CPU path)")
+        four = [float(v) for v in coeffs]
+        if len(four) != 4:
+            raise RuntimeError("Distortion: coeffs must be the four numbers (k1, k2, p1, p2) (got %r)" % (coeffs,))
+        self.lib = L.get_lib()
+        self.learn = key
+        self._init_adam((4,), lr, betas, eps)
+        self._state = ("dist", "exp_avg", "exp_avg_sq")
+        self.dist.copy_(torch.tensor(four, dtype=torch.float32))
+        self.mask = torch.tensor(_LEARN_DIST[key], dtype=torch.uint8).to(self.dev)
+
+    def values(self):
+        """(k1, k2, p1, p2): the object's own parameter of 4, the `distortion` of select_training_rays / get_ray_bundle /
+        render_pose_rows (the kernels read it in place; no launch)."""
+        return self.dist
+
+    def state_dict(self):
+        return dict(super().state_dict(), learn=self.learn)
+
+    def load_state_dict(self, state):
+        if "learn" in state and (tuple(state["learn"]) if isinstance(state["learn"], (list, tuple)) else state["learn"]) != self.learn:
+            raise RuntimeError("Distortion.load_state_dict: the state was saved with learn=%r, this object has learn=%r"
                                % (state["learn"], self.learn))
         super().load_state_dict(state)

@@ -80,9 +80,11 @@ extern "C" int nerfhip_select_indices(uint64_t seed, uint64_t step, int64_t popu
 // k of that view.  Pose of view v: poses + v * view_stride, row stride ld; image of view v: targets + v * H * W * channels.
 // Intrinsics, near / far, NDC and viewdirs are shared by all views.  One view (nerfhip_select_rays; the views entry point
 // at V = 1): g is k itself, nothing is divided out.  intr (device, fx fy cx cy; nerfhip_select_rays_views_intr) replaces the
-// camera of (s.height, s.width, s.focal) in the pin-hole direction -- and nowhere else: the NDC constants stay ndc's.
-NH_KERNEL void k_select_rays(nerfhip_select_cfg s, NhNdc ndc, const float* __restrict__ intr, const float* __restrict__ poses,
-                             int64_t view_stride, int ld, int num_views, const float* __restrict__ cached_o, const float* __restrict__ cached_d,
+// camera of (s.height, s.width, s.focal) in the pin-hole direction -- and nowhere else: the NDC constants stay ndc's.  dist (device,
+// k1 k2 p1 p2; nerfhip_select_rays_views_dist) undistorts that direction (nh_undistort); NULL skips the solve.
+NH_KERNEL void k_select_rays(nerfhip_select_cfg s, NhNdc ndc, const float* __restrict__ intr, const float* __restrict__ dist,
+                             const float* __restrict__ poses, int64_t view_stride, int ld, int num_views,
+                             const float* __restrict__ cached_o, const float* __restrict__ cached_d,
                              const float* __restrict__ targets, uint64_t population,
                              const int64_t* __restrict__ inds_in, int64_t n, float* __restrict__ rays,
                              float* __restrict__ target_out, int64_t* __restrict__ inds_out) {
@@ -110,7 +112,7 @@ NH_KERNEL void k_select_rays(nerfhip_select_cfg s, NhNdc ndc, const float* __res
         int64_t row = k % s.height, col = k / s.height;
         float f[4];
         nh_intrinsics(intr, s.height, s.width, s.focal, f);
-        nh_pinhole_ray(f, poses + view * view_stride, ld, row, col, o, d);
+        nh_camera_ray(f, dist, poses + view * view_stride, ld, row, col, o, d);
         pix = base + row * s.width + col;
     } else {
 #pragma unroll
@@ -133,17 +135,18 @@ static NhNdc ndc_of(const nerfhip_select_cfg* cfg) {
 }
 
 // the checks and the launch of the three selection entry points (`what`: the entry point, for the messages)
-static int select_launch(const char* what, const nerfhip_select_cfg* cfg, const float* intr, int num_views, const float* poses,
-                         int64_t view_stride, int ld, const float* co, const float* cd, const float* targets, int64_t population, const int64_t* inds,
-                         int64_t n, float* rays, float* target_out, int64_t* inds_out, nerfhip_stream_t stream) {
+static int select_launch(const char* what, const nerfhip_select_cfg* cfg, const float* intr, const float* dist, int num_views,
+                         const float* poses, int64_t view_stride, int ld, const float* co, const float* cd, const float* targets,
+                         int64_t population, const int64_t* inds, int64_t n, float* rays, float* target_out, int64_t* inds_out,
+                         nerfhip_stream_t stream) {
     NH_REQUIRE(cfg && n >= 0 && (n == 0 || rays), "%s: bad arguments", what);
     NH_REQUIRE(!targets || (target_out && cfg->channels >= 1 && cfg->channels <= 4), "%s: bad target arguments", what);
     NH_REQUIRE(population >= 0 && population <= ((int64_t)1 << 32), "%s: bad population", what);
     NH_REQUIRE(inds || (cfg->first >= 0 && cfg->first + n <= population),
                "%s: first + n exceeds the population (sampling is without replacement)", what);
     if (n == 0) return NERFHIP_OK;
-    NH_LAUNCH(k_select_rays, nh_ceil_div(n, 256), 256, 0, stream, *cfg, ndc_of(cfg), intr, poses, view_stride, ld, num_views, co, cd,
-              targets, (uint64_t)population, inds, n, rays, target_out, inds_out);
+    NH_LAUNCH(k_select_rays, nh_ceil_div(n, 256), 256, 0, stream, *cfg, ndc_of(cfg), intr, dist, poses, view_stride, ld, num_views, co,
+              cd, targets, (uint64_t)population, inds, n, rays, target_out, inds_out);
     return nh_launch_status(what);
 }
 
@@ -171,8 +174,8 @@ extern "C" int nerfhip_select_rays(const nerfhip_select_cfg* cfg, const float* c
                                    const int64_t* select_inds, int64_t n, float* rays, float* target,
                                    int64_t* inds_out, nerfhip_stream_t stream) {
     NH_REQUIRE(cfg && c2w && c2w_ld >= 4 && cfg->height > 0 && cfg->width > 0, "select_rays: bad arguments");
-    return select_launch("select_rays", cfg, nullptr, 1, c2w, 0, c2w_ld, nullptr, nullptr, image, (int64_t)cfg->height * cfg->width,
-                         select_inds, n, rays, target, inds_out, stream);
+    return select_launch("select_rays", cfg, nullptr, nullptr, 1, c2w, 0, c2w_ld, nullptr, nullptr, image,
+                         (int64_t)cfg->height * cfg->width, select_inds, n, rays, target, inds_out, stream);
 }
 
 extern "C" int nerfhip_select_cached_rays(const nerfhip_select_cfg* cfg, const float* ray_origins,
@@ -180,8 +183,8 @@ extern "C" int nerfhip_select_cached_rays(const nerfhip_select_cfg* cfg, const f
                                           const int64_t* select_inds, int64_t n, float* rays, float* target,
                                           int64_t* inds_out, nerfhip_stream_t stream) {
     NH_REQUIRE(cfg && ray_origins && ray_directions, "select_cached_rays: bad arguments");
-    return select_launch("select_cached_rays", cfg, nullptr, 0, nullptr, 0, 0, ray_origins, ray_directions, targets, population,
-                         select_inds, n, rays, target, inds_out, stream);
+    return select_launch("select_cached_rays", cfg, nullptr, nullptr, 0, nullptr, 0, 0, ray_origins, ray_directions, targets,
+                         population, select_inds, n, rays, target, inds_out, stream);
 }
 
 extern "C" int nerfhip_select_rays_views(const nerfhip_select_cfg* cfg, int num_views, const float* poses,
@@ -189,8 +192,8 @@ extern "C" int nerfhip_select_rays_views(const nerfhip_select_cfg* cfg, int num_
                                          int64_t n, float* rays, float* target, int64_t* inds_out, nerfhip_stream_t stream) {
     int rc = views_check(cfg, num_views, poses, pose_view_stride, pose_ld, "select_rays_views");
     if (rc) return rc;
-    return select_launch("select_rays_views", cfg, nullptr, num_views, poses, pose_view_stride, pose_ld, nullptr, nullptr, images,
-                         (int64_t)num_views * cfg->height * cfg->width, select_inds, n, rays, target, inds_out, stream);
+    return select_launch("select_rays_views", cfg, nullptr, nullptr, num_views, poses, pose_view_stride, pose_ld, nullptr, nullptr,
+                         images, (int64_t)num_views * cfg->height * cfg->width, select_inds, n, rays, target, inds_out, stream);
 }
 
 extern "C" int nerfhip_select_rays_views_intr(const nerfhip_select_cfg* cfg, const float* intr, int num_views, const float* poses,
@@ -201,7 +204,19 @@ extern "C" int nerfhip_select_rays_views_intr(const nerfhip_select_cfg* cfg, con
     NH_REQUIRE(intr, "%s: intr must not be NULL", what);
     int rc = views_check(cfg, num_views, poses, pose_view_stride, pose_ld, what);
     if (rc) return rc;
-    return select_launch(what, cfg, intr, num_views, poses, pose_view_stride, pose_ld, nullptr, nullptr, images,
+    return select_launch(what, cfg, intr, nullptr, num_views, poses, pose_view_stride, pose_ld, nullptr, nullptr, images,
+                         (int64_t)num_views * cfg->height * cfg->width, select_inds, n, rays, target, inds_out, stream);
+}
+
+extern "C" int nerfhip_select_rays_views_dist(const nerfhip_select_cfg* cfg, const float* intr, const float* dist, int num_views,
+                                              const float* poses, int64_t pose_view_stride, int pose_ld, const float* images,
+                                              const int64_t* select_inds, int64_t n, float* rays, float* target, int64_t* inds_out,
+                                              nerfhip_stream_t stream) {
+    const char* what = "select_rays_views_dist";
+    NH_REQUIRE(dist, "%s: dist must not be NULL", what);
+    int rc = views_check(cfg, num_views, poses, pose_view_stride, pose_ld, what);
+    if (rc) return rc;
+    return select_launch(what, cfg, intr, dist, num_views, poses, pose_view_stride, pose_ld, nullptr, nullptr, images,
                          (int64_t)num_views * cfg->height * cfg->width, select_inds, n, rays, target, inds_out, stream);
 }
 
@@ -228,6 +243,7 @@ struct PoseVjpArgs {
     nerfhip_select_cfg s;
     NhNdc ndc;
     const float* intr;        // select form: the device intrinsics (fx fy cx cy), or NULL: the camera of (s.height, s.width, s.focal)
+    const float* dist;        // select form: the device distortion coefficients (k1 k2 p1 p2), or NULL: the pin-hole camera
     int select;               // 1: select form (row k % height, col k / height; packing / NDC backward); 0: bundle form
     const float* c2w;         // select form only (the pre-NDC ray)
     int ld;
@@ -249,8 +265,8 @@ PoseVjpArgs select_vjp_args(const nerfhip_select_cfg* cfg, const float* c2w, int
     return a;
 }
 
-// this ray's camera direction dc under the intrinsics f, and the cotangents go / gd of its pre-NDC origin / direction
-// (ray i of the batch, k: its select index / linear pixel id)
+// this ray's camera direction dc under the intrinsics f (undistorted under a.dist), and the cotangents go / gd of its pre-NDC
+// origin / direction (ray i of the batch, k: its select index / linear pixel id)
 // c2w: the ray's pose (select form only)
 NH_DEVICE void pose_vjp_ray_cot(const PoseVjpArgs& a, const float* f, const float* __restrict__ c2w, int64_t i, int64_t k, float* dc,
                                 float* go, float* gd) {
@@ -262,7 +278,7 @@ NH_DEVICE void pose_vjp_ray_cot(const PoseVjpArgs& a, const float* f, const floa
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) go[c] = 0.f, gd[c] = 0.f;
-    nh_pinhole_cam(f[0], f[1], f[2], f[3], row, col, dc);
+    nh_camera_dir(f, a.dist, row, col, dc);
     if (a.select) {
         const float* ga = a.g_a + i * a.g_stride;
         const float* gb = a.g_b ? a.g_b + i * a.g_stride : nullptr;
@@ -270,7 +286,7 @@ NH_DEVICE void pose_vjp_ray_cot(const PoseVjpArgs& a, const float* f, const floa
         const int cols = a.s.use_viewdirs ? 11 : 8;
         for (int c = 0; c < cols; ++c) gr[c] = gb ? ga[c] + gb[c] : ga[c];  // (columns 6, 7: near / far carry no gradient)
         float o[3], d[3];
-        nh_pinhole_ray(f, c2w, a.ld, row, col, o, d);
+        nh_rotate_ray(dc, c2w, a.ld, o, d);
         if (a.s.ndc) {
             nh_ndc_ray_vjp(a.ndc, o, d, gr, gr + 3, go, gd);
         } else {
@@ -491,39 +507,94 @@ int64_t pv_views_words(int64_t n, int num_views, int64_t* slots) {
 // are shared by the views, so this is ONE sum over all n rays in batch order -- the single-view tree above (k_pose_vjp_part's loop,
 // pv_block_sum<4>, k_pose_vjp_sum<4>) with four sums in place of twelve; each ray reads the pose of its own view, inds[i] / (H W).  No
 // grouping, no atomics: the order depends on n only.  An index outside [0, V H W) contributes nothing (as it belongs to no view above).
+// Under lens distortion (p.a.dist) dc is the undistorted direction and the four terms come from nh_undistort_vjp; dist = 0 gives the
+// pin-hole terms' bits.
+// ray i's camera direction dc and the cotangent of its x and y, g_dc = R^T g_d; false: the index belongs to no view (dropped)
+NH_DEVICE bool intr_vjp_ray_gdc(const PoseViewsArgs& p, const float* f, int64_t population, int64_t i, int64_t* row, int64_t* col,
+                                float* dc, float* gdc) {
+    const int64_t g = p.a.inds[i];
+    if (g < 0 || g >= population) return false;
+    const int64_t view = p.num_views > 1 ? g / p.hw : 0;
+    const float* __restrict__ c2w = p.a.c2w + view * p.view_stride;
+    const int64_t k = g - view * p.hw;
+    *row = k % p.a.s.height, *col = k / p.a.s.height;
+    float go[3], gd[3];
+    pose_vjp_ray_cot(p.a, f, c2w, i, k, dc, go, gd);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        float v = gd[0] * c2w[j];
+        v = v + gd[1] * c2w[p.a.ld + j];
+        v = v + gd[2] * c2w[2 * p.a.ld + j];
+        gdc[j] = v;
+    }
+    return true;
+}
+// ray i's terms under distortion (nh_undistort_vjp at the ray's solution): those of the coefficients and / or of the intrinsics
+NH_DEVICE void dist_vjp_ray_terms(const float* f, const float* kp, int64_t row, int64_t col, const float* dc,
+                                  const float* gdc, float* t_dist, float* t_intr) {
+    float pin[3];
+    nh_pinhole_cam(f[0], f[1], f[2], f[3], row, col, pin);  // the observed point (xd, yd) = (pin[0], -pin[1])
+    nh_undistort_vjp(kp, f, dc[0], -dc[1], pin[0], -pin[1], gdc[0], -gdc[1], t_dist, t_intr);
+}
+
 NH_KERNEL void k_intr_vjp_part(PoseViewsArgs p, float* __restrict__ part) {
     NH_SHARED float s_part[PV_THREADS / 64][4];
-    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f}, f[4];
+    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f}, f[4], kp[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     nh_intrinsics(p.a.intr, p.a.s.height, p.a.s.width, p.a.s.focal, f);
+    if (p.a.dist) kp[0] = p.a.dist[0], kp[1] = p.a.dist[1], kp[2] = p.a.dist[2], kp[3] = p.a.dist[3];
     const int64_t population = (int64_t)p.num_views * p.hw;
     const int64_t step = (int64_t)gridDim.x * PV_THREADS;
     for (int64_t i = (int64_t)blockIdx.x * PV_THREADS + threadIdx.x; i < p.a.n; i += step) {
-        const int64_t g = p.a.inds[i];
-        if (g < 0 || g >= population) continue;
-        const int64_t view = p.num_views > 1 ? g / p.hw : 0;
-        const float* __restrict__ c2w = p.a.c2w + view * p.view_stride;
-        float dc[3], go[3], gd[3], gdc[2];
-        pose_vjp_ray_cot(p.a, f, c2w, i, g - view * p.hw, dc, go, gd);
+        int64_t row, col;
+        float dc[3], gdc[2];
+        if (!intr_vjp_ray_gdc(p, f, population, i, &row, &col, dc, gdc)) continue;
+        if (p.a.dist) {
+            float t[4];
+            dist_vjp_ray_terms(f, kp, row, col, dc, gdc, nullptr, t);
 #pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            float v = gd[0] * c2w[k];
-            v = v + gd[1] * c2w[p.a.ld + k];
-            v = v + gd[2] * c2w[2 * p.a.ld + k];
-            gdc[k] = v;
+            for (int j = 0; j < 4; ++j) acc[j] += t[j];
+        } else {
+            acc[0] += -(gdc[0] * dc[0]) / f[0];
+            acc[1] += -(gdc[1] * dc[1]) / f[1];
+            acc[2] += -gdc[0] / f[0];
+            acc[3] += gdc[1] / f[1];
         }
-        acc[0] += -(gdc[0] * dc[0]) / f[0];
-        acc[1] += -(gdc[1] * dc[1]) / f[1];
-        acc[2] += -gdc[0] / f[0];
-        acc[3] += gdc[1] / f[1];
     }
     pv_block_sum<4>(acc, s_part, part + (int64_t)blockIdx.x * 4);
 }
 
-// both forms of the views VJP: g_poses (the three launches above) and / or g_intr (two launches); intr == NULL: cfg's camera
-int views_bwd(const char* what, const nerfhip_select_cfg* cfg, const float* intr, int num_views, const float* poses,
+// ---- the VJP w.r.t. the shared distortion coefficients (k1, k2, p1, p2) -------------------------------------------------------------
+// The same ONE sum over all n rays in batch order along the single-view tree, with nh_undistort_vjp's four coefficient terms.  mask
+// (device, one byte per coefficient, or NULL = all): a masked entry's partial is an exact zero in every workgroup, so its sum is one.
+NH_KERNEL void k_dist_vjp_part(PoseViewsArgs p, const unsigned char* __restrict__ mask, float* __restrict__ part) {
+    NH_SHARED float s_part[PV_THREADS / 64][4];
+    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f}, f[4];
+    nh_intrinsics(p.a.intr, p.a.s.height, p.a.s.width, p.a.s.focal, f);
+    const float kp[4] = {p.a.dist[0], p.a.dist[1], p.a.dist[2], p.a.dist[3]};
+    const int64_t population = (int64_t)p.num_views * p.hw;
+    const int64_t step = (int64_t)gridDim.x * PV_THREADS;
+    for (int64_t i = (int64_t)blockIdx.x * PV_THREADS + threadIdx.x; i < p.a.n; i += step) {
+        int64_t row, col;
+        float dc[3], gdc[2], t[4];
+        if (!intr_vjp_ray_gdc(p, f, population, i, &row, &col, dc, gdc)) continue;
+        dist_vjp_ray_terms(f, kp, row, col, dc, gdc, t, nullptr);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] += t[j];
+    }
+    if (mask) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (!mask[j]) acc[j] = 0.0f;
+    }
+    pv_block_sum<4>(acc, s_part, part + (int64_t)blockIdx.x * 4);
+}
+
+// every form of the views VJP: g_poses (the three launches above), g_intr (two launches) and / or g_dist (two launches); intr == NULL:
+// cfg's camera; dist == NULL: no lens distortion (then g_dist is NULL too)
+int views_bwd(const char* what, const nerfhip_select_cfg* cfg, const float* intr, const float* dist, int num_views, const float* poses,
               int64_t pose_view_stride, int pose_ld, const int64_t* inds, int64_t n, const float* g_rays, const float* g_rays_2,
               int g_rays_stride, void* tmp, int64_t need, int64_t tmp_bytes, const char* need_name, float* g_poses, float* g_intr,
-              nerfhip_stream_t stream) {
+              float* g_dist, const unsigned char* dist_mask, nerfhip_stream_t stream) {
     int rc = views_check(cfg, num_views, poses, pose_view_stride, pose_ld, what);
     if (rc) return rc;
     NH_REQUIRE(n >= 0 && n < ((int64_t)1 << 31) && (n == 0 || (inds && g_rays)), "%s: bad arguments", what);
@@ -537,7 +608,7 @@ int views_bwd(const char* what, const nerfhip_select_cfg* cfg, const float* intr
     if (n > 0) {
         words = pv_views_words(n, num_views, &slots);
         p.a = select_vjp_args(cfg, poses, pose_ld, inds, n, g_rays, g_rays_2, g_rays_stride, tmp);
-        p.a.intr = intr;
+        p.a.intr = intr, p.a.dist = dist;
         p.num_views = num_views, p.view_stride = pose_view_stride, p.hw = (int64_t)cfg->height * cfg->width;
         p.cnt = (int*)tmp + slots * 12, p.off = p.cnt + num_views, p.list = p.off + num_views;
     }
@@ -566,6 +637,19 @@ int views_bwd(const char* what, const nerfhip_select_cfg* cfg, const float* intr
         NH_LAUNCH_NAMED("k_intr_vjp_sum", k_pose_vjp_sum<4>, 1, 4 * 64, 0, stream, (const float*)part, (int)wgs, (const int*)nullptr, (const int*)nullptr,
                   g_intr);  // (n == 0: zeros)
         rc = nh_launch_status(what);
+        if (rc) return rc;
+    }
+    if (g_dist) {
+        const int64_t wgs = pv_wgs(n);
+        float* part = n > 0 ? (float*)tmp + words + wgs * 4 : nullptr;  // [G(n)][4], behind the intrinsics' partials
+        if (wgs > 0) {
+            NH_LAUNCH(k_dist_vjp_part, wgs, PV_THREADS, 0, stream, p, dist_mask, part);
+            rc = nh_launch_status(what);
+            if (rc) return rc;
+        }
+        NH_LAUNCH_NAMED("k_dist_vjp_sum", k_pose_vjp_sum<4>, 1, 4 * 64, 0, stream, (const float*)part, (int)wgs, (const int*)nullptr,
+                        (const int*)nullptr, g_dist);  // (n == 0: zeros)
+        rc = nh_launch_status(what);
     }
     return rc;
 }
@@ -590,9 +674,27 @@ extern "C" int nerfhip_select_rays_views_intr_bwd(const nerfhip_select_cfg* cfg,
     const char* what = "select_rays_views_intr_bwd";
     NH_REQUIRE(intr, "%s: intr must not be NULL", what);
     NH_REQUIRE(g_poses || g_intr, "%s: g_poses and g_intr must not both be NULL", what);
-    return views_bwd(what, cfg, intr, num_views, poses, pose_view_stride, pose_ld, inds, n, g_rays, g_rays_2, g_rays_stride, tmp,
-                     nerfhip_intr_grad_views_tmp_bytes(n, num_views), tmp_bytes, "nerfhip_intr_grad_views_tmp_bytes", g_poses, g_intr,
-                     stream);
+    return views_bwd(what, cfg, intr, nullptr, num_views, poses, pose_view_stride, pose_ld, inds, n, g_rays, g_rays_2, g_rays_stride,
+                     tmp, nerfhip_intr_grad_views_tmp_bytes(n, num_views), tmp_bytes, "nerfhip_intr_grad_views_tmp_bytes", g_poses,
+                     g_intr, nullptr, nullptr, stream);
+}
+
+extern "C" int64_t nerfhip_dist_grad_views_tmp_bytes(int64_t n, int num_views) {
+    const int64_t b = nerfhip_intr_grad_views_tmp_bytes(n, num_views);
+    return b < 0 ? -1 : b + pv_wgs(n) * 4 * (int64_t)sizeof(float);
+}
+
+extern "C" int nerfhip_select_rays_views_dist_bwd(const nerfhip_select_cfg* cfg, const float* intr, const float* dist, int num_views,
+                                                  const float* poses, int64_t pose_view_stride, int pose_ld, const int64_t* inds,
+                                                  int64_t n, const float* g_rays, const float* g_rays_2, int g_rays_stride, void* tmp,
+                                                  int64_t tmp_bytes, float* g_poses, float* g_intr, float* g_dist,
+                                                  const unsigned char* dist_mask, nerfhip_stream_t stream) {
+    const char* what = "select_rays_views_dist_bwd";
+    NH_REQUIRE(dist, "%s: dist must not be NULL", what);
+    NH_REQUIRE(g_poses || g_intr || g_dist, "%s: g_poses, g_intr and g_dist must not all be NULL", what);
+    return views_bwd(what, cfg, intr, dist, num_views, poses, pose_view_stride, pose_ld, inds, n, g_rays, g_rays_2, g_rays_stride, tmp,
+                     nerfhip_dist_grad_views_tmp_bytes(n, num_views), tmp_bytes, "nerfhip_dist_grad_views_tmp_bytes", g_poses, g_intr,
+                     g_dist, dist_mask, stream);
 }
 
 extern "C" int nerfhip_select_rays_views_bwd(const nerfhip_select_cfg* cfg, int num_views, const float* poses,
@@ -601,9 +703,9 @@ extern "C" int nerfhip_select_rays_views_bwd(const nerfhip_select_cfg* cfg, int 
                                              int64_t tmp_bytes, float* g_poses, nerfhip_stream_t stream) {
     const char* what = "select_rays_views_bwd";
     NH_REQUIRE(g_poses, "%s: bad arguments", what);
-    return views_bwd(what, cfg, nullptr, num_views, poses, pose_view_stride, pose_ld, inds, n, g_rays, g_rays_2, g_rays_stride, tmp,
-                     nerfhip_pose_grad_views_tmp_bytes(n, num_views), tmp_bytes, "nerfhip_pose_grad_views_tmp_bytes", g_poses, nullptr,
-                     stream);
+    return views_bwd(what, cfg, nullptr, nullptr, num_views, poses, pose_view_stride, pose_ld, inds, n, g_rays, g_rays_2, g_rays_stride,
+                     tmp, nerfhip_pose_grad_views_tmp_bytes(n, num_views), tmp_bytes, "nerfhip_pose_grad_views_tmp_bytes", g_poses,
+                     nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int64_t nerfhip_pose_grad_tmp_bytes(int64_t n) { return n < 0 ? -1 : pv_wgs(n) * 12 * (int64_t)sizeof(float); }

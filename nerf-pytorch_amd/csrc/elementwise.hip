@@ -19,16 +19,18 @@ void nh_set_error(const char* fmt, ...) {
 extern "C" const char* nerfhip_last_error(void) { return g_err; }
 extern "C" int nerfhip_version(void) {
 #ifdef NH_DIAG  // (make variant: an A/B or diagnostic build -- nh_diag.h; the Python package refuses it)
-    return 110 + NH_DIAG_VERSION_FLAG;
+    return 111 + NH_DIAG_VERSION_FLAG;
 #else
-    return 110;  // (102: round 6 -- the compacted backward's three entry points; 103: + the fused backward modes 3 / 4 of 64-wide nets; 104: + mode 5;
+    return 111;  // (102: round 6 -- the compacted backward's three entry points; 103: + the fused backward modes 3 / 4 of 64-wide nets; 104: + mode 5;
                  // 105: + the pose VJP, nerfhip_pose_grad_tmp_bytes / nerfhip_ray_bundle_bwd / nerfhip_select_rays_bwd;
                  // 106: + batches over a stack of views, nerfhip_select_rays_views / _views_bwd / nerfhip_pose_grad_views_tmp_bytes;
                  // 107: + the camera table, nerfhip_pose_table_fwd / nerfhip_pose_table_bwd;
                  // 108: + the encoding window, nerfhip_plan_window_index / nerfhip_window_params / nerfhip_window_grads;
                  // 109: + the frozen ray gradient, nerfhip_render_grad_rays / nerfhip_render_grad_rays_tmp_bytes;
                  // 110: + device intrinsics, nerfhip_select_rays_views_intr / _intr_bwd / nerfhip_intr_grad_views_tmp_bytes /
-                 //      nerfhip_ray_bundle_intr / nerfhip_intrinsics_fwd / nerfhip_intrinsics_bwd)
+                 //      nerfhip_ray_bundle_intr / nerfhip_intrinsics_fwd / nerfhip_intrinsics_bwd;
+                 // 111: + lens distortion, nerfhip_select_rays_views_dist / _dist_bwd / nerfhip_dist_grad_views_tmp_bytes /
+                 //      nerfhip_ray_bundle_dist)
 #endif
 }
 extern "C" int nerfhip_is_emulated(void) {
@@ -167,8 +169,10 @@ extern "C" int nerfhip_profile_report(char* buf, int64_t cap) {
 }
 
 // ---- K1 get_ray_bundle (nerf/nerf_helpers.py:67-110) ----------------------------------------------------------------
-// intr (device, fx fy cx cy; nerfhip_ray_bundle_intr), or NULL: the camera of (height, width, focal)
-NH_KERNEL void k_ray_bundle(int height, int width, float focal, const float* __restrict__ intr, const float* __restrict__ c2w, int ld,
+// intr (device, fx fy cx cy; nerfhip_ray_bundle_intr), or NULL: the camera of (height, width, focal); dist (device, k1 k2 p1 p2;
+// nerfhip_ray_bundle_dist), or NULL: no lens distortion
+NH_KERNEL void k_ray_bundle(int height, int width, float focal, const float* __restrict__ intr, const float* __restrict__ dist,
+                            const float* __restrict__ c2w, int ld,
                             const int64_t* __restrict__ pixels, int64_t n, float* __restrict__ ro,
                             float* __restrict__ rd) {
     int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -176,7 +180,7 @@ NH_KERNEL void k_ray_bundle(int height, int width, float focal, const float* __r
     int64_t p = pixels ? pixels[idx] : idx;
     float o[3], d[3], f[4];
     nh_intrinsics(intr, height, width, focal, f);
-    nh_pinhole_ray(f, c2w, ld, p / width, p % width, o, d);
+    nh_camera_ray(f, dist, c2w, ld, p / width, p % width, o, d);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         rd[idx * 3 + c] = d[c];
@@ -191,8 +195,8 @@ extern "C" int nerfhip_ray_bundle(int height, int width, float focal, const floa
                "ray_bundle: bad arguments");
     NH_REQUIRE(pixels || n == (int64_t)height * width, "ray_bundle: n must be height*width when pixels is NULL");
     if (n == 0) return NERFHIP_OK;
-    NH_LAUNCH(k_ray_bundle, nh_ceil_div(n, 256), 256, 0, stream, height, width, focal, (const float*)nullptr, c2w, c2w_ld, pixels, n,
-              ray_origins, ray_directions);
+    NH_LAUNCH(k_ray_bundle, nh_ceil_div(n, 256), 256, 0, stream, height, width, focal, (const float*)nullptr, (const float*)nullptr,
+              c2w, c2w_ld, pixels, n, ray_origins, ray_directions);
     return nh_launch_status("ray_bundle");
 }
 
@@ -203,9 +207,22 @@ extern "C" int nerfhip_ray_bundle_intr(int height, int width, const float* intr,
                "ray_bundle_intr: bad arguments");
     NH_REQUIRE(pixels || n == (int64_t)height * width, "ray_bundle_intr: n must be height*width when pixels is NULL");
     if (n == 0) return NERFHIP_OK;
-    NH_LAUNCH(k_ray_bundle, nh_ceil_div(n, 256), 256, 0, stream, height, width, 0.0f, intr, c2w, c2w_ld, pixels, n, ray_origins,
-              ray_directions);
+    NH_LAUNCH(k_ray_bundle, nh_ceil_div(n, 256), 256, 0, stream, height, width, 0.0f, intr, (const float*)nullptr, c2w, c2w_ld, pixels,
+              n, ray_origins, ray_directions);
     return nh_launch_status("ray_bundle_intr");
+}
+
+extern "C" int nerfhip_ray_bundle_dist(int height, int width, float focal, const float* intr, const float* dist, const float* c2w,
+                                       int c2w_ld, const int64_t* pixels, int64_t n, float* ray_origins, float* ray_directions,
+                                       nerfhip_stream_t stream) {
+    NH_REQUIRE(dist, "ray_bundle_dist: dist must not be NULL");
+    NH_REQUIRE(height > 0 && width > 0 && c2w && ray_origins && ray_directions && c2w_ld >= 4 && n >= 0,
+               "ray_bundle_dist: bad arguments");
+    NH_REQUIRE(pixels || n == (int64_t)height * width, "ray_bundle_dist: n must be height*width when pixels is NULL");
+    if (n == 0) return NERFHIP_OK;
+    NH_LAUNCH(k_ray_bundle, nh_ceil_div(n, 256), 256, 0, stream, height, width, focal, intr, dist, c2w, c2w_ld, pixels, n, ray_origins,
+              ray_directions);
+    return nh_launch_status("ray_bundle_dist");
 }
 
 // ---- the intrinsics' parametrisation (what Adam steps when the camera model is learned) -----------------------------------------

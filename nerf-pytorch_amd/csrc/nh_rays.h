@@ -1,6 +1,7 @@
 // nh_rays.h -- per-ray device arithmetic shared by the unit kernels (elementwise.hip), the fused training-ray selection and
-// the pose VJP (dataio.hip), so that they produce identical bits.
+// the camera VJPs (dataio.hip: pose, intrinsics, lens distortion), so that they produce identical bits.
 #pragma once
+#include "../../include/nerfhip.h"
 #include "nh_device.h"
 
 // get_ray_bundle (nerf/nerf_helpers.py:67-110)
@@ -24,10 +25,8 @@ NH_DEVICE void nh_intrinsics(const float* __restrict__ intr, int height, int wid
         f[0] = focal, f[1] = focal, f[2] = (float)(width * 0.5), f[3] = (float)(height * 0.5);
     }
 }
-// one pin-hole ray: d = c2w[:3, :3] dc, o = c2w[:3, 3]
-NH_DEVICE void nh_pinhole_ray(const float* f, const float* __restrict__ c2w, int ld, int64_t row, int64_t col, float* o, float* d) {
-    float dc[3];
-    nh_pinhole_cam(f[0], f[1], f[2], f[3], row, col, dc);
+// a ray from its camera direction: d = c2w[:3, :3] dc, o = c2w[:3, 3]
+NH_DEVICE void nh_rotate_ray(const float* dc, const float* __restrict__ c2w, int ld, float* o, float* d) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         float v = dc[0] * c2w[c * ld + 0];
@@ -36,6 +35,88 @@ NH_DEVICE void nh_pinhole_ray(const float* f, const float* __restrict__ c2w, int
         d[c] = v;
         o[c] = c2w[c * ld + 3];
     }
+}
+
+// ---- lens distortion (include/nerfhip.h: COLMAP's OPENCV model, kp = (k1, k2, p1, p2)) ---------------------------------------------
+// (Fx, Fy) = F(x, y; kp), the distorted image of the normalised point (x, y) (y down), and F's Jacobian [[a, b], [b, d]], which is
+// symmetric for this model.  With r2 = x^2 + y^2, rad = 1 + k1 r2 + k2 r2^2 and dr = 2 (k1 + 2 k2 r2) (so that d rad / dx = dr x):
+//     Fx = x rad + 2 p1 x y + p2 (r2 + 2 x^2),              Fy = y rad + p1 (r2 + 2 y^2) + 2 p2 x y,
+//     a = rad + dr x^2 + 2 p1 y + 6 p2 x,     b = dr x y + 2 p1 x + 2 p2 y,     d = rad + dr y^2 + 6 p1 y + 2 p2 x.
+// kp = 0: every product with a coefficient is a zero, so F is (x, y) and J is I, exactly.
+NH_DEVICE void nh_distort(const float* kp, float x, float y, float* Fx, float* Fy, float* a, float* b, float* d) {
+    const float k1 = kp[0], k2 = kp[1], p1 = kp[2], p2 = kp[3];
+    const float xx = x * x, yy = y * y, xy = x * y;
+    const float r2 = xx + yy;
+    const float rad = (1.0f + k1 * r2) + k2 * (r2 * r2);
+    const float dr = 2.0f * (k1 + (2.0f * k2) * r2);
+    *Fx = (x * rad + (2.0f * p1) * xy) + p2 * (r2 + 2.0f * xx);
+    *Fy = (y * rad + p1 * (r2 + 2.0f * yy)) + (2.0f * p2) * xy;
+    *a = ((rad + dr * xx) + (2.0f * p1) * y) + (6.0f * p2) * x;
+    *b = (dr * xy + (2.0f * p1) * x) + (2.0f * p2) * y;
+    *d = ((rad + dr * yy) + (6.0f * p1) * y) + (2.0f * p2) * x;
+}
+// the undistorted point (x, y) of the observed (xd, yd): Newton's iteration on F(x, y) = (xd, yd) from (xd, yd), with the analytic
+// Jacobian, NERFHIP_UNDISTORT_ITERS steps on every ray -- no data-dependent exit, so a ray's bits depend on its inputs only.  kp = 0:
+// the residual is an exact zero and J is I, so every step is x - 0 and (xd, yd) comes back bit for bit.
+NH_DEVICE void nh_undistort(const float* kp, float xd, float yd, float* x, float* y) {
+    float px = xd, py = yd;
+    for (int it = 0; it < NERFHIP_UNDISTORT_ITERS; ++it) {
+        float Fx, Fy, a, b, d;
+        nh_distort(kp, px, py, &Fx, &Fy, &a, &b, &d);
+        const float rx = Fx - xd, ry = Fy - yd;
+        const float det = a * d - b * b;
+        px = px - (d * rx - b * ry) / det;
+        py = py - (a * ry - b * rx) / det;
+    }
+    *x = px, *y = py;
+}
+// The gradient through the solve by the implicit-function theorem (nothing is back-propagated through the iterations): (x, y) the
+// solution, (xd, yd) the observed point under the intrinsics f, (g0, g1) the cotangent of (x, y); lambda = J^-T (g0, g1) at the
+// solution.  t_dist: the ray's terms of d(loss)/d(k1, k2, p1, p2); t_intr: those of d(loss)/d(fx, fy, cx, cy), in the operation order
+// of the pin-hole terms (kp = 0: lambda is (g0, g1) and they are the pin-hole terms bit for bit).  Either may be NULL.
+NH_DEVICE void nh_undistort_vjp(const float* kp, const float* f, float x, float y, float xd, float yd, float g0, float g1,
+                                float* t_dist, float* t_intr) {
+    float Fx, Fy, a, b, d;
+    nh_distort(kp, x, y, &Fx, &Fy, &a, &b, &d);
+    const float det = a * d - b * b;
+    const float l0 = (d * g0 - b * g1) / det, l1 = (a * g1 - b * g0) / det;
+    if (t_dist) {
+        const float xx = x * x, yy = y * y, xy2 = 2.0f * (x * y);
+        const float r2 = xx + yy;
+        const float lp = l0 * x + l1 * y;
+        t_dist[0] = -(r2 * lp);
+        t_dist[1] = -((r2 * r2) * lp);
+        t_dist[2] = -(l0 * xy2 + l1 * (r2 + 2.0f * yy));
+        t_dist[3] = -(l0 * (r2 + 2.0f * xx) + l1 * xy2);
+    }
+    if (t_intr) {
+        t_intr[0] = -(l0 * xd) / f[0];
+        t_intr[1] = -(l1 * yd) / f[1];
+        t_intr[2] = -l0 / f[0];
+        t_intr[3] = -l1 / f[1];
+    }
+}
+// the camera direction of pixel (row, col): the pin-hole one, undistorted under dist (device, k1 k2 p1 p2) when given -- (x, -y, -1)
+NH_DEVICE void nh_camera_dir(const float* f, const float* __restrict__ dist, int64_t row, int64_t col, float* dc) {
+    nh_pinhole_cam(f[0], f[1], f[2], f[3], row, col, dc);
+    if (dist) {
+        const float kp[4] = {dist[0], dist[1], dist[2], dist[3]};
+        float x, y;
+        nh_undistort(kp, dc[0], -dc[1], &x, &y);
+        dc[0] = x;
+        dc[1] = -y;
+    }
+}
+// one ray of the camera (f, dist)
+NH_DEVICE void nh_camera_ray(const float* f, const float* __restrict__ dist, const float* __restrict__ c2w, int ld, int64_t row,
+                             int64_t col, float* o, float* d) {
+    float dc[3];
+    nh_camera_dir(f, dist, row, col, dc);
+    nh_rotate_ray(dc, c2w, ld, o, d);
+}
+// one pin-hole ray
+NH_DEVICE void nh_pinhole_ray(const float* f, const float* __restrict__ c2w, int ld, int64_t row, int64_t col, float* o, float* d) {
+    nh_camera_ray(f, nullptr, c2w, ld, row, col, o, d);
 }
 NH_DEVICE void nh_pinhole_ray(int height, int width, float focal, const float* __restrict__ c2w, int ld, int64_t row,
                               int64_t col, float* o, float* d) {

@@ -25,7 +25,7 @@ import torch
 from . import _lib as L
 from . import backward_mode as BM
 from . import train_utils as TU
-from .cameras import Intrinsics, check_device_vector
+from .cameras import Distortion, Intrinsics, check_device_vector
 from .nerf_helpers import linspace01
 from .parallel import allreduce_gradients, shard_bounds
 
@@ -429,7 +429,7 @@ class TrainEngine:
         return self.loss
 
     def step_on_image(self, image, pose, height, width, focal_length, options, num_random_rays, lr=None, global_rays=None,
-                      pose_grad=None, intrinsics=None):
+                      pose_grad=None, intrinsics=None, distortion=None):
         """One whole iteration of the reference's loop body (train_nerf.py:210-270) on a resident training image:
         on-device selection of this rank's distinct pixels (ranks take disjoint slices of one permutation keyed by
         (seed, iteration)), their rays and targets, then `step`.  No host work besides launches.
@@ -442,15 +442,16 @@ class TrainEngine:
         updates the nets as usual (lr=0 freezes them); a pose parametrisation of one's own takes the gradient with
         torch.autograd.backward(pose_expr[:3, :4], pose_grad).  One rank only.
         intrinsics: None, or a cameras.Intrinsics on the engine's device: the rays are generated from its (fx, fy, cx, cy), read on
-        the device, and the step learns them -- see step_on_views.  `focal_length` must still be passed: it fixes the NDC constants."""
+        the device, and the step learns them -- see step_on_views.  `focal_length` must still be passed: it fixes the NDC constants.
+        distortion: None, or a cameras.Distortion on the engine's device -- see step_on_views."""
         if pose_grad is not None:
             self._no_pose_grad_across_ranks("pose_grad")
             self._check_pose_grads("pose_grad", pose_grad, (3, 4))
         return self._step_on_selection((height, width, focal_length, options), pose, image, False, num_random_rays, lr, global_rays,
-                                       pose_grad, None, intrinsics, False)
+                                       pose_grad, None, intrinsics, False, distortion)
 
     def step_on_views(self, images, poses, height, width, focal_length, options, num_random_rays, lr=None, global_rays=None,
-                      pose_grads=None, cameras=None, intrinsics=None):
+                      pose_grads=None, cameras=None, intrinsics=None, distortion=None):
         """step_on_image over a resident stack of views: this rank's rays are drawn from ALL of `images` (V, H, W, 3|4) with the
         rays of each generated from its own row of `poses` (V, >=3, 4) -- train_utils.select_training_rays_views --, then `step`.
         Same rank slicing (first = rank * n, or the shard_bounds slice of `global_rays`) over the permutation of V * H * W, same
@@ -468,38 +469,43 @@ class TrainEngine:
         ONE VJP call that fills the pose gradients (when asked) and intrinsics.g_intr -> cameras.backward() -> intrinsics.backward()
         -> the nets' Adam -> cameras.step() -> intrinsics.step().  Allowed with neither pose_grads nor cameras (it turns the ray
         gradient on).  `focal_length` must still be passed: it fixes the NDC constants, which do not follow the learned values.  One
-        rank only."""
+        rank only.
+        distortion: None, or a cameras.Distortion on the engine's device: the rays are undistorted under its (k1, k2, p1, p2), read on
+        the device, and the step learns them, with or without `intrinsics` and `cameras`: the same ONE VJP call also fills
+        distortion.g_dist, and distortion.step() follows intrinsics.step().  Alone it turns the ray gradient on.  One rank only."""
         return self._step_on_selection((height, width, focal_length, options), poses, images, True, num_random_rays, lr, global_rays,
-                                       pose_grads, cameras, intrinsics, False)
+                                       pose_grads, cameras, intrinsics, False, distortion)
 
-    def localize_on_image(self, image, pose, height, width, focal_length, options, num_random_rays, pose_grad=None, intrinsics=None):
+    def localize_on_image(self, image, pose, height, width, focal_length, options, num_random_rays, pose_grad=None, intrinsics=None,
+                          distortion=None):
         """step_on_image(pose_grad=...) for FROZEN nets (camera localisation against a trained field): the same selection, forward and
         pose VJP, with the render backward w.r.t. the rays alone (forward_backward(frozen=True)) and no optimizer step.  Nothing of
         the nets or their optimiser moves -- flat_params, exp_avg, exp_avg_sq, grad, the packed images and step_count are what they
         were, bit for bit --; the selection and the in-kernel draws are keyed by `localize_count`, which advances instead.
         pose_grad: a contiguous float32 (3, 4) tensor on the engine's device, overwritten with d(loss)/d(pose[:3, :4]).  One rank only.
         intrinsics: None, or a cameras.Intrinsics (see step_on_views): its values are learned against the frozen field; then
-        pose_grad may be None."""
+        pose_grad may be None.
+        distortion: None, or a cameras.Distortion (see step_on_views), learned against the frozen field; then pose_grad may be None."""
         self._no_pose_grad_across_ranks("localize_on_image")
-        if pose_grad is None and intrinsics is None:
-            raise RuntimeError("TrainEngine: localize_on_image needs pose_grad=... or intrinsics=...")
+        if pose_grad is None and intrinsics is None and distortion is None:
+            raise RuntimeError("TrainEngine: localize_on_image needs pose_grad=... or intrinsics=... (or distortion=...)")
         if pose_grad is not None:
             self._check_pose_grads("pose_grad", pose_grad, (3, 4))
         return self._step_on_selection((height, width, focal_length, options), pose, image, False, num_random_rays, None, None,
-                                       pose_grad, None, intrinsics, True)
+                                       pose_grad, None, intrinsics, True, distortion)
 
     def localize_on_views(self, images, poses, height, width, focal_length, options, num_random_rays, pose_grads=None, cameras=None,
-                          intrinsics=None):
+                          intrinsics=None, distortion=None):
         """step_on_views for FROZEN nets (see localize_on_image): with pose_grads (V, 3, 4) the step writes d(loss)/d(poses[v, :3, :4])
         of every view; with cameras=T (then poses must be None and pose_grads must not be given) the table composes its poses, takes
         the gradients in its own buffer, pulls them back to its twists (T.backward()) and steps them (T.step()) -- the nets stay put.
         intrinsics: None, or a cameras.Intrinsics (see step_on_views): its values are learned against the frozen field, alone or
-        together with the poses.  One rank only."""
+        together with the poses.  distortion: None, or a cameras.Distortion, in the same way.  One rank only."""
         self._no_pose_grad_across_ranks("localize_on_views")
-        if cameras is None and pose_grads is None and intrinsics is None:
-            raise RuntimeError("TrainEngine: localize_on_views needs pose_grads=..., cameras=... or intrinsics=...")
+        if cameras is None and pose_grads is None and intrinsics is None and distortion is None:
+            raise RuntimeError("TrainEngine: localize_on_views needs pose_grads=..., cameras=... or intrinsics=... (or distortion=...)")
         return self._step_on_selection((height, width, focal_length, options), poses, images, True, num_random_rays, None, None,
-                                       pose_grads, cameras, intrinsics, True)
+                                       pose_grads, cameras, intrinsics, True, distortion)
 
     def _resolve_cameras(self, poses, pose_grads, cameras):
         """(poses, pose_grads) of a step over views: the caller's, checked; or, with cameras=T, the table's composed poses and its own
@@ -521,15 +527,17 @@ class TrainEngine:
     def _check_pose_grads(self, name, g, shape):
         check_device_vector(g, shape, self.dev, "TrainEngine: " + name)
 
-    def _step_on_selection(self, scene, poses, images, views, num_random_rays, lr, global_rays, pose_grads, cameras, intrinsics, frozen):
+    def _step_on_selection(self, scene, poses, images, views, num_random_rays, lr, global_rays, pose_grads, cameras, intrinsics, frozen,
+                           distortion=None):
         """The step of step_on_image / step_on_views / localize_on_* behind their own argument checks.  scene: (height, width,
-        focal_length, options); views: whether `poses` / `images` carry a view axis.  In launch order: the checks of intrinsics=I, then
-        I.values(); cameras=T checked, T.poses() (_resolve_cameras); this rank's slice of the step's permutation; the selection; `step`
-        -- or, with any of pose_grads / cameras / intrinsics, forward_backward with the ray gradient, then on the main stream after
-        the two streams joined ONE VJP call that fills `pose_grads` (when asked) and I.g_intr, T.backward(), I.backward(),
-        optimizer_step, T.step(), I.step().  frozen (localize_on_*): the ray gradient alone and no optimizer_step; the selection and
-        the draws are keyed by localize_count, which advances.  Without intrinsics no intrinsics keyword is passed on: the step reaches
-        the entry points of the selection without them."""
+        focal_length, options); views: whether `poses` / `images` carry a view axis.  In launch order: the checks of intrinsics=I and
+        distortion=D, then I.values() and D.values(); cameras=T checked, T.poses() (_resolve_cameras); this rank's slice of the
+        step's permutation; the selection; `step` -- or, with any of pose_grads / cameras / intrinsics / distortion,
+        forward_backward with the ray gradient, then on the main stream after the two streams joined ONE VJP call that fills
+        `pose_grads` (when asked), I.g_intr and D.g_dist, T.backward(), I.backward(), optimizer_step, T.step(), I.step(), D.step().
+        frozen (localize_on_*): the ray gradient alone and no optimizer_step; the selection and the draws are keyed by
+        localize_count, which advances.  Without intrinsics (distortion) no intrinsics (distortion) keyword is passed on: the step
+        reaches the entry points of the selection without them."""
         height, width, focal_length, options = scene
         kw, vjp_kw = {}, {}
         if intrinsics is not None:
@@ -539,10 +547,21 @@ class TrainEngine:
             if intrinsics.dev != self.dev:
                 raise RuntimeError("TrainEngine: the intrinsics live on %s, the engine on %s" % (intrinsics.dev, self.dev))
             kw = dict(intrinsics=intrinsics.values())
+        if distortion is not None:
+            if not isinstance(distortion, Distortion):
+                raise RuntimeError("TrainEngine: distortion must be a cameras.Distortion (got %s)" % type(distortion).__name__)
+            self._no_pose_grad_across_ranks("distortion")
+            if distortion.dev != self.dev:
+                raise RuntimeError("TrainEngine: the distortion lives on %s, the engine on %s" % (distortion.dev, self.dev))
+            kw = dict(kw, distortion=distortion.values())
         if views:
             poses, pose_grads = self._resolve_cameras(poses, pose_grads, cameras)
-        if intrinsics is not None:   # (pose_grads None: the intrinsics alone -- no pose gradient is computed)
-            vjp_kw = dict(kw, out_intrinsics=intrinsics.g_intr, want_poses=pose_grads is not None)
+        if intrinsics is not None or distortion is not None:   # (pose_grads None: no pose gradient is computed)
+            vjp_kw = dict(kw, want_poses=pose_grads is not None)
+        if intrinsics is not None:
+            vjp_kw["out_intrinsics"] = intrinsics.g_intr
+        if distortion is not None:
+            vjp_kw.update(out_distortion=distortion.g_dist, distortion_mask=distortion.mask)
         if global_rays is None:
             n = int(num_random_rays)
             first = self.rank * n
@@ -553,7 +572,7 @@ class TrainEngine:
         count = self.localize_count if frozen else self.step_count
         with torch.no_grad():
             rays, target, used = select(height, width, focal_length, poses, images, n, options, seed=self.seed, step=count, first=first, **kw)
-        if pose_grads is None and intrinsics is None:
+        if pose_grads is None and intrinsics is None and distortion is None:
             return self.step(rays, target, ray_offset=first, lr=lr, global_rays=global_rays)
         self._ray_grad_bufs(n, own=True)
         self.forward_backward(rays, target, first, global_rays, None, self._ray_grad, frozen, count)
@@ -572,6 +591,8 @@ class TrainEngine:
             cameras.step()
         if intrinsics is not None:
             intrinsics.step()
+        if distortion is not None:
+            distortion.step()
         return self.loss
 
     @staticmethod

@@ -73,7 +73,7 @@ def png_bytes(img):
 
 
 def render_pose_rows(height, width, focal_length, pose, model_coarse, model_fine, options, encode_position_fn=None,
-                     encode_direction_fn=None, rank=0, world_size=1, mode="validation", intrinsics=None):
+                     encode_direction_fn=None, rank=0, world_size=1, mode="validation", intrinsics=None, distortion=None):
     """One pose of the render loop of eval_nerf.py (:158-176), ray-sharded (BASELINE config 5): rank `rank` of
     `world_size` generates and renders only ITS contiguous block of image rows (parallel.shard_bounds) -- rays are
     independent, so no rank ever needs another rank's data and there is no collective; the concatenation of the ranks'
@@ -81,13 +81,15 @@ def render_pose_rows(height, width, focal_length, pose, model_coarse, model_fine
     writer on rank 0).  Returns (outputs, (row_lo, row_hi)) with `outputs` the 6-tuple of run_one_iter_of_nerf shaped
     (rows, width, .).  The nets render under their current encoding window (FlexibleNeRFModel.set_encoding_window), if one is set.
     intrinsics: None, or a float32 device tensor (fx, fy, cx, cy), e.g. Intrinsics.values(): the rays are generated from it in
-    place of `focal_length` and the image centre (`focal_length` still fixes the NDC constants)."""
+    place of `focal_length` and the image centre (`focal_length` still fixes the NDC constants).
+    distortion: None, or a float32 device tensor (k1, k2, p1, p2), e.g. Distortion.values(): the rays are undistorted under it."""
     from .nerf_helpers import get_rays_at_pixels
     from .parallel import shard_bounds
     from .train_utils import run_one_iter_of_nerf
     lo, hi = shard_bounds(int(height), int(rank), int(world_size))
     pix = torch.arange(lo * int(width), hi * int(width), dtype=torch.int64, device=pose.device)
-    ro, rd = get_rays_at_pixels(height, width, focal_length, pose[:3, :4] if pose.shape[0] > 3 else pose, pix, intrinsics=intrinsics)
+    ro, rd = get_rays_at_pixels(height, width, focal_length, pose[:3, :4] if pose.shape[0] > 3 else pose, pix, intrinsics=intrinsics,
+                                distortion=distortion)
     shape = (hi - lo, int(width), 3)
     out = run_one_iter_of_nerf(height, width, focal_length, model_coarse, model_fine, ro.view(shape), rd.view(shape), options,
                                mode=mode, encode_position_fn=encode_position_fn, encode_direction_fn=encode_direction_fn)

@@ -158,12 +158,16 @@ class _RayBundle(torch.autograd.Function):
         return (_pose_grad_like(pose, g34),) + (None,) * 5
 
 
-def _ray_bundle_launch(height, width, focal, c2w, pix, shape, intr=None):
+def _ray_bundle_launch(height, width, focal, c2w, pix, shape, intr=None, dist=None):
     n = height * width if pix is None else pix.numel()
     ro = torch.empty(shape, dtype=torch.float32, device=c2w.device)
     rd = torch.empty_like(ro)
-    with launch_on(c2w, pix, ro, rd, intr) as st:
-        if intr is not None:  # (the device intrinsics in place of the focal and the image centre: nerfhip_ray_bundle_intr)
+    with launch_on(c2w, pix, ro, rd, intr, dist) as st:
+        if dist is not None:  # (lens distortion, over the device intrinsics or the scalar camera: nerfhip_ray_bundle_dist)
+            get_lib().ray_bundle_dist(height, width, focal, intr.data_ptr() if intr is not None else None, dist.data_ptr(),
+                                      c2w.data_ptr(), c2w.stride(0), pix.data_ptr() if pix is not None else None, n, ro.data_ptr(),
+                                      rd.data_ptr(), st)
+        elif intr is not None:  # (the device intrinsics in place of the focal and the image centre: nerfhip_ray_bundle_intr)
             get_lib().ray_bundle_intr(height, width, intr.data_ptr(), c2w.data_ptr(), c2w.stride(0),
                                       pix.data_ptr() if pix is not None else None, n, ro.data_ptr(), rd.data_ptr(), st)
         else:
@@ -181,6 +185,26 @@ def _intr_vector(intrinsics, dev, what=None):
     return intrinsics.detach().reshape(4).contiguous()
 
 
+def _dist_vector(distortion, dev, what=None):
+    """The distortion coefficients (k1, k2, p1, p2) as the kernels read them: four contiguous float32 values on `dev`, the poses'
+    device (`what`: the calling function, leading the message)."""
+    if (not isinstance(distortion, torch.Tensor) or distortion.dtype != torch.float32 or distortion.numel() != 4
+            or distortion.device != dev):
+        raise RuntimeError("%sdistortion must be a float32 tensor of 4 (k1, k2, p1, p2) on %s" % (what + ": " if what else "", dev))
+    return distortion.detach().reshape(4).contiguous()
+
+
+def _bundle_distortion(distortion, pose, c2w):
+    """The `distortion` argument of the bundle forms (forward only): _dist_vector on the pose's device."""
+    if distortion is None:
+        return None
+    if _wants_pose_grad(pose):
+        raise RuntimeError("get_ray_bundle(distortion=...) is forward only: the bundle form has no VJP under lens distortion, so a "
+                           "pose that requires grad cannot be combined with it (select_training_rays(distortion=...) carries "
+                           "the gradients)")
+    return _dist_vector(distortion, c2w.device)
+
+
 def _bundle_intrinsics(intrinsics, pose, c2w):
     """The `intrinsics` argument of the bundle forms (forward only): _intr_vector on the pose's device."""
     if intrinsics is None:
@@ -196,33 +220,38 @@ def _wants_pose_grad(pose):
     return torch.is_grad_enabled() and isinstance(pose, torch.Tensor) and pose.requires_grad
 
 
-def get_ray_bundle(height: int, width: int, focal_length, tform_cam2world: torch.Tensor, intrinsics=None):
+def get_ray_bundle(height: int, width: int, focal_length, tform_cam2world: torch.Tensor, intrinsics=None, distortion=None):
     """nerf/nerf_helpers.py:67-110.  Returns (ray_origins, ray_directions), each (height, width, 3); directions are
     not normalised.  Differentiable w.r.t. tform_cam2world (its [:3, :4] entries), as the reference is.
     intrinsics: None, or a float32 device tensor (fx, fy, cx, cy) that replaces `focal_length` and the image centre (evaluation
-    under learned intrinsics); forward only -- together with a pose that requires grad it raises."""
+    under learned intrinsics); forward only -- together with a pose that requires grad it raises.
+    distortion: None, or a float32 device tensor (k1, k2, p1, p2), the lens distortion the directions are undistorted under
+    (include/nerfhip.h; with or without `intrinsics`); forward only in the same way."""
     c2w = _dev32(tform_cam2world, "tform_cam2world")
     if c2w.dim() != 2 or c2w.shape[0] < 3 or c2w.shape[1] < 4:
         raise RuntimeError("tform_cam2world must be at least 3x4")
     focal = float(focal_length)
     intr = _bundle_intrinsics(intrinsics, tform_cam2world, c2w)
-    if intr is not None:
-        return _ray_bundle_launch(height, width, focal, c2w, None, (height, width, 3), intr)
+    dist = _bundle_distortion(distortion, tform_cam2world, c2w)
+    if intr is not None or dist is not None:
+        return _ray_bundle_launch(height, width, focal, c2w, None, (height, width, 3), intr, dist)
     if _wants_pose_grad(tform_cam2world):
         return _RayBundle.apply(tform_cam2world, height, width, focal, None, (height, width, 3))
     return _ray_bundle_launch(height, width, focal, c2w, None, (height, width, 3))
 
 
-def get_rays_at_pixels(height: int, width: int, focal_length, tform_cam2world: torch.Tensor, pixels: torch.Tensor, intrinsics=None):
+def get_rays_at_pixels(height: int, width: int, focal_length, tform_cam2world: torch.Tensor, pixels: torch.Tensor, intrinsics=None,
+                       distortion=None):
     """Rays of selected pixels only: `pixels` are int64 linear ids row*width+col.  Equivalent to
     get_ray_bundle(...)[...].reshape(-1, 3)[pixels] without generating the whole image (differentiable w.r.t. the pose
-    in the same way; `intrinsics` as for get_ray_bundle)."""
+    in the same way; `intrinsics` and `distortion` as for get_ray_bundle)."""
     c2w = _dev32(tform_cam2world, "tform_cam2world")
     pix = pixels.to(device=c2w.device, dtype=torch.int64).contiguous()
     n = pix.numel()
     intr = _bundle_intrinsics(intrinsics, tform_cam2world, c2w)
-    if intr is not None:
-        return _ray_bundle_launch(height, width, float(focal_length), c2w, pix, (n, 3), intr)
+    dist = _bundle_distortion(distortion, tform_cam2world, c2w)
+    if intr is not None or dist is not None:
+        return _ray_bundle_launch(height, width, float(focal_length), c2w, pix, (n, 3), intr, dist)
     if _wants_pose_grad(tform_cam2world):
         return _RayBundle.apply(tform_cam2world, height, width, float(focal_length), pix, (n, 3))
     return _ray_bundle_launch(height, width, float(focal_length), c2w, pix, (n, 3))

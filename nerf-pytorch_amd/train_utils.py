@@ -20,7 +20,8 @@ import torch
 from . import _lib as L
 from . import backward_mode as BM
 from .models import FlexibleNeRFModel
-from .nerf_helpers import EmbeddingFunction, _intr_vector, get_minibatches, linspace01, ndc_rays, sample_pdf_2 as sample_pdf
+from .nerf_helpers import (EmbeddingFunction, _dist_vector, _intr_vector, get_minibatches, linspace01, ndc_rays,
+                           sample_pdf_2 as sample_pdf)
 from .volume_rendering_utils import volume_render_radiance_field
 
 
@@ -380,79 +381,98 @@ def _pose_table(poses, views):
     return p if ok else p.contiguous()
 
 
-# (intrinsics?, a view axis?) -> the selection's entry point, its VJP's, the VJP's tmp-size function.  (The single view without
-# intrinsics keeps its own VJP: two launches where the views form at V = 1 issues three.)
-_SELECT_ENTRY = {(False, False): ("select_rays", "select_rays_bwd", "pose_grad_tmp_bytes"),
-                 (False, True): ("select_rays_views", "select_rays_views_bwd", "pose_grad_views_tmp_bytes"),
-                 (True, False): ("select_rays_views_intr", "select_rays_views_intr_bwd", "intr_grad_views_tmp_bytes"),
-                 (True, True): ("select_rays_views_intr", "select_rays_views_intr_bwd", "intr_grad_views_tmp_bytes")}
+# (the camera model: 0 the scalar pin-hole, 1 device intrinsics, 2 lens distortion; a view axis?) -> the selection's entry point, its
+# VJP's, the VJP's tmp-size function.  (The single view without intrinsics keeps its own VJP: two launches where the views form at
+# V = 1 issues three.)
+_SELECT_ENTRY = {(0, False): ("select_rays", "select_rays_bwd", "pose_grad_tmp_bytes"),
+                 (0, True): ("select_rays_views", "select_rays_views_bwd", "pose_grad_views_tmp_bytes"),
+                 (1, False): ("select_rays_views_intr", "select_rays_views_intr_bwd", "intr_grad_views_tmp_bytes"),
+                 (1, True): ("select_rays_views_intr", "select_rays_views_intr_bwd", "intr_grad_views_tmp_bytes"),
+                 (2, False): ("select_rays_views_dist", "select_rays_views_dist_bwd", "dist_grad_views_tmp_bytes"),
+                 (2, True): ("select_rays_views_dist", "select_rays_views_dist_bwd", "dist_grad_views_tmp_bytes")}
 
 
-def _table_args(poses, views, intr=None):
-    """The pose arguments of the entry points of _SELECT_ENTRY: (pointer, row stride) of the single pose, or -- with a view axis or
-    `intr`, whose pointer then leads -- the table (num_views, pointer, view stride, row stride); a single pose is the table of one view."""
-    if intr is None and not views:
+def _camera_model(intr, dist):
+    return 2 if dist is not None else (1 if intr is not None else 0)
+
+
+def _table_args(poses, views, intr=None, dist=None):
+    """The pose arguments of the entry points of _SELECT_ENTRY: (pointer, row stride) of the single pose, or -- with a view axis,
+    `intr` or `dist`, whose pointers then lead (intr, or intr | NULL and dist) -- the table (num_views, pointer, view stride, row
+    stride); a single pose is the table of one view."""
+    if intr is None and dist is None and not views:
         return poses.data_ptr(), poses.stride(-2)
     head = () if intr is None else (intr.data_ptr(),)
+    if dist is not None:
+        head = (intr.data_ptr() if intr is not None else None, dist.data_ptr())
     if views:
         return head + (poses.shape[0], poses.data_ptr(), poses.stride(0), poses.stride(1))
     return head + (1, poses.data_ptr(), 0, poses.stride(-2))
 
 
-def _select_launch(cfg, poses, images, select_inds, n, views, intr=None):
+def _select_launch(cfg, poses, images, select_inds, n, views, intr=None, dist=None):
     """nerfhip_select_rays (`poses` one pose, `images` one image) or, with a view axis, nerfhip_select_rays_views; with `intr` (the
-    device intrinsics) nerfhip_select_rays_views_intr in both cases."""
+    device intrinsics) nerfhip_select_rays_views_intr in both cases; with `dist` (the device distortion coefficients, with or
+    without `intr`) nerfhip_select_rays_views_dist."""
     dev = poses.device
     rays = torch.empty((n, 11 if cfg.use_viewdirs else 8), dtype=torch.float32, device=dev)
     target = torch.empty((n, cfg.channels), dtype=torch.float32, device=dev) if images is not None else None
     used = torch.empty((n,), dtype=torch.int64, device=dev)
-    fn = getattr(L.get_lib(), _SELECT_ENTRY[intr is not None, bool(views)][0])
-    with L.launch_on(poses, images, select_inds, rays, intr) as st:
-        fn(C.byref(cfg), *_table_args(poses, views, intr), images.data_ptr() if images is not None else None,
+    fn = getattr(L.get_lib(), _SELECT_ENTRY[_camera_model(intr, dist), bool(views)][0])
+    with L.launch_on(poses, images, select_inds, rays, intr, dist) as st:
+        fn(C.byref(cfg), *_table_args(poses, views, intr, dist), images.data_ptr() if images is not None else None,
            select_inds.data_ptr() if select_inds is not None else None, n, rays.data_ptr(),
            target.data_ptr() if target is not None else None, used.data_ptr(), st)
     return rays, target, used
 
 
-def _select_vjp(cfg, intr, poses, used, g_rays, g_rays_2, views, want_poses=True, want_intr=True, out=None, out_intr=None):
-    """The VJP entry point of _SELECT_ENTRY on the current stream: (d(loss)/d(pose[:3, :4]) (3 x 4 float32; with a view axis V x 3 x 4),
-    d(loss)/d(intr) (4 float32; None without `intr`)) of the rays the select call with `cfg` / `poses` / `intr` made at the select
-    indices `used`, from d(loss)/d(rays) rows g_rays (+ g_rays_2, added row by row).  With `intr` an output that is not wanted is
-    None and is not computed."""
+def _select_vjp(cfg, intr, poses, used, g_rays, g_rays_2, views, want_poses=True, want_intr=True, out=None, out_intr=None, dist=None,
+                want_dist=True, out_dist=None, dist_mask=None):
+    """The VJP entry point of _SELECT_ENTRY on the current stream: the triple (d(loss)/d(pose[:3, :4]) (3 x 4 float32; with a view
+    axis V x 3 x 4), d(loss)/d(intr) (4 float32; None without `intr`), d(loss)/d(dist) (4 float32; None without `dist`)) of the rays
+    the select call with `cfg` / `poses` / `intr` / `dist` made at the select indices `used`, from d(loss)/d(rays) rows g_rays
+    (+ g_rays_2, added row by row).  With `intr` or `dist` an output that is not wanted is None and is not computed.  dist_mask: None,
+    or 4 bytes on the device: a coefficient whose byte is 0 gets an exact zero."""
     lib = L.get_lib()
-    _, fn, tmp_fn = _SELECT_ENTRY[intr is not None, bool(views)]
+    model = _camera_model(intr, dist)
+    _, fn, tmp_fn = _SELECT_ENTRY[model, bool(views)]
     n, nv = used.numel(), poses.shape[0] if views else 1
-    tb = getattr(lib, tmp_fn)(*((n, nv) if views or intr is not None else (n,)))
+    tb = getattr(lib, tmp_fn)(*((n, nv) if views or model else (n,)))
     if tb < 0:
         raise RuntimeError("select_training_rays_views: %d rays over %d views is outside the kernel's limits" % (n, nv))
     mk = lambda *shape: torch.empty(shape, dtype=torch.float32, device=poses.device)  # noqa: E731
     tmp = mk(tb // 4 + 1)
-    gp = gi = None
-    if intr is None or want_poses:
+    gp = gi = gd = None
+    if not model or want_poses:
         gp = out if out is not None else mk(*((nv, 3, 4) if views else (3, 4)))
     if intr is not None and want_intr:
         gi = out_intr if out_intr is not None else mk(4)
-    outs = (gp.data_ptr(),) if intr is None else (gp.data_ptr() if gp is not None else None, gi.data_ptr() if gi is not None else None)
-    with L.launch_on(poses, used, g_rays, g_rays_2, tmp, gp, gi, intr) as st:
-        getattr(lib, fn)(C.byref(cfg), *_table_args(poses, views, intr), used.data_ptr(), n, g_rays.data_ptr(),
+    if dist is not None and want_dist:
+        gd = out_dist if out_dist is not None else mk(4)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    outs = (ptr(gp), ptr(gi), ptr(gd), ptr(dist_mask))[:{0: 1, 1: 2, 2: 4}[model]]   # (what the model's VJP entry point takes)
+    with L.launch_on(poses, used, g_rays, g_rays_2, tmp, gp, gi, gd, intr, dist, dist_mask) as st:
+        getattr(lib, fn)(C.byref(cfg), *_table_args(poses, views, intr, dist), used.data_ptr(), n, g_rays.data_ptr(),
                          g_rays_2.data_ptr() if g_rays_2 is not None else None, g_rays.stride(0), tmp.data_ptr(), tb, *outs, st)
-    return gp, gi
+    return gp, gi, gd
 
 
 class _SelectRays(torch.autograd.Function):
     """select_training_rays / select_training_rays_views with the pose VJP (nerfhip_select_rays_bwd / nerfhip_select_rays_views_bwd):
-    the gradient flows from the rays to the [:3, :4] entries of the pose (of every pose of the table) and, with `intrinsics`, to
-    the four intrinsics (nerfhip_select_rays_views_intr_bwd: one call for both); targets and select indices carry none.  The
-    forward issues exactly the launch of the plain call."""
+    the gradient flows from the rays to the [:3, :4] entries of the pose (of every pose of the table), with `intrinsics` to the four
+    intrinsics and with `distortion` to the four coefficients (nerfhip_select_rays_views_intr_bwd / _dist_bwd: one call for all of
+    them); targets and select indices carry none.  The forward issues exactly the launch of the plain call."""
 
     @staticmethod
-    def forward(ctx, poses, intrinsics, cfg, images, select_inds, n, views):
+    def forward(ctx, poses, intrinsics, distortion, cfg, images, select_inds, n, views):
         p = _pose_table(poses, views)
         k = None if intrinsics is None else _intr_vector(intrinsics, p.device, "select_training_rays")
-        rays, target, used = _select_launch(cfg, p, images, select_inds, n, views, k)
-        ctx.keep = (cfg, p, used, views, k)
+        d = None if distortion is None else _dist_vector(distortion, p.device, "select_training_rays")
+        rays, target, used = _select_launch(cfg, p, images, select_inds, n, views, k, d)
+        ctx.keep = (cfg, p, used, views, k, d)
         ctx.poses_shape = (poses.shape, poses.dtype)
         ctx.intr_shape = None if intrinsics is None else intrinsics.shape
+        ctx.dist_shape = None if distortion is None else distortion.shape
         ctx.mark_non_differentiable(*[t for t in (target, used) if t is not None])
         ctx.set_materialize_grads(False)
         return rays, target, used
@@ -460,31 +480,41 @@ class _SelectRays(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_rays, _g_target, _g_used):
         if g_rays is None:
-            return (None,) * 7
-        cfg, p, used, views, k = ctx.keep
+            return (None,) * 8
+        cfg, p, used, views, k, d = ctx.keep
         g_rays = g_rays.contiguous().float()
-        g34, gi = _select_vjp(cfg, k, p, used, g_rays, None, views, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        g34, gi, gd = _select_vjp(cfg, k, p, used, g_rays, None, views, ctx.needs_input_grad[0], ctx.needs_input_grad[1], dist=d,
+                                  want_dist=ctx.needs_input_grad[2])
         gi = gi.reshape(ctx.intr_shape) if gi is not None else None
+        gd = gd.reshape(ctx.dist_shape) if gd is not None else None
         g = None
         if g34 is not None:
             shape, dtype = ctx.poses_shape
             g = torch.zeros(shape, dtype=dtype, device=p.device)
             g[..., :3, :4] = g34.to(dtype)
-        return g, gi, None, None, None, None, None
+        return g, gi, gd, None, None, None, None, None
 
 
-def _select(cfg, poses, images, select_inds, n, views, intrinsics=None):
+def _select(cfg, poses, images, select_inds, n, views, intrinsics=None, distortion=None):
     if images is not None:
         images = images.detach().float().contiguous()
     if select_inds is not None:
         select_inds = torch.as_tensor(select_inds, dtype=torch.int64, device=poses.device).contiguous()
-    if torch.is_grad_enabled() and (poses.requires_grad or (intrinsics is not None and intrinsics.requires_grad)):
-        return _SelectRays.apply(poses, intrinsics, cfg, images, select_inds, n, views)
+    if torch.is_grad_enabled() and (poses.requires_grad or (intrinsics is not None and intrinsics.requires_grad)
+                                    or (isinstance(distortion, torch.Tensor) and distortion.requires_grad)):
+        return _SelectRays.apply(poses, intrinsics, distortion, cfg, images, select_inds, n, views)
     k = None if intrinsics is None else _intr_vector(intrinsics, poses.device, "select_training_rays")
-    return _select_launch(cfg, _pose_table(poses, views), images, select_inds, n, views, k)
+    d = None if distortion is None else _dist_vector(distortion, poses.device, "select_training_rays")
+    return _select_launch(cfg, _pose_table(poses, views), images, select_inds, n, views, k, d)
 
 
-def _select_bwd(what, cfg, poses, select_inds, g_rays, g_rays_2, out, views, intrinsics=None, out_intrinsics=None, want_poses=True):
+def _check_out4(what, name, t, dev):
+    if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (4,) or not t.is_contiguous() or t.device != dev):
+        raise RuntimeError("%s: %s must be a contiguous float32 (4) tensor on %s" % (what, name, dev))
+
+
+def _select_bwd(what, cfg, poses, select_inds, g_rays, g_rays_2, out, views, intrinsics=None, out_intrinsics=None, want_poses=True,
+                distortion=None, out_distortion=None, distortion_mask=None):
     """The checks of g_rays / g_rays_2 / out (`what`: the public function, for the messages), then the VJP."""
     for name, g in (("g_rays", g_rays), ("g_rays_2", g_rays_2)):
         if g is not None and (g.dtype != torch.float32 or g.dim() != 2 or g.stride(1) != 1
@@ -497,21 +527,30 @@ def _select_bwd(what, cfg, poses, select_inds, g_rays, g_rays_2, out, views, int
     if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous()):
         raise RuntimeError("%s: out must be a contiguous float32 (%s) tensor" % (what, ", ".join(str(d) for d in shape)))
     used = torch.as_tensor(select_inds, dtype=torch.int64, device=poses.device).contiguous()
-    if not want_poses and (intrinsics is None or out is not None):
-        raise RuntimeError("%s: want_poses=False asks for the intrinsics' gradient alone: it needs intrinsics and excludes out" % what)
-    if intrinsics is None:
-        if out_intrinsics is not None:
-            raise RuntimeError("%s: out_intrinsics needs intrinsics" % what)
-        return _select_vjp(cfg, None, p, used, g_rays, g_rays_2, views, out=out)[0]
-    if out_intrinsics is not None and (out_intrinsics.dtype != torch.float32 or tuple(out_intrinsics.shape) != (4,)
-                                       or not out_intrinsics.is_contiguous() or out_intrinsics.device != p.device):
-        raise RuntimeError("%s: out_intrinsics must be a contiguous float32 (4) tensor on %s" % (what, p.device))
-    return _select_vjp(cfg, _intr_vector(intrinsics, p.device, what), p, used, g_rays, g_rays_2, views, want_poses=want_poses, out=out,
-                       out_intr=out_intrinsics)
+    if not want_poses and ((intrinsics is None and distortion is None) or out is not None):
+        raise RuntimeError("%s: want_poses=False asks for the intrinsics' (or the distortion's) gradient alone: it needs intrinsics "
+                           "or distortion and excludes out" % what)
+    if intrinsics is None and out_intrinsics is not None:
+        raise RuntimeError("%s: out_intrinsics needs intrinsics" % what)
+    if distortion is None:
+        if out_distortion is not None or distortion_mask is not None:
+            raise RuntimeError("%s: out_distortion and distortion_mask need distortion" % what)
+        if intrinsics is None:
+            return _select_vjp(cfg, None, p, used, g_rays, g_rays_2, views, out=out)[0]
+    _check_out4(what, "out_intrinsics", out_intrinsics, p.device)
+    k = None if intrinsics is None else _intr_vector(intrinsics, p.device, what)
+    if distortion is None:
+        return _select_vjp(cfg, k, p, used, g_rays, g_rays_2, views, want_poses=want_poses, out=out, out_intr=out_intrinsics)[:2]
+    _check_out4(what, "out_distortion", out_distortion, p.device)
+    if distortion_mask is not None and (not isinstance(distortion_mask, torch.Tensor) or distortion_mask.dtype != torch.uint8
+                                        or tuple(distortion_mask.shape) != (4,) or distortion_mask.device != p.device):
+        raise RuntimeError("%s: distortion_mask must be a uint8 (4) tensor on %s" % (what, p.device))
+    return _select_vjp(cfg, k, p, used, g_rays, g_rays_2, views, want_poses=want_poses, out=out, out_intr=out_intrinsics,
+                       dist=_dist_vector(distortion, p.device, what), out_dist=out_distortion, dist_mask=distortion_mask)
 
 
 def select_training_rays(height, width, focal_length, pose, image, num_random_rays, options, select_inds=None, seed=0,
-                         step=0, first=0, intrinsics=None):
+                         step=0, first=0, intrinsics=None, distortion=None):
     """The image branch of the training loop (train_nerf.py:210-227) fused with run_one_iter_of_nerf's ray packing
     (train_utils.py:143-168), in ONE launch: draws `num_random_rays` distinct pixels on the device (or takes the
     reference's `select_inds`, the flat indices it draws with np.random.choice), generates only those rays from `pose`
@@ -522,28 +561,35 @@ def select_training_rays(height, width, focal_length, pose, image, num_random_ra
     intrinsics: None, or a float32 device tensor (fx, fy, cx, cy) in pixels that replaces `focal_length` and the image centre in
     the pin-hole direction ((col - cx) / fx, -(row - cy) / fy, -1) -- read on the device, so a learned focal is never read back
     to the host.  `focal_length` still fixes the NDC constants, which do not follow `intrinsics`.  With `intrinsics` requiring
-    grad the rays are differentiable w.r.t. it as well."""
+    grad the rays are differentiable w.r.t. it as well.
+    distortion: None, or a float32 device tensor (k1, k2, p1, p2): the lens distortion of the capture (COLMAP's OPENCV model,
+    include/nerfhip.h); the pin-hole direction is undistorted under it on the device, with or without `intrinsics`.  With
+    `distortion` requiring grad the rays are differentiable w.r.t. it as well (the same node, the same one VJP call)."""
     channels = 3 if image is None else image.shape[-1]
     cfg = _select_cfg(height, width, focal_length, options, channels, seed, step, first)
-    return _select(cfg, pose, image, select_inds, int(num_random_rays), False, intrinsics)
+    return _select(cfg, pose, image, select_inds, int(num_random_rays), False, intrinsics, distortion)
 
 
 def select_training_rays_bwd(height, width, focal_length, pose, select_inds, g_rays, options, g_rays_2=None, out=None,
-                             intrinsics=None, out_intrinsics=None, want_poses=True):
+                             intrinsics=None, out_intrinsics=None, want_poses=True, distortion=None, out_distortion=None,
+                             distortion_mask=None):
     """The pose VJP of select_training_rays without autograd: d(loss)/d(pose[:3, :4]) (3 x 4 float32 device tensor; written
     into `out` when given) of the rays select_training_rays(height, width, focal_length, pose, ..., options) made at
     `select_inds` (its third output), from d(loss)/d(rays) rows `g_rays` (+ `g_rays_2`, added row by row: e.g. the coarse and
     the fine net's parts that TrainEngine.forward_backward(ray_grad=...) leaves).  Enqueued on the current stream.
     With `intrinsics` (those of the forward) the result is the pair (d(loss)/d(pose[:3, :4]), d(loss)/d(intrinsics) (4 float32;
     written into `out_intrinsics` when given)), from one call; want_poses=False (with `intrinsics` only) leaves the pose gradient
-    out -- it is not computed, and the first entry of the pair is None."""
+    out -- it is not computed, and the first entry of the pair is None.
+    With `distortion` (that of the forward) the result is the triple (pose gradient, d(loss)/d(intrinsics) -- None without
+    `intrinsics` --, d(loss)/d(distortion) (4 float32; written into `out_distortion` when given)), from one call; distortion_mask:
+    None, or a uint8 device tensor of 4: a coefficient whose byte is 0 gets an exact zero."""
     cfg = _select_cfg(height, width, focal_length, options, 3, 0, 0, 0)
     return _select_bwd("select_training_rays_bwd", cfg, pose, select_inds, g_rays, g_rays_2, out, False, intrinsics, out_intrinsics,
-                       want_poses)
+                       want_poses, distortion, out_distortion, distortion_mask)
 
 
 def select_training_rays_views(height, width, focal_length, poses, images, num_random_rays, options, select_inds=None, seed=0,
-                               step=0, first=0, intrinsics=None):
+                               step=0, first=0, intrinsics=None, distortion=None):
     """select_training_rays over a stack of views, in ONE launch: `num_random_rays` distinct (view, pixel) pairs drawn from all of
     `images` (V, H, W, 3|4; or None) with the rays of each generated from its own row of `poses` (V, >=3, 4; device; a strided
     slice of a larger table is read in place).  Intrinsics and options are shared by the views.  The indices (third output, and
@@ -551,27 +597,29 @@ def select_training_rays_views(height, width, focal_length, poses, images, num_r
     select_inds) as select_training_rays does; every row equals the row that call makes for (poses[v], images[v], [k]).
     With `poses` requiring grad the rays are differentiable w.r.t. them: the backward runs the per-view pose VJP
     (select_training_rays_views_bwd), so every view with a ray in the batch gets its gradient from one step.
-    intrinsics: as for select_training_rays (one (fx, fy, cx, cy) for all views)."""
+    intrinsics, distortion: as for select_training_rays (one (fx, fy, cx, cy) and one (k1, k2, p1, p2) for all views)."""
     channels = 3 if images is None else images.shape[-1]
     cfg = _select_cfg(height, width, focal_length, options, channels, seed, step, first)
     if images is not None and (images.dim() != 4 or images.shape[0] != poses.shape[0]
                                or tuple(images.shape[1:3]) != (cfg.height, cfg.width)):
         raise RuntimeError("select_training_rays_views: images must be (V, H, W, C) with V = %d, H = %d, W = %d (got %s)"
                            % (poses.shape[0], cfg.height, cfg.width, tuple(images.shape)))
-    return _select(cfg, poses, images, select_inds, int(num_random_rays), True, intrinsics)
+    return _select(cfg, poses, images, select_inds, int(num_random_rays), True, intrinsics, distortion)
 
 
 def select_training_rays_views_bwd(height, width, focal_length, poses, select_inds, g_rays, options, g_rays_2=None, out=None,
-                                   intrinsics=None, out_intrinsics=None, want_poses=True):
+                                   intrinsics=None, out_intrinsics=None, want_poses=True, distortion=None, out_distortion=None,
+                                   distortion_mask=None):
     """The per-view pose VJP of select_training_rays_views without autograd: d(loss)/d(poses[:, :3, :4]) (V x 3 x 4 float32 device
     tensor; written into `out` when given) from d(loss)/d(rays) rows `g_rays` (+ `g_rays_2`, added row by row) at the global
     `select_inds` of the forward.  Entry v is bit-identical to select_training_rays_bwd on the rays of view v alone (in batch
     order); a view without a ray gets zeros.  Enqueued on the current stream; no host synchronisation.
     With `intrinsics` the result is the pair (pose gradients, d(loss)/d(intrinsics)), as for select_training_rays_bwd: the
-    intrinsics' gradient is one fixed-order sum over all rays of the batch, whatever their view; want_poses=False as there."""
+    intrinsics' gradient is one fixed-order sum over all rays of the batch, whatever their view; want_poses=False as there.
+    With `distortion` the result is the triple (pose gradients, d(loss)/d(intrinsics) or None, d(loss)/d(distortion)), as there."""
     cfg = _select_cfg(height, width, focal_length, options, 3, 0, 0, 0)
     return _select_bwd("select_training_rays_views_bwd", cfg, poses, select_inds, g_rays, g_rays_2, out, True, intrinsics,
-                       out_intrinsics, want_poses)
+                       out_intrinsics, want_poses, distortion, out_distortion, distortion_mask)
 
 
 def select_cached_training_rays(cache_dict, num_random_rays, options, select_inds=None, seed=0, step=0, first=0):

@@ -1,0 +1,532 @@
+"""GPU suite (-m gpu): the device-resident lens distortion -- the kernels of tests/distortion_cases.py on the product library, the
+drop-in autograd node (select_training_rays_views(distortion=...)), cameras.Distortion and TrainEngine.step_on_views /
+localize_on_views (distortion=...), the kernels one step of each new form launches (tests/step_launches_distortion.json, recorded by
+this module:
+
+    python tests/test_gpu_distortion.py --record tests/step_launches_distortion.json
+
+) and a radial coefficient that starts at zero recovered against frozen nets."""
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import conftest  # noqa: F401 (first: run as a script, --record, this is what puts the package and the oracle on sys.path)
+import distortion_cases as DC
+import pose_vjp as P
+import test_gpu_localize as TL
+import test_gpu_step_forms as SF
+import test_gpu_views as TV
+
+pytestmark = pytest.mark.gpu
+
+FIXTURE = os.path.join(conftest.ROOT, "tests", "step_launches_distortion.json")
+
+
+# ---- the kernels ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("ndc", [False, True])
+@pytest.mark.parametrize("view", [False, True])
+@pytest.mark.parametrize("kappa", ["barrel", "pincushion"])
+def test_selection_rows_against_fp64(gpu, ndc, view, kappa):
+    DC.case_forward_fp64(gpu, ndc, view, kappa)
+
+
+def test_selection_rows_against_fp64_on_the_scalar_camera(gpu):
+    DC.case_forward_fp64(gpu, True, True, "pincushion", with_intr=False)
+
+
+def test_ray_bundle_under_distortion(gpu):
+    DC.case_bundle(gpu)
+
+
+@pytest.mark.parametrize("n", [1, 63, 256, 257, 700])
+@pytest.mark.parametrize("ndc", [False, True])
+@pytest.mark.parametrize("view", [False, True])
+@pytest.mark.parametrize("two,stride", [(False, 11), (True, 16), (True, 11), (False, 16)])
+def test_vjp_against_fp64(gpu, n, ndc, view, two, stride):
+    DC.case_vjp(gpu, n, ndc, view, two, stride)
+
+
+@pytest.mark.parametrize("ndc", [False, True])
+@pytest.mark.parametrize("view", [False, True])
+def test_vjp_against_fp64_4096_rays_over_100_views(gpu, ndc, view):
+    DC.case_vjp(gpu, 4096, ndc, view, True, 11, big=True, kappa="barrel")
+
+
+@pytest.mark.parametrize("ndc", [False, True])
+@pytest.mark.parametrize("view", [False, True])
+@pytest.mark.parametrize("layout", ["4x4", "embedded"])
+def test_zero_distortion_selects_the_rows_of_the_call_without_it(gpu, ndc, view, layout):
+    DC.case_zero_selection_bits(gpu, ndc, view, layout)
+
+
+@pytest.mark.parametrize("n", [1, 63, 256, 257, 700])
+@pytest.mark.parametrize("ndc", [False, True])
+@pytest.mark.parametrize("view", [False, True])
+def test_zero_distortion_gives_the_existing_gradients_bits(gpu, n, ndc, view):
+    DC.case_zero_vjp_bits(gpu, n, ndc, view)
+
+
+@pytest.mark.parametrize("mask", DC.MASKS, ids=["".join(map(str, m)) for m in DC.MASKS])
+def test_masked_coefficients_get_exact_zeros_and_never_move(gpu, mask):
+    DC.case_mask(gpu, mask)
+
+
+def test_vjp_of_no_rays_an_empty_view_and_dropped_indices(gpu):
+    DC.case_vjp_edges(gpu)
+
+
+def test_entry_points_reject_bad_arguments(gpu):
+    DC.case_refusals(gpu)
+
+
+# ---- drop-in autograd ---------------------------------------------------------------------------------------------------------------
+def _kappa(dev, k=DC.KAPPA_BARREL):
+    return torch.from_numpy(np.ascontiguousarray(k, np.float32)).to(dev)
+
+
+def test_dropin_distortion_gradient_is_the_kernel_and_none_is_the_existing_path():
+    """select_training_rays_views(distortion=t): with t (and with the intrinsics and the poses) requiring grad, backward() leaves the
+    bits of the _bwd call from ONE node; the forward is the plain launch; distortion=None is the existing node and function; zero
+    coefficients give the rows of the call without them; the bundle forms and render_pose_rows take the distortion forward only."""
+    import nerf_pytorch_amd as N
+    dev = TV._dev()
+    mc, mf, H, W, focal, pose0 = TV._lego(dev)
+    V, n = 3, 700
+    g = torch.Generator().manual_seed(8)
+    imgs = torch.rand(V, H, W, 3, generator=g).to(dev)
+    gr = torch.randn(n, 11, generator=g).to(dev)
+    opts = N.make_options(64, 64)
+    poses = TV._views(pose0, dev, V)
+    intr = torch.tensor([focal * 1.03, focal * 0.98, W * 0.5 + 1.25, H * 0.5 - 0.75], dtype=torch.float32, device=dev)
+    kap = _kappa(dev)
+    plain = N.select_training_rays_views(H, W, focal, poses, imgs, n, opts, seed=4, step=1, intrinsics=intr, distortion=kap)
+    assert plain[0].grad_fn is None
+    want_p, want_i, want_d = N.select_training_rays_views_bwd(H, W, focal, poses, plain[2], gr, opts, intrinsics=intr, distortion=kap)
+    assert tuple(want_p.shape) == (V, 3, 4) and tuple(want_i.shape) == (4,) and tuple(want_d.shape) == (4,)
+    assert torch.all(torch.isfinite(want_d)) and torch.all(want_d != 0) and torch.all(want_i != 0)
+    for with_poses, with_intr in ((False, False), (True, False), (False, True), (True, True)):
+        t = kap.clone().requires_grad_(True)
+        k = intr.clone().requires_grad_(with_intr)
+        p = poses.clone().requires_grad_(with_poses)
+        rays, tgt, used = N.select_training_rays_views(H, W, focal, p, imgs, n, opts, seed=4, step=1, intrinsics=k, distortion=t)
+        assert rays.grad_fn is not None and not tgt.requires_grad and not used.requires_grad
+        assert type(rays.grad_fn).__name__.startswith("_SelectRays")
+        for a, b in zip((rays, tgt, used), plain):
+            assert torch.equal(a, b)
+        (rays * gr).sum().backward()
+        assert torch.equal(t.grad, want_d)
+        assert torch.equal(k.grad, want_i) if with_intr else k.grad is None
+        if with_poses:
+            assert torch.equal(p.grad[:, :3, :4], want_p) and torch.all(p.grad[:, 3] == 0)
+        else:
+            assert p.grad is None
+    # the poses alone require grad: the distortion gets none
+    p = poses.clone().requires_grad_(True)
+    rays, _, _ = N.select_training_rays_views(H, W, focal, p, imgs, n, opts, seed=4, step=1, intrinsics=intr, distortion=kap)
+    (rays * gr).sum().backward()
+    assert torch.equal(p.grad[:, :3, :4], want_p) and kap.grad is None and intr.grad is None
+    # out buffers are written in place; the mask writes exact zeros; the distortion's gradient alone has the same bits
+    op, oi, od = (torch.full(s, float("nan"), device=dev) for s in ((V, 3, 4), (4,), (4,)))
+    N.select_training_rays_views_bwd(H, W, focal, poses, plain[2], gr, opts, out=op, intrinsics=intr, out_intrinsics=oi, distortion=kap,
+                                     out_distortion=od)
+    assert torch.equal(op, want_p) and torch.equal(oi, want_i) and torch.equal(od, want_d)
+    mask = torch.tensor([1, 1, 0, 0], dtype=torch.uint8, device=dev)
+    no_p, gi, gd = N.select_training_rays_views_bwd(H, W, focal, poses, plain[2], gr, opts, intrinsics=intr, distortion=kap,
+                                                    want_poses=False, distortion_mask=mask)
+    assert no_p is None and torch.equal(gi, want_i) and torch.equal(gd[:2], want_d[:2]) and torch.all(gd[2:] == 0)
+    # without intrinsics: the scalar camera; the middle entry of the triple is None
+    s_plain = N.select_training_rays_views(H, W, focal, poses, imgs, n, opts, seed=4, step=1, distortion=kap)
+    gp, none_i, gd = N.select_training_rays_views_bwd(H, W, focal, poses, s_plain[2], gr, opts, distortion=kap)
+    assert none_i is None and torch.all(gd != 0) and tuple(gp.shape) == (V, 3, 4)
+    t = kap.clone().requires_grad_(True)
+    rays, _, _ = N.select_training_rays_views(H, W, focal, poses, imgs, n, opts, seed=4, step=1, distortion=t)
+    assert torch.equal(rays, s_plain[0])
+    (rays * gr).sum().backward()
+    assert torch.equal(t.grad, gd)
+    # distortion=None: the existing node and function, unchanged; zero coefficients: their rows
+    zero = torch.zeros(4, device=dev)
+    r0 = N.select_training_rays_views(H, W, focal, poses, imgs, n, opts, seed=4, step=1, intrinsics=intr, distortion=None)
+    r1 = N.select_training_rays_views(H, W, focal, poses, imgs, n, opts, seed=4, step=1, intrinsics=intr)
+    r2 = N.select_training_rays_views(H, W, focal, poses, imgs, n, opts, seed=4, step=1, intrinsics=intr, distortion=zero)
+    for a, b, c in zip(r0, r1, r2):
+        assert torch.equal(a, b) and torch.equal(a, c)
+    assert not torch.equal(r0[0], plain[0])
+    pair = N.select_training_rays_views_bwd(H, W, focal, poses, r1[2], gr, opts, intrinsics=intr, distortion=None)
+    assert len(pair) == 2
+    zp, zi, _ = N.select_training_rays_views_bwd(H, W, focal, poses, r1[2], gr, opts, intrinsics=intr, distortion=zero)
+    assert torch.equal(zp, pair[0]) and torch.equal(zi, pair[1])
+    s0 = N.select_training_rays(H, W, focal, poses[1], imgs[1], 256, opts, seed=2, step=0)
+    s1 = N.select_training_rays(H, W, focal, poses[1], imgs[1], 256, opts, seed=2, step=0, distortion=zero)
+    assert torch.equal(s0[0], s1[0]) and torch.equal(s0[1], s1[1]) and torch.equal(s0[2], s1[2])
+    one = N.select_training_rays(H, W, focal, poses[1], imgs[1], 256, opts, seed=2, step=0, distortion=kap)
+    g34, _, g4 = N.train_utils.select_training_rays_bwd(H, W, focal, poses[1], one[2], gr[:256], opts, distortion=kap)
+    assert tuple(g34.shape) == (3, 4) and torch.all(g4 != 0) and not torch.equal(one[0], s0[0])
+    # the bundle forms: forward only
+    ro0, rd0 = N.get_ray_bundle(H, W, focal, poses[0])
+    ro1, rd1 = N.get_ray_bundle(H, W, focal, poses[0], distortion=zero)
+    assert torch.equal(ro0, ro1) and torch.equal(rd0, rd1)
+    pix = torch.tensor([0, 5, H * W - 1], device=dev)
+    for k in (None, intr):
+        a, b = N.get_rays_at_pixels(H, W, focal, poses[0], pix, intrinsics=k, distortion=kap)
+        full = N.get_ray_bundle(H, W, focal, poses[0], intrinsics=k, distortion=kap)
+        assert torch.equal(b, full[1].reshape(-1, 3)[pix]) and not torch.equal(full[1], N.get_ray_bundle(H, W, focal, poses[0], intrinsics=k)[1])
+    with pytest.raises(RuntimeError, match="forward only"):
+        N.get_ray_bundle(H, W, focal, poses[0].clone().requires_grad_(True), distortion=kap)
+    ex, ed = TV._ex_ed()
+    eval_opts = N.make_options(8, 8, perturb=False, radiance_field_noise_std=0.0)
+    rows0 = N.render_pose_rows(H, W, focal, poses[0], mc, mf, eval_opts, ex, ed, rank=1, world_size=8)
+    rows1 = N.render_pose_rows(H, W, focal, poses[0], mc, mf, eval_opts, ex, ed, rank=1, world_size=8, distortion=zero)
+    rows2 = N.render_pose_rows(H, W, focal, poses[0], mc, mf, eval_opts, ex, ed, rank=1, world_size=8, distortion=kap)
+    assert rows0[1] == rows1[1] and torch.equal(rows0[0][0], rows1[0][0]) and not torch.equal(rows0[0][0], rows2[0][0])
+    # refusals: the value is checked the way the intrinsics are
+    for bad in (kap.double(), kap[:3], kap.cpu(), [0.0, 0.0, 0.0, 0.0]):
+        with pytest.raises(RuntimeError, match="distortion must be a float32 tensor of 4"):
+            N.select_training_rays_views(H, W, focal, poses, imgs, n, opts, distortion=bad)
+    with pytest.raises(RuntimeError, match="out_distortion"):
+        N.select_training_rays_views_bwd(H, W, focal, poses, plain[2], gr, opts, out_distortion=od)
+
+
+# ---- cameras.Distortion and the engine ------------------------------------------------------------------------------------------------
+def test_distortion_object_values_masks_and_state():
+    import nerf_pytorch_amd as N
+    dev = TV._dev()
+    D = N.Distortion(learn="radial", lr=1e-2, device=dev)
+    assert torch.equal(D.values(), torch.zeros(4, device=dev)) and D.mask.tolist() == [1, 1, 0, 0]
+    D.g_dist.copy_(torch.tensor([0.5, -0.25, 0.0, 0.0], device=dev))   # (what the masked VJP leaves: exact zeros in p1, p2)
+    for _ in range(3):
+        D.step()
+    assert D.step_count == 3 and torch.all(D.dist[:2] != 0) and torch.all(D.dist[2:] == 0)
+    assert D.values().data_ptr() == D.dist.data_ptr()
+    J = N.Distortion((-0.1, 0.02, 1e-3, -1e-3), learn="all", lr=1e-2, device=dev)
+    assert torch.equal(J.values(), torch.tensor([-0.1, 0.02, 1e-3, -1e-3], device=dev)) and J.mask.tolist() == [1, 1, 1, 1]
+    J.g_dist.copy_(torch.tensor([0.5, -0.25, 3.0, -2.0], device=dev))
+    J.step()
+    state = J.state_dict()
+    assert sorted(state) == ["dist", "exp_avg", "exp_avg_sq", "learn", "step"]
+    K = N.Distortion(learn="all", lr=1e-2, device=dev)
+    K.load_state_dict(state)
+    for o in (J, K):
+        o.g_dist.copy_(torch.tensor([0.1, 0.2, -0.3, 0.4], device=dev))
+        o.step()
+    assert K.step_count == J.step_count == 2
+    for name in ("dist", "exp_avg", "exp_avg_sq", "g_dist"):
+        assert torch.equal(getattr(J, name), getattr(K, name)), name
+    assert N.Distortion(learn=(), device=dev).mask.tolist() == [0, 0, 0, 0]
+    with pytest.raises(RuntimeError, match="learn"):
+        N.Distortion(learn="tangential", device=dev)
+    with pytest.raises(RuntimeError, match="learn"):
+        N.Distortion(learn="radial", device=dev).load_state_dict(state)
+    with pytest.raises(RuntimeError, match="coeffs"):
+        N.Distortion((0.0, 0.0), device=dev)
+
+
+def _by_hand(eng, N, T, I, D, imgs, H, W, focal, opts, n):
+    """One step of step_on_views(cameras=T, intrinsics=I, distortion=D) from its parts, in its order."""
+    k, d, poses = I.values(), D.values(), T.poses()
+    with torch.no_grad():
+        rays, tgt, used = N.select_training_rays_views(H, W, focal, poses, imgs, n, opts, seed=eng.seed, step=eng.step_count, first=0,
+                                                       intrinsics=k, distortion=d)
+    rg = torch.empty_like(rays)
+    eng.forward_backward(rays, tgt, 0, None, None, rg)
+    N.select_training_rays_views_bwd(H, W, focal, poses, used, rg, opts, eng.ray_grad_coarse, out=T.g_poses, intrinsics=k,
+                                     out_intrinsics=I.g_intr, distortion=d, out_distortion=D.g_dist, distortion_mask=D.mask)
+    T.backward()
+    I.backward()
+    eng.optimizer_step()
+    T.step()
+    I.step()
+    D.step()
+    return eng.loss
+
+
+def test_step_on_views_with_distortion_equals_its_parts():
+    """Five steps of step_on_views(cameras=T, intrinsics=I, distortion=D) against the same calls made by hand: loss, nets, twists, q
+    and the coefficients on the bits."""
+    import nerf_pytorch_amd as N
+    dev = TV._dev()
+    V, n = 3, 256
+    opts = N.make_options(32, 32)
+    res = {}
+    for arm in ("engine", "parts"):
+        mc, mf, H, W, focal, pose0 = TV._lego(dev)
+        eng = N.TrainEngine(mc, mf, 32, 32, perturb=True, white_background=True, noise_std=0.2, seed=3, lr=5e-4, world_size=1, rank=0)
+        imgs = torch.rand(V, H, W, 3, generator=torch.Generator().manual_seed(1)).to(dev)
+        T = N.CameraTable(TV._views(pose0, dev, V), lr=2e-3)
+        I = N.Intrinsics(H, W, focal * 1.02, learn="all", lr=1e-3, device=dev)
+        D = N.Distortion((-0.05, 0.01, 1e-3, -1e-3), learn="all", lr=1e-3, device=dev)
+        seen = []
+        for _ in range(5):
+            if arm == "engine":
+                loss = eng.step_on_views(imgs, None, H, W, focal, opts, n, cameras=T, intrinsics=I, distortion=D)
+            else:
+                loss = _by_hand(eng, N, T, I, D, imgs, H, W, focal, opts, n)
+            seen.append([t.clone() for t in (loss, mc.flat_params, mf.flat_params, T.xi, I.q, I.g_intr, D.dist, D.exp_avg, D.exp_avg_sq,
+                                             D.g_dist)])
+        torch.cuda.synchronize()
+        res[arm] = seen
+        assert eng.step_count == T.step_count == I.step_count == D.step_count == 5
+        assert torch.all(torch.isfinite(D.dist)) and torch.all(D.g_dist != 0) and torch.all(I.q != 0) and float(T.xi.abs().sum()) > 0
+    for step, (a, b) in enumerate(zip(res["engine"], res["parts"])):
+        for name, x, y in zip(("loss", "coarse", "fine", "xi", "q", "g_intr", "dist", "exp_avg", "exp_avg_sq", "g_dist"), a, b):
+            assert torch.equal(x, y), (step, name)
+
+
+def test_a_distortion_that_learns_nothing_leaves_the_step_what_it_was():
+    """learn=() at zero coefficients: every step's loss and net gradient, and after five steps nets, twists, q and the intrinsics'
+    gradient, are those of step_on_views(cameras=T, intrinsics=I) without distortion, on the bits; the same with the distortion
+    alone against step_on_views with pose_grads."""
+    import nerf_pytorch_amd as N
+    dev = TV._dev()
+    V, n = 3, 256
+    opts = N.make_options(32, 32)
+    res = {}
+    for arm in ("with", "without", "alone", "plain"):
+        mc, mf, H, W, focal, pose0 = TV._lego(dev)
+        eng = N.TrainEngine(mc, mf, 32, 32, perturb=True, white_background=True, noise_std=0.2, seed=3, lr=5e-4, world_size=1, rank=0)
+        imgs = torch.rand(V, H, W, 3, generator=torch.Generator().manual_seed(1)).to(dev)
+        base = TV._views(pose0, dev, V)
+        T = N.CameraTable(base, lr=2e-3)
+        I = N.Intrinsics(H, W, focal * 1.02, learn="all", lr=1e-3, device=dev)
+        D = N.Distortion(learn=(), device=dev) if arm in ("with", "alone") else None
+        pg = torch.zeros((V, 3, 4), device=dev)   # (written by the two arms that pass it)
+        per_step = []
+        for _ in range(5):
+            if arm in ("with", "without"):
+                loss = eng.step_on_views(imgs, None, H, W, focal, opts, n, cameras=T, intrinsics=I, distortion=D)
+            else:
+                loss = eng.step_on_views(imgs, base, H, W, focal, opts, n, pose_grads=pg, distortion=D)
+            per_step += [loss.clone(), eng.grad.clone()]   # (the step's net gradient, coarse and fine, as the backward left it)
+        torch.cuda.synchronize()
+        assert float(per_step[-1].abs().sum()) > 0
+        res[arm] = [torch.stack(per_step[0::2]), torch.stack(per_step[1::2])] + [t.clone() for t in (mc.flat_params, mf.flat_params, T.xi,
+                                                                                                     I.q, I.g_intr, pg)]
+        if D is not None:
+            assert D.step_count == 5 and torch.all(D.dist == 0) and torch.all(D.g_dist == 0) and torch.all(D.exp_avg == 0)
+    for a, b in (("with", "without"), ("alone", "plain")):
+        for name, x, y in zip(("losses", "net gradients", "coarse", "fine", "xi", "q", "g_intr", "pose_grads"), res[a], res[b]):
+            assert torch.equal(x, y), (a, name)
+
+
+def test_localize_with_distortion_leaves_the_nets_alone_and_refusals():
+    import nerf_pytorch_amd as N
+    dev = TV._dev()
+    mc, mf, H, W, focal, pose0 = TL._small(dev)
+    V, n = 3, 256
+    opts = N.make_options(8, 8)
+    imgs = torch.rand(V, H, W, 3, generator=torch.Generator().manual_seed(1)).to(dev)
+    base = TV._views(pose0, dev, V)
+    eng = N.TrainEngine(mc, mf, 8, 8, perturb=True, white_background=True, noise_std=0.2, seed=3, lr=5e-4, world_size=1, rank=0)
+    eng.grad.normal_(), eng.exp_avg.normal_(), eng.exp_avg_sq.uniform_()
+    before = TL._state(eng)
+    D = N.Distortion(learn="radial", lr=1e-3, device=dev)
+    I = N.Intrinsics(H, W, focal * 1.05, learn="focal", lr=1e-3, device=dev)
+    T = N.CameraTable(base, lr=2e-3)
+    for _ in range(2):
+        eng.localize_on_views(imgs, base, H, W, focal, opts, n, distortion=D)     # the distortion alone
+    eng.localize_on_views(imgs, None, H, W, focal, opts, n, cameras=T, intrinsics=I, distortion=D)
+    pg = torch.full((3, 4), float("nan"), device=dev)
+    eng.localize_on_image(imgs[0], base[0], H, W, focal, opts, n, pose_grad=pg, distortion=D)
+    eng.localize_on_image(imgs[0], base[0], H, W, focal, opts, n, distortion=D)
+    torch.cuda.synchronize()
+    for name, a, b in zip(("coarse", "fine", "exp_avg", "exp_avg_sq", "grad", "packed_c", "packed_f"), before, TL._state(eng)):
+        assert torch.equal(a, b), name
+    assert eng.step_count == 0 and eng.localize_count == 5 and D.step_count == 5 and I.step_count == 1 and T.step_count == 1
+    assert torch.all(D.dist[:2] != 0) and torch.all(D.dist[2:] == 0) and torch.all(D.g_dist[2:] == 0)
+    assert torch.all(torch.isfinite(pg)) and float(pg.abs().sum()) > 0
+    with pytest.raises(RuntimeError, match="Distortion"):
+        eng.step_on_views(imgs, base, H, W, focal, opts, n, distortion=D.values())
+    eng2 = N.TrainEngine(mc, mf, 8, 8, world_size=2, rank=0)
+    for call in (lambda: eng2.step_on_views(imgs, base, H, W, focal, opts, n, distortion=D),
+                 lambda: eng2.step_on_image(imgs[0], base[0], H, W, focal, opts, n, distortion=D)):
+        with pytest.raises(NotImplementedError, match="distortion with world size 2"):
+            call()
+    with pytest.raises(RuntimeError, match="needs"):
+        eng.localize_on_views(imgs, base, H, W, focal, opts, n)
+    assert D.step_count == 5
+
+
+# ---- the kernels one step of each new form launches ---------------------------------------------------------------------------------------
+def _forms(s):
+    """{form: (engine, cameras, intrinsics, distortion) -> one step of that form}."""
+    img, vw, no_poses = s.image_args(), s.views_args(), s.views_args(poses=False)
+    g34 = lambda: torch.empty(3, 4, device=s.dev)  # noqa: E731
+    gv34 = lambda: torch.empty(SF.V, 3, 4, device=s.dev)  # noqa: E731
+    return {
+        "step_on_image distortion": lambda e, T, I, D: e.step_on_image(*img, distortion=D),
+        "step_on_image pose_grad intrinsics distortion": lambda e, T, I, D: e.step_on_image(*img, pose_grad=g34(), intrinsics=I, distortion=D),
+        "step_on_views distortion": lambda e, T, I, D: e.step_on_views(*vw, distortion=D),
+        "step_on_views pose_grads distortion": lambda e, T, I, D: e.step_on_views(*vw, pose_grads=gv34(), distortion=D),
+        "step_on_views cameras distortion": lambda e, T, I, D: e.step_on_views(*no_poses, cameras=T, distortion=D),
+        "step_on_views intrinsics distortion": lambda e, T, I, D: e.step_on_views(*vw, intrinsics=I, distortion=D),
+        "step_on_views cameras intrinsics distortion": lambda e, T, I, D: e.step_on_views(*no_poses, cameras=T, intrinsics=I, distortion=D),
+        "localize_on_image distortion": lambda e, T, I, D: e.localize_on_image(*img, distortion=D),
+        "localize_on_views distortion": lambda e, T, I, D: e.localize_on_views(*vw, distortion=D),
+        "localize_on_views cameras intrinsics distortion": lambda e, T, I, D: e.localize_on_views(*no_poses, cameras=T, intrinsics=I,
+                                                                                                distortion=D),
+    }
+
+
+def _launches():
+    """{form: {kernel name: launches}} of the second step of every form (the first one warms up), fresh objects for each."""
+    import ctypes
+    s = SF._Scene()
+    lib = s.N._lib.get_lib()
+    out = {}
+    for form, step in _forms(s).items():
+        eng, T, I = s.engine(world_size=1), s.table(), s.intrinsics()
+        D = s.N.Distortion((-0.05, 0.01, 0.0, 0.0), learn="radial", lr=1e-3, device=s.dev)
+        step(eng, T, I, D)
+        torch.cuda.synchronize()
+        lib.profile_reserve(256)
+        lib.profile_enable(1)
+        try:
+            step(eng, T, I, D)
+            torch.cuda.synchronize()
+        finally:
+            lib.profile_enable(0)
+        buf = ctypes.create_string_buffer(1 << 16)
+        lib.profile_report(buf, len(buf))
+        counts = {}
+        for ln in buf.value.decode().splitlines():   # "kernel_name launches total_ms"
+            parts = ln.rsplit(None, 2)
+            if len(parts) == 3:
+                counts[parts[0]] = counts.get(parts[0], 0) + int(parts[1])
+        out[form] = counts
+    return out
+
+
+def test_every_distortion_step_form_launches_what_the_fixture_recorded():
+    with open(FIXTURE) as f:
+        want = json.load(f)
+    got = _launches()
+    assert sorted(got) == sorted(want) and len(got) == 10
+    for form in want:
+        assert got[form] and got[form] == want[form], (form, got[form], want[form])
+        assert got[form]["k_select_rays"] == 1 and got[form]["k_dist_vjp_part"] == 1 and got[form]["k_dist_vjp_sum"] == 1
+        assert ("k_intr_vjp_part" in got[form]) == ("intrinsics" in form)
+
+
+# ---- the capability: a radial coefficient recovered against frozen nets ---------------------------------------------------------------------
+# The search space of the issue, in its order; CHOSEN is the first combination whose REFERENCE arm alone ends below one fifth of its
+# starting |k1 - k1_true| (found by `python tests/test_gpu_distortion.py --search`, which runs the reference arm only).
+SEARCH = [(k1, lr, steps) for k1 in (-0.1, -0.2) for lr in (1e-3, 3e-3) for steps in (300, 600)]
+CHOSEN = SEARCH[0]
+RAYS = 1024
+
+
+def _undistort_torch(xd, yd, kappa):
+    """The reference arm's rays: the converged solve (fp64, detached), then one differentiable Newton step from the coefficient leaf
+    with the Jacobian held fixed -- tests/distortion_cases.py's reference in torch on the device."""
+    with torch.no_grad():
+        k64 = kappa.detach().double()
+        x, y = xd.double(), yd.double()
+        for _ in range(12):
+            Fx, Fy, a, b, d = DC.distort(x, y, k64)
+            det = a * d - b * b
+            x, y = x - (d * (Fx - xd) - b * (Fy - yd)) / det, y - (a * (Fy - yd) - b * (Fx - xd)) / det
+        _, _, a, b, d = DC.distort(x, y, k64)
+        det = a * d - b * b
+    Fx, Fy, _, _, _ = DC.distort(x, y, kappa.double())
+    rx, ry = Fx - xd, Fy - yd
+    return (x - (d * rx - b * ry) / det).float(), (y - (a * ry - b * rx) / det).float()
+
+
+def _capability_scene(dev, k1_true):
+    import nerf_pytorch_amd as N
+    mc, mf, H, W, focal, pose0 = TV._lego(dev)
+    for p in list(mc.parameters()) + list(mf.parameters()):
+        p.requires_grad_(False)
+    ex, ed = TV._ex_ed()
+    opts = N.make_options(64, 64, perturb=False, white_background=True, radiance_field_noise_std=0.0)
+    gt0 = torch.from_numpy(pose0).to(dev)
+    turn = torch.eye(4, device=dev)
+    turn[:3, :3] = P.rodrigues(torch.tensor([0.0, 0.0, np.deg2rad(20.0)], dtype=torch.float64)).float().to(dev)
+    gts = torch.stack([gt0, turn @ gt0]).contiguous()
+    k_true = torch.tensor([k1_true, 0.0, 0.0, 0.0], dtype=torch.float32, device=dev)
+    with torch.no_grad():
+        targets = []
+        for v in range(2):
+            ro, rd = N.get_ray_bundle(H, W, focal, gts[v], distortion=k_true)
+            targets.append(N.run_one_iter_of_nerf(H, W, focal, mc, mf, ro, rd, opts, mode="validation", encode_position_fn=ex,
+                                                  encode_direction_fn=ed)[3])
+        targets = torch.stack(targets).contiguous()
+    return N, mc, mf, H, W, focal, ex, ed, opts, gts, targets
+
+
+def _reference_arm(scene, k1_true, lr, steps, seed):
+    """The reference arm: the engine arm's batches, rays from _undistort_torch, the nets under set_frozen, torch.optim.Adam."""
+    N, mc, mf, H, W, focal, ex, ed, opts, gts, targets = scene
+    dev = gts.device
+    k1 = torch.zeros((), device=dev, requires_grad=True)
+    opt = torch.optim.Adam([k1], lr=lr)
+    mc.set_frozen(True), mf.set_frozen(True)
+    curve = [(-1, abs(k1_true))]
+    hw, near, far = H * W, float(opts.dataset.near), float(opts.dataset.far)
+    zero = torch.zeros((), device=dev)
+    try:
+        for it in range(steps):
+            with torch.no_grad():
+                _, tgt, used = N.select_training_rays_views(H, W, focal, gts, targets, RAYS, opts, seed=seed, step=it, first=0)
+            opt.zero_grad()
+            vid, k = used // hw, used % hw
+            row, col = (k % H).float(), (k // H).float()
+            x, y = _undistort_torch((col - W * 0.5) / focal, (row - H * 0.5) / focal, torch.stack([k1, zero, zero, zero]))
+            dc = torch.stack([x, -y, -torch.ones_like(x)], -1)
+            d = (gts[vid][:, :3, :3] * dc[:, None, :]).sum(-1)
+            o = gts[vid][:, :3, 3]
+            rays = torch.cat([o, d, torch.full_like(d[:, :1], near), torch.full_like(d[:, :1], far), d / d.norm(dim=-1, keepdim=True)], -1)
+            out = N.predict_and_render_radiance(rays, mc, mf, opts, encode_position_fn=ex, encode_direction_fn=ed)
+            loss = torch.nn.functional.mse_loss(out[0], tgt) + torch.nn.functional.mse_loss(out[3], tgt)
+            loss.backward()
+            opt.step()
+            if it % 50 == 0 or it == steps - 1:
+                curve.append((it, abs(float(k1.detach()) - k1_true)))
+    finally:
+        mc.set_frozen(False), mf.set_frozen(False)
+    return curve
+
+
+def test_a_radial_coefficient_is_recovered_on_frozen_nets():
+    """Frozen lego-lowres nets; two views at their exact poses and intrinsics with targets rendered through
+    get_ray_bundle(distortion=(k1_true, 0, 0, 0)) (64 + 64 samples, no perturb, white background).  Engine arm: STEPS
+    localize_on_views(distortion=D) steps of RAYS rays, D = Distortion(learn="radial") from zero.  Reference arm: _reference_arm.  The
+    bar: the engine arm's final |k1 - k1_true| is at most 3 x the reference arm's (the margin of the three existing capability
+    tests); the reference arm alone must end below one fifth of its start, which is what fixed CHOSEN."""
+    dev = TV._dev()
+    k1_true, lr, steps = CHOSEN
+    scene = _capability_scene(dev, k1_true)
+    N, mc, mf, H, W, focal, ex, ed, opts, gts, targets = scene
+    eng = N.TrainEngine(mc, mf, 64, 64, perturb=False, white_background=True, noise_std=0.0, lr=0.0, world_size=1, rank=0)
+    D = N.Distortion(learn="radial", lr=lr, device=dev)
+    curve_e = [(-1, abs(k1_true))]
+    for it in range(steps):
+        eng.localize_on_views(targets, gts, H, W, focal, opts, RAYS, distortion=D)
+        if it % 50 == 0 or it == steps - 1:
+            curve_e.append((it, abs(float(D.dist[0]) - k1_true)))
+    assert torch.all(D.dist[2:] == 0) and torch.all(torch.isfinite(D.dist))
+    curve_r = _reference_arm(scene, k1_true, lr, steps, eng.seed)
+    print("k1 recovery, engine arm (step, |k1 - k1_true|): %s" % curve_e)
+    print("k1 recovery, reference arm: %s" % curve_r)
+    print("DISTORTION_CAPABILITY " + json.dumps(dict(k1_true=k1_true, steps=steps, lr=lr, rays=RAYS, engine=curve_e, reference=curve_r)))
+    assert curve_r[-1][1] < curve_r[0][1] / 5, curve_r        # the reference arm alone
+    assert curve_e[-1][1] <= 3 * curve_r[-1][1], (curve_e, curve_r)
+
+
+if __name__ == "__main__":
+    if len(sys.argv) == 3 and sys.argv[1] == "--record":
+        with open(sys.argv[2], "w") as f:
+            json.dump(_launches(), f, indent=1, sort_keys=True)
+            f.write("\n")
+    elif len(sys.argv) == 2 and sys.argv[1] == "--search":
+        for k1_true, lr, steps in SEARCH:   # the reference arm alone, in the issue's order; the first that passes is CHOSEN
+            curve = _reference_arm(_capability_scene(torch.device("cuda", 0), k1_true), k1_true, lr, steps, 0)
+            ok = curve[-1][1] < curve[0][1] / 5
+            print("DISTORTION_SEARCH " + json.dumps(dict(k1_true=k1_true, lr=lr, steps=steps, passes=ok, reference=curve)), flush=True)
+            if ok:
+                break
+    else:
+        sys.exit("usage: python tests/test_gpu_distortion.py --record PATH | --search")
