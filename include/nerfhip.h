@@ -601,6 +601,33 @@ int nerfhip_select_rays_views_dist_bwd(const nerfhip_select_cfg* cfg, const floa
 int nerfhip_ray_bundle_dist(int height, int width, float focal, const float* intr, const float* dist, const float* c2w, int c2w_ld,
                             const int64_t* pixels, int64_t n, float* ray_origins, float* ray_directions, nerfhip_stream_t stream);
 
+/* ---- per-view exposure: a colour gain and offset per view behind the render, with their gradient (NeRF-W / URF style) ----------------
+ * expo: dev float [V][6], row v = (s_r, s_g, s_b, b_r, b_g, b_b): per-channel log-gain and offset of view v.  Ray i belongs to view
+ * inds[i] / hw (inds: the GLOBAL indices the views selection returns, hw = height * width); its corrected prediction in channel c is
+ *     p' = e p + b,   e = exp(s[v][c]),   b = b[v][c],
+ * alike for the coarse and the fine rgb, and the loss is nerfhip_mse_loss_fwd_bwd's on p'.  A zero table is the identity; an index
+ * outside [0, V hw) belongs to no view: identity in the loss, dropped from the table gradient.
+ * Arithmetic (fp32, one rounding per operation, unless said): e = (float)exp((double)s) -- one fp64 exp --; q = e p; d = (q + b) - t;
+ * k = 2 / (3 n) * grad_scale; the loss sums (double)d (double)d as the plain loss does; g_rgb = (d k) e; per ray and net the table
+ * gradient adds (d k) q to g_s[v][c] and d k to g_b[v][c], the coarse term first.
+ * Limits: 1 <= num_views <= NERFHIP_MAX_VIEWS, hw >= 1, num_views * hw <= 2^32, n < 2^31, target_stride >= 3; expo must not be NULL. */
+/* nerfhip_mse_loss_fwd_bwd under the table: one launch, the same workgroup, order of summation and fp64 sums; rgb_fine and
+ * either g_rgb_* may be NULL; n > 0.  expo == 0 gives nerfhip_mse_loss_fwd_bwd's loss words and cotangents. */
+int nerfhip_mse_loss_views_fwd_bwd(const float* rgb_coarse, const float* rgb_fine, const float* target, int target_stride, int64_t n,
+                                   float grad_scale, const int64_t* inds, int64_t hw, const float* expo, int num_views,
+                                   float* g_rgb_coarse, float* g_rgb_fine, float* loss_out, nerfhip_stream_t stream);
+/* d(loss_coarse + loss_fine)/d(expo) -> g_expo: dev float [V][6], written completely (n == 0, or a view without a ray: exact zeros).
+ * Row v is ONE sum over view v's rays in ascending batch position along the single-view tree of the pose VJP with n = n_v: three
+ * launches whose grids depend on (n, V) only (the grouping of nerfhip_select_rays_views_bwd, floor(n / 256) + V workgroups of six
+ * partial sums, V workgroups that add them), no atomics, bit-reproducible; the result depends on the rays' view assignment and values
+ * only.  mask: dev, V * 6 bytes, or NULL = all learned: an entry whose byte is 0 gets an exact zero (with Adam it never moves).
+ * tmp: dev scratch of nerfhip_exposure_grad_tmp_bytes(n, num_views) = 4 (6 (floor(n / 256) + V) + 2 V + n) bytes (-1 for n < 0,
+ * n >= 2^31 or num_views outside 1 .. NERFHIP_MAX_VIEWS). */
+int64_t nerfhip_exposure_grad_tmp_bytes(int64_t n, int num_views);
+int nerfhip_exposure_bwd(const float* rgb_coarse, const float* rgb_fine, const float* target, int target_stride, int64_t n,
+                         float grad_scale, const int64_t* inds, int64_t hw, const float* expo, int num_views, const unsigned char* mask,
+                         void* tmp, int64_t tmp_bytes, float* g_expo, nerfhip_stream_t stream);
+
 /* ---- camera table: one se(3) twist per view composed onto a base pose (the parametrisation pose refinement steps) --------
  * poses[v] = base[v] * Exp(xi[v]): a camera-frame perturbation.  xi: dev float [V][6] = [w (3), v (3)]; Exp is the full SE(3)
  * exponential: R = I + A W + B W^2, t = (I + B W + C W^2) v with W = hat(w), th = |w|, A = sin th / th, B = (1 - cos th) / th^2,

@@ -7,7 +7,7 @@ select_training_rays_views; their cameras as se(3) twists on base poses: cameras
 tree and the CLI scripts of the reference are out of scope.
 """
 from . import eval_utils, io_utils, models  # noqa: F401
-from .cameras import CameraTable, Distortion, Intrinsics, se3_poses  # noqa: F401
+from .cameras import CameraTable, Distortion, Exposure, Intrinsics, se3_poses  # noqa: F401
 from .cfg import AttrDict, make_options  # noqa: F401
 from .engine import TrainEngine  # noqa: F401
 from .models import FlexibleNeRFModel  # noqa: F401
@@ -16,7 +16,7 @@ from .nerf_helpers import (cumprod_exclusive, get_embedding_function, get_miniba
                            sample_pdf, sample_pdf_2, sample_pdf_with_indices)
 from .eval_utils import ImageWriter, cast_to_disparity_image, cast_to_image, render_pose_rows  # noqa: F401
 from .io_utils import load_cached_example, load_checkpoint, save_cached_example, save_checkpoint  # noqa: F401
-from .train_utils import (pack_rays, predict_and_render_radiance, run_network, run_one_iter_of_nerf,  # noqa: F401
+from .train_utils import (exposure_mse_loss, pack_rays, predict_and_render_radiance, run_network, run_one_iter_of_nerf,  # noqa: F401
                           select_cached_training_rays, select_training_rays, select_training_rays_views,
                           select_training_rays_views_bwd)
 from .volume_rendering_utils import volume_render_radiance_field  # noqa: F401

@@ -161,6 +161,10 @@ _PROTOS = {
     "nerfhip_select_rays_views_dist_bwd": (C.c_int, [C.POINTER(SelectCfg), c_f, c_f, C.c_int, c_f, c_i64, C.c_int, c_f, c_i64, c_f,
                                                      c_f, C.c_int, c_f, c_i64, c_f, c_f, c_f, c_f, c_f]),
     "nerfhip_ray_bundle_dist": (C.c_int, [C.c_int, C.c_int, C.c_float, c_f, c_f, c_f, C.c_int, c_f, c_i64, c_f, c_f, c_f]),
+    "nerfhip_mse_loss_views_fwd_bwd": (C.c_int, [c_f, c_f, c_f, C.c_int, c_i64, C.c_float, c_f, c_i64, c_f, C.c_int, c_f, c_f, c_f,
+                                                 c_f]),
+    "nerfhip_exposure_grad_tmp_bytes": (c_i64, [c_i64, C.c_int]),
+    "nerfhip_exposure_bwd": (C.c_int, [c_f, c_f, c_f, C.c_int, c_i64, C.c_float, c_f, c_i64, c_f, C.c_int, c_f, c_f, c_i64, c_f, c_f]),
     "nerfhip_intrinsics_fwd": (C.c_int, [c_f, c_f, C.c_int, c_f, c_f]),
     "nerfhip_intrinsics_bwd": (C.c_int, [c_f, c_f, C.c_int, c_f, c_f, c_f, c_f]),
     "nerfhip_pose_table_fwd": (C.c_int, [c_f, c_f, c_i64, C.c_int, C.c_int, c_f, c_f]),

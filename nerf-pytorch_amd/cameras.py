@@ -12,6 +12,9 @@ d(loss)/d(poses) back to the twists (nerfhip_pose_table_bwd), and the twists are
   ``TrainEngine.step_on_views(intrinsics=...)`` learns them next to the field and the poses.
 * ``Distortion`` -- the shared lens distortion (k1, k2, p1, p2) on the device with its Adam state;
   ``TrainEngine.step_on_views(distortion=...)`` learns it next to the field, the poses and the intrinsics.
+* ``Exposure`` -- a colour log-gain and offset per view and channel on the device with its Adam state: the photometric side of a real
+  capture (auto-exposure, auto-white-balance); ``TrainEngine.step_on_views(exposure=...)`` learns it next to everything above,
+  ``localize_on_views(exposure=...)`` fits it against frozen nets.
 """
 import torch
 
@@ -84,7 +87,7 @@ def check_device_vector(t, shape, dev, what=None):
 
 
 class _AdamVector:
-    """A learned device vector with its Adam state: the parameter `_param` ("xi" / "q" / "dist"), its gradient buffer "g_" + _param,
+    """A learned device vector with its Adam state: the parameter `_param` ("xi" / "q" / "dist" / "expo"), its gradient buffer "g_" + _param,
     the two moments, step_count, lr, betas, eps; the state dict holds the parameter, the moments, `base` (where the vector is a
     perturbation of one) and the step count."""
 
@@ -274,4 +277,118 @@ class Distortion(_AdamVector):
         if "learn" in state and (tuple(state["learn"]) if isinstance(state["learn"], (list, tuple)) else state["learn"]) != self.learn:
             raise RuntimeError("Distortion.load_state_dict: the state was saved with learn=%r, this object has learn=%r"
                                % (state["learn"], self.learn))
+        super().load_state_dict(state)
+
+
+_LEARN_EXPO = {"affine": (1, 1, 1, 1, 1, 1), "gain": (1, 1, 1, 0, 0, 0), (): (0, 0, 0, 0, 0, 0)}
+
+
+def exposure_grad(rgb_coarse, rgb_fine, target, inds, hw, table, grad_scale=1.0, mask=None, tmp=None, out=None):
+    """nerfhip_exposure_bwd on the current stream of the tensors' device: d(loss_coarse + loss_fine)/d(table) (V x 6 float32) of
+    the loss under the table (include/nerfhip.h), into `out` (or a new tensor).  rgb_*: contiguous float32 (n, 3) (rgb_fine may be
+    None); target: (n, >= 3) rows of unit-stride floats; inds: the selection's int64 global indices; tmp: None, or a float32 scratch
+    of at least nerfhip_exposure_grad_tmp_bytes(n, V) bytes.  Three launches, no host synchronisation."""
+    lib = L.get_lib()
+    if not isinstance(table, torch.Tensor) or not table.is_cuda or table.dim() != 2:
+        raise RuntimeError("exposure_grad: table must be a (V, 6) tensor on a CUDA (HIP) device")
+    dev, nv = table.device, table.shape[0]
+    check_device_vector(table, (nv, 6), dev, "exposure_grad: table")
+    if not isinstance(rgb_coarse, torch.Tensor) or rgb_coarse.dim() != 2:
+        raise RuntimeError("exposure_grad: rgb_coarse must be a contiguous float32 (n, 3) tensor on %s" % dev)
+    n = rgb_coarse.shape[0]
+    check_device_vector(rgb_coarse, (n, 3), dev, "exposure_grad: rgb_coarse")
+    if rgb_fine is not None:
+        check_device_vector(rgb_fine, (n, 3), dev, "exposure_grad: rgb_fine")
+    if not (isinstance(target, torch.Tensor) and target.device == dev and target.dtype == torch.float32 and target.dim() == 2
+            and target.shape[0] == n and target.shape[1] >= 3 and target.stride(1) == 1):
+        raise RuntimeError("exposure_grad: target must hold one row of >= 3 unit-stride float32 per ray (%d) on %s" % (n, dev))
+    if not (isinstance(inds, torch.Tensor) and inds.device == dev and inds.dtype == torch.int64 and tuple(inds.shape) == (n,)
+            and inds.is_contiguous()):
+        raise RuntimeError("exposure_grad: inds must be a contiguous int64 (%d) tensor on %s" % (n, dev))
+    if mask is not None and not (isinstance(mask, torch.Tensor) and mask.device == dev and mask.dtype == torch.uint8
+                                 and tuple(mask.shape) == (nv, 6) and mask.is_contiguous()):
+        raise RuntimeError("exposure_grad: mask must be a contiguous uint8 (%d, 6) tensor on %s" % (nv, dev))
+    tb = lib.exposure_grad_tmp_bytes(n, nv)
+    if tb < 0:
+        raise RuntimeError("exposure_grad: %d rays over %d views is outside the kernel's limits" % (n, nv))
+    if tmp is None:
+        tmp = torch.empty(tb // 4 + 1, dtype=torch.float32, device=dev)
+    elif not (isinstance(tmp, torch.Tensor) and tmp.device == dev and tmp.dtype == torch.float32 and tmp.is_contiguous()
+              and tmp.numel() * 4 >= tb):
+        raise RuntimeError("exposure_grad: tmp must be a contiguous float32 tensor of at least %d bytes on %s" % (tb, dev))
+    if out is None:
+        out = torch.empty((nv, 6), dtype=torch.float32, device=dev)
+    else:
+        check_device_vector(out, (nv, 6), dev, "exposure_grad: out")
+    with L.launch_on(rgb_coarse, rgb_fine, target, inds, table, mask, tmp, out) as st:
+        lib.exposure_bwd(rgb_coarse.data_ptr(), rgb_fine.data_ptr() if rgb_fine is not None else None, target.data_ptr(),
+                         target.stride(0), n, float(grad_scale), inds.data_ptr(), int(hw), table.data_ptr(), nv,
+                         mask.data_ptr() if mask is not None else None, tmp.data_ptr(), tmp.numel() * 4, out.data_ptr(), st)
+    return out
+
+
+class Exposure(_AdamVector):
+    """The per-view exposure of a capture: row v of the (V, 6) table `expo` is (s_r, s_g, s_b, b_r, b_g, b_b), and a ray of view v
+    is compared with its target as exp(s) * rgb + b per channel, coarse and fine alike (include/nerfhip.h).  Resident on the device
+    with its Adam state; the table is stepped directly.  It sits behind the render, so its gradient needs no ray gradient:
+    backward() is nerfhip_exposure_bwd (three launches) on the two rgb buffers, the targets and the selection's global indices, and
+    step() is the fused Adam kernel the nets use.  Every buffer is allocated here (the scratch of backward() once per batch size that
+    grows it); no host synchronisation.
+
+    learn: "affine" (gain and offset), "gain" (the s columns only), or () (nothing moves).  anchor: views that stay at the
+    identity -- their rows of `mask` are all zero, so their gradient is an exact zero --: one anchored view removes the global
+    gain / offset ambiguity between the field and the table; anchor=() anchors none."""
+    _param, _holder = "expo", "the object"
+
+    def __init__(self, num_views, learn="affine", anchor=(0,), lr=1e-3, betas=(0.9, 0.999), eps=1e-8, device=None):
+        key = tuple(learn) if isinstance(learn, (list, tuple)) else learn
+        if key not in _LEARN_EXPO:
+            raise RuntimeError('Exposure: learn must be "affine", "gain" or () (got %r)' % (learn,))
+        self.dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.dev.type != "cuda":
+            raise RuntimeError("Exposure lives on a CUDA (HIP) device (nerf_pytorch_amd has no CPU path)")
+        self.num_views = v = int(num_views)
+        if v < 1:
+            raise RuntimeError("Exposure: num_views must be >= 1 (got %r)" % (num_views,))
+        self.anchor = tuple(sorted(set(int(a) for a in anchor)))
+        if any(a < 0 or a >= v for a in self.anchor):
+            raise RuntimeError("Exposure: anchor views must be in 0 .. %d (got %r)" % (v - 1, anchor))
+        self.lib = L.get_lib()
+        self.learn = key
+        self._init_adam((v, 6), lr, betas, eps)
+        self._state = ("expo", "exp_avg", "exp_avg_sq")
+        mask = torch.tensor(_LEARN_EXPO[key], dtype=torch.uint8).repeat(v, 1)
+        if self.anchor:
+            mask[list(self.anchor)] = 0
+        self.mask = mask.to(self.dev).contiguous()
+        self._tmp = None
+
+    def values(self):
+        """The (V, 6) table: the object's own parameter, the `table` of train_utils.exposure_mse_loss (the kernels read it in
+        place; no launch)."""
+        return self.expo
+
+    def backward(self, rgb_coarse, rgb_fine, target, inds, hw, grad_scale=1.0):
+        """d(loss)/d(expo) into the object's own `g_expo` (masked entries: exact zeros), from the rgb the nets rendered for the batch
+        (rgb_fine may be None), its targets and its global indices `inds` (view = inds // hw)."""
+        tb = self.lib.exposure_grad_tmp_bytes(rgb_coarse.shape[0], self.num_views)
+        if tb >= 0 and (self._tmp is None or self._tmp.numel() * 4 < tb):
+            self._tmp = torch.empty(tb // 4 + 1, dtype=torch.float32, device=self.dev)
+        return exposure_grad(rgb_coarse, rgb_fine, target, inds, hw, self.expo, grad_scale, self.mask, self._tmp, self.g_expo)
+
+    def apply(self, rgb, view):
+        """exp(s) * rgb + b with row `view`, for an evaluation image rendered at that view: plain torch arithmetic on the device."""
+        row = self.expo[int(view)]
+        return rgb[..., :3] * torch.exp(row[:3]) + row[3:]
+
+    def state_dict(self):
+        return dict(super().state_dict(), learn=self.learn, anchor=self.anchor)
+
+    def load_state_dict(self, state):
+        if "learn" in state and (tuple(state["learn"]) if isinstance(state["learn"], (list, tuple)) else state["learn"]) != self.learn:
+            raise RuntimeError("Exposure.load_state_dict: the state was saved with learn=%r, this object has learn=%r"
+                               % (state["learn"], self.learn))
+        if "anchor" in state and tuple(int(a) for a in state["anchor"]) != self.anchor:
+            raise RuntimeError("Exposure.load_state_dict: the state was saved with anchor=%r, this object has anchor=%r"
+                               % (tuple(state["anchor"]), self.anchor))
         super().load_state_dict(state)

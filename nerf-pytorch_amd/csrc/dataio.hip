@@ -654,7 +654,116 @@ int views_bwd(const char* what, const nerfhip_select_cfg* cfg, const float* intr
     return rc;
 }
 
+// ---- the gradient of the per-view exposure table (nerfhip_exposure_bwd) ---------------------------------------------------------------
+// expo [V][6] = (s_r s_g s_b b_r b_g b_b) per view sits behind the render: p' = exp(s) p + b (k_mse_loss_views, elementwise.hip), so
+// its gradient needs the two rgb buffers, the targets and the batch's global indices, and no ray gradient.  Row v is ONE sum over view
+// v's rays in ascending batch position along the single-view tree with n = n_v -- the pose VJP's scheme over views: the same grouping
+// launch (k_pose_views_group: off, cnt, the stable per-view list), k_pose_views_part's slots with six thread sums in list order,
+// pv_block_sum<6>, then k_pose_vjp_sum<6> with V workgroups.  An index outside [0, V hw) is in no view's list: dropped.
+// Per ray of the list and channel c, in this order, every operation one fp32 rounding unless said (e, b: the view's, once per thread):
+//     e = (float)exp((double)s)                                       (one fp64 exp, then the final rounding)
+//     coarse:  q = e * p;  d = (q + b) - t;  dk = d * k;  acc_s[c] += dk * q;  acc_b[c] += dk
+//     fine (when given): the same on the fine rgb, added after the coarse term
+// with k = 2 / (3 n) * grad_scale formed as k_mse_loss forms it.  mask (device, [V][6] bytes, or NULL = all learned): a masked
+// entry's partial is an exact zero in every workgroup of its view, so its sum is one.
+struct ExpoArgs {
+    const float *rc, *rf, *tgt;   // rf may be NULL
+    int tstride;
+    int64_t n;
+    float grad_scale;
+    const float* expo;
+    const unsigned char* mask;
+    float* part;                  // the slots' partials [floor(n / 256) + V][6]
+};
+
+NH_KERNEL void k_expo_part(PoseViewsArgs p, ExpoArgs x) {
+    NH_SHARED float s_part[PV_THREADS / 64][6];
+    const int w = (int)blockIdx.x;
+    int v = 0, top = p.num_views - 1;  // the last view whose first slot is <= w (k_pose_views_part)
+    while (v < top) {
+        const int mid = (v + top + 1) >> 1;
+        if (p.off[mid] / PV_THREADS + mid <= w)
+            v = mid;
+        else
+            top = mid - 1;
+    }
+    const int off = p.off[v], nv = p.cnt[v];
+    const int b = w - (off / PV_THREADS + v), wgs = (int)pv_wgs(nv);
+    // (a slot no view uses; the whole workgroup leaves.  b < 0: indices below 0 count as "less" for every view, so with 256 or more of
+    // them view 0's first slot is above 0 and the workgroups below it belong to nobody)
+    if (b < 0 || b >= wgs) return;
+    const float k = 2.0f / (float)(3 * x.n) * x.grad_scale;
+    float e[3], o[3], acc[6];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        e[c] = (float)exp((double)x.expo[(int64_t)v * 6 + c]);
+        o[c] = x.expo[(int64_t)v * 6 + 3 + c];
+        acc[c] = 0.0f, acc[3 + c] = 0.0f;
+    }
+    const int step = wgs * PV_THREADS;
+    for (int r = b * PV_THREADS + (int)threadIdx.x; r < nv; r += step) {
+        const int64_t i = p.list[off + r];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float t = x.tgt[i * x.tstride + c];
+            float q = e[c] * x.rc[i * 3 + c];
+            float dk = ((q + o[c]) - t) * k;
+            acc[c] += dk * q;
+            acc[3 + c] += dk;
+            if (x.rf) {
+                q = e[c] * x.rf[i * 3 + c];
+                dk = ((q + o[c]) - t) * k;
+                acc[c] += dk * q;
+                acc[3 + c] += dk;
+            }
+        }
+    }
+    if (x.mask) {
+#pragma unroll
+        for (int j = 0; j < 6; ++j)
+            if (!x.mask[(int64_t)v * 6 + j]) acc[j] = 0.0f;
+    }
+    pv_block_sum<6>(acc, s_part, x.part + (int64_t)w * 6);
+}
+
 }  // namespace
+
+extern "C" int64_t nerfhip_exposure_grad_tmp_bytes(int64_t n, int num_views) {
+    if (n < 0 || n >= ((int64_t)1 << 31) || num_views < 1 || num_views > NERFHIP_MAX_VIEWS) return -1;
+    return (int64_t)sizeof(float) * (6 * (n / PV_THREADS + num_views) + 2 * (int64_t)num_views + n);
+}
+
+extern "C" int nerfhip_exposure_bwd(const float* rgb_coarse, const float* rgb_fine, const float* target, int target_stride, int64_t n,
+                                    float grad_scale, const int64_t* inds, int64_t hw, const float* expo, int num_views,
+                                    const unsigned char* mask, void* tmp, int64_t tmp_bytes, float* g_expo, nerfhip_stream_t stream) {
+    const char* what = "exposure_bwd";
+    int rc = nh_exposure_check(what, inds, n, hw, expo, num_views);
+    if (rc) return rc;
+    NH_REQUIRE(g_expo && (n == 0 || (rgb_coarse && target)), "%s: bad arguments", what);
+    NH_REQUIRE(target_stride >= 3, "%s: target_stride must be >= 3 (got %d)", what, target_stride);
+    const int64_t need = nerfhip_exposure_grad_tmp_bytes(n, num_views);
+    NH_REQUIRE(tmp && tmp_bytes >= need, "%s: tmp must hold nerfhip_exposure_grad_tmp_bytes(n, num_views) = %lld bytes", what,
+               (long long)need);
+    PoseViewsArgs p;
+    memset(&p, 0, sizeof(p));
+    const int64_t slots = n / PV_THREADS + num_views;
+    float* part = (float*)tmp;
+    if (n > 0) {
+        p.a.inds = inds, p.a.n = n;
+        p.num_views = num_views, p.hw = hw;
+        p.cnt = (int*)tmp + slots * 6, p.off = p.cnt + num_views, p.list = p.off + num_views;
+        ExpoArgs x = {rgb_coarse, rgb_fine, target, target_stride, n, grad_scale, expo, mask, part};
+        NH_LAUNCH(k_pose_views_group, num_views, PV_THREADS, 0, stream, p);
+        rc = nh_launch_status(what);
+        if (rc) return rc;
+        NH_LAUNCH(k_expo_part, slots, PV_THREADS, 0, stream, p, x);
+        rc = nh_launch_status(what);
+        if (rc) return rc;
+    }
+    NH_LAUNCH_NAMED("k_expo_sum", k_pose_vjp_sum<6>, num_views, 6 * 64, 0, stream, (const float*)part, 0, (const int*)p.cnt,
+                    (const int*)p.off, g_expo);  // (n == 0: cnt is NULL, zeros)
+    return nh_launch_status(what);
+}
 
 extern "C" int64_t nerfhip_pose_grad_views_tmp_bytes(int64_t n, int num_views) {
     int64_t slots;

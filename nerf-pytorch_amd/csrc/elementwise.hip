@@ -19,9 +19,9 @@ void nh_set_error(const char* fmt, ...) {
 extern "C" const char* nerfhip_last_error(void) { return g_err; }
 extern "C" int nerfhip_version(void) {
 #ifdef NH_DIAG  // (make variant: an A/B or diagnostic build -- nh_diag.h; the Python package refuses it)
-    return 111 + NH_DIAG_VERSION_FLAG;
+    return 112 + NH_DIAG_VERSION_FLAG;
 #else
-    return 111;  // (102: round 6 -- the compacted backward's three entry points; 103: + the fused backward modes 3 / 4 of 64-wide nets; 104: + mode 5;
+    return 112;  // (102: round 6 -- the compacted backward's three entry points; 103: + the fused backward modes 3 / 4 of 64-wide nets; 104: + mode 5;
                  // 105: + the pose VJP, nerfhip_pose_grad_tmp_bytes / nerfhip_ray_bundle_bwd / nerfhip_select_rays_bwd;
                  // 106: + batches over a stack of views, nerfhip_select_rays_views / _views_bwd / nerfhip_pose_grad_views_tmp_bytes;
                  // 107: + the camera table, nerfhip_pose_table_fwd / nerfhip_pose_table_bwd;
@@ -30,7 +30,8 @@ extern "C" int nerfhip_version(void) {
                  // 110: + device intrinsics, nerfhip_select_rays_views_intr / _intr_bwd / nerfhip_intr_grad_views_tmp_bytes /
                  //      nerfhip_ray_bundle_intr / nerfhip_intrinsics_fwd / nerfhip_intrinsics_bwd;
                  // 111: + lens distortion, nerfhip_select_rays_views_dist / _dist_bwd / nerfhip_dist_grad_views_tmp_bytes /
-                 //      nerfhip_ray_bundle_dist)
+                 //      nerfhip_ray_bundle_dist;
+                 // 112: + per-view exposure, nerfhip_mse_loss_views_fwd_bwd / nerfhip_exposure_bwd / nerfhip_exposure_grad_tmp_bytes)
 #endif
 }
 extern "C" int nerfhip_is_emulated(void) {
@@ -556,23 +557,77 @@ extern "C" int nerfhip_window_grads(float* g_params, const uint8_t* codes, int64
 // ---- loss (train_nerf.py:244-258) ------------------------------------------------------------------------------------
 // One workgroup; deterministic fp64 tree.  loss_out = {mse(rgb_c, tgt), mse(rgb_f, tgt), sum}; cotangents are
 // 2 (rgb - tgt) / (3 n) * grad_scale.
-NH_KERNEL void k_mse_loss(const float* __restrict__ rc, const float* __restrict__ rf, const float* __restrict__ tgt,
-                          int tstride, int64_t n, float grad_scale, float* __restrict__ gc, float* __restrict__ gf,
-                          float* __restrict__ loss_out) {
-    NH_SHARED double red[2][16];
+// Under a per-view exposure table (EXPO; nerfhip_mse_loss_views_fwd_bwd): expo [V][6] = (s_r s_g s_b b_r b_g b_b) per view, ray r
+// belongs to view inds[r] / hw (an index outside [0, V hw): the identity).  Per ray, channel and net, in this order, every
+// operation one fp32 rounding unless said:
+//     e = (float)exp((double)s)      (one fp64 exp, then the final rounding; s = b = 0 for a ray of no view: e = 1, q = p, d = p - t)
+//     q = e * p;   d = (q + b) - t;   sum += (double)d * (double)d  (exact product, fp64 sum);   g_rgb = (d * k) * e
+// with k = 2 / (3 n) * grad_scale as above.  The elements of a thread and their order of summation, the wave and block sums and the
+// final division are the plain kernel's.
+constexpr int MSE_VIEWS_BATCH = 4;
+template <bool EXPO>
+NH_DEVICE void mse_loss_body(double (*red)[16], const float* __restrict__ rc, const float* __restrict__ rf, const float* __restrict__ tgt,
+                             int tstride, int64_t n, float grad_scale, const int64_t* __restrict__ inds, int64_t hw,
+                             const float* __restrict__ expo, int64_t population, float* __restrict__ gc, float* __restrict__ gf,
+                             float* __restrict__ loss_out) {
     double sc = 0.0, sf = 0.0;
     const float k = 2.0f / (float)(3 * n) * grad_scale;
-    for (int64_t i = threadIdx.x; i < n * 3; i += blockDim.x) {
-        int64_t r = i / 3;
-        int c = (int)(i % 3);
-        float t = tgt[r * tstride + c];
-        float dc = rc[i] - t;
-        sc += (double)dc * (double)dc;
-        if (gc) gc[i] = dc * k;
-        if (rf) {
-            float df = rf[i] - t;
-            sf += (double)df * (double)df;
-            if (gf) gf[i] = df * k;
+    if (EXPO) {
+        // the plain loop's elements in the plain loop's order, MSE_VIEWS_BATCH of a thread's elements at a time: their indices, targets
+        // and rgb are loaded together, then their rows of the table, so that an element's three dependent loads (index -> row -> use)
+        // cost a batch one round trip each.  An element past the end repeats the last one's loads and is not used.
+        const int64_t n3 = n * 3;
+        const float* __restrict__ rfp = rf ? rf : rc;  // (loaded unconditionally; unused without a fine net)
+        for (int64_t i0 = threadIdx.x; i0 < n3; i0 += (int64_t)MSE_VIEWS_BATCH * blockDim.x) {
+            int64_t at[MSE_VIEWS_BATCH], g[MSE_VIEWS_BATCH];
+            int ch[MSE_VIEWS_BATCH];
+            float t[MSE_VIEWS_BATCH], pc[MSE_VIEWS_BATCH], pf[MSE_VIEWS_BATCH], s[MSE_VIEWS_BATCH], o[MSE_VIEWS_BATCH];
+#pragma unroll
+            for (int u = 0; u < MSE_VIEWS_BATCH; ++u) {
+                const int64_t i = i0 + (int64_t)u * blockDim.x;
+                at[u] = i < n3 ? i : n3 - 1;
+                const int64_t r = at[u] / 3;
+                ch[u] = (int)(at[u] % 3);
+                g[u] = inds[r];
+                t[u] = tgt[r * tstride + ch[u]];
+                pc[u] = rc[at[u]];
+                pf[u] = rfp[at[u]];
+            }
+#pragma unroll
+            for (int u = 0; u < MSE_VIEWS_BATCH; ++u) {
+                const bool in_view = g[u] >= 0 && g[u] < population;
+                const float* row = expo + (in_view ? g[u] / hw : 0) * 6;
+                s[u] = in_view ? row[ch[u]] : 0.0f;   // (exp(0) = 1 and b = 0: the identity)
+                o[u] = in_view ? row[3 + ch[u]] : 0.0f;
+            }
+#pragma unroll
+            for (int u = 0; u < MSE_VIEWS_BATCH; ++u) {
+                const int64_t i = i0 + (int64_t)u * blockDim.x;
+                if (i >= n3) break;
+                const float e = (float)exp((double)s[u]);
+                float dc = (e * pc[u] + o[u]) - t[u];
+                sc += (double)dc * (double)dc;
+                if (gc) gc[i] = (dc * k) * e;
+                if (rf) {
+                    float df = (e * pf[u] + o[u]) - t[u];
+                    sf += (double)df * (double)df;
+                    if (gf) gf[i] = (df * k) * e;
+                }
+            }
+        }
+    } else {
+        for (int64_t i = threadIdx.x; i < n * 3; i += blockDim.x) {
+            int64_t r = i / 3;
+            int c = (int)(i % 3);
+            float t = tgt[r * tstride + c];
+            float dc = rc[i] - t;
+            sc += (double)dc * (double)dc;
+            if (gc) gc[i] = dc * k;
+            if (rf) {
+                float df = rf[i] - t;
+                sf += (double)df * (double)df;
+                if (gf) gf[i] = df * k;
+            }
         }
     }
     sc = nh_wave_sum_d(sc);
@@ -597,6 +652,21 @@ NH_KERNEL void k_mse_loss(const float* __restrict__ rc, const float* __restrict_
     }
 }
 
+NH_KERNEL void k_mse_loss(const float* __restrict__ rc, const float* __restrict__ rf, const float* __restrict__ tgt,
+                          int tstride, int64_t n, float grad_scale, float* __restrict__ gc, float* __restrict__ gf,
+                          float* __restrict__ loss_out) {
+    NH_SHARED double red[2][16];
+    mse_loss_body<false>(red, rc, rf, tgt, tstride, n, grad_scale, nullptr, 1, nullptr, 0, gc, gf, loss_out);
+}
+
+NH_KERNEL void k_mse_loss_views(const float* __restrict__ rc, const float* __restrict__ rf, const float* __restrict__ tgt,
+                                int tstride, int64_t n, float grad_scale, const int64_t* __restrict__ inds, int64_t hw,
+                                const float* __restrict__ expo, int64_t population, float* __restrict__ gc, float* __restrict__ gf,
+                                float* __restrict__ loss_out) {
+    NH_SHARED double red[2][16];
+    mse_loss_body<true>(red, rc, rf, tgt, tstride, n, grad_scale, inds, hw, expo, population, gc, gf, loss_out);
+}
+
 extern "C" int nerfhip_mse_loss_fwd_bwd(const float* rgb_coarse, const float* rgb_fine, const float* target,
                                         int target_stride, int64_t n, float grad_scale, float* g_rgb_coarse,
                                         float* g_rgb_fine, float* loss_out, nerfhip_stream_t stream) {
@@ -604,6 +674,32 @@ extern "C" int nerfhip_mse_loss_fwd_bwd(const float* rgb_coarse, const float* rg
     NH_LAUNCH(k_mse_loss, 1, 1024, 0, stream, rgb_coarse, rgb_fine, target, target_stride, n, grad_scale, g_rgb_coarse,
               g_rgb_fine, loss_out);
     return nh_launch_status("mse_loss");
+}
+
+// what both exposure entry points ask of the table and the indices (the limits of the views forms, dataio.hip)
+int nh_exposure_check(const char* what, const int64_t* inds, int64_t n, int64_t hw, const float* expo, int num_views) {
+    NH_REQUIRE(expo, "%s: expo must not be NULL (without a table the entry point is nerfhip_mse_loss_fwd_bwd)", what);
+    NH_REQUIRE(num_views >= 1 && num_views <= NERFHIP_MAX_VIEWS, "%s: num_views must be 1 .. %d (got %d)", what, NERFHIP_MAX_VIEWS,
+               num_views);
+    NH_REQUIRE(hw >= 1 && hw <= ((int64_t)1 << 32) && (int64_t)num_views * hw <= ((int64_t)1 << 32),
+               "%s: hw must be >= 1 and num_views * hw must not exceed 2^32 (got hw %lld)", what, (long long)hw);
+    NH_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "%s: n must be 0 .. 2^31 - 1 (got %lld)", what, (long long)n);
+    NH_REQUIRE(n == 0 || inds, "%s: inds must not be NULL", what);
+    return NERFHIP_OK;
+}
+
+extern "C" int nerfhip_mse_loss_views_fwd_bwd(const float* rgb_coarse, const float* rgb_fine, const float* target, int target_stride,
+                                              int64_t n, float grad_scale, const int64_t* inds, int64_t hw, const float* expo,
+                                              int num_views, float* g_rgb_coarse, float* g_rgb_fine, float* loss_out,
+                                              nerfhip_stream_t stream) {
+    const char* what = "mse_loss_views";
+    int rc = nh_exposure_check(what, inds, n, hw, expo, num_views);
+    if (rc) return rc;
+    NH_REQUIRE(rgb_coarse && target && loss_out && n > 0, "%s: bad arguments", what);
+    NH_REQUIRE(target_stride >= 3, "%s: target_stride must be >= 3 (got %d)", what, target_stride);
+    NH_LAUNCH(k_mse_loss_views, 1, 1024, 0, stream, rgb_coarse, rgb_fine, target, target_stride, n, grad_scale, inds, hw, expo,
+              (int64_t)num_views * hw, g_rgb_coarse, g_rgb_fine, loss_out);
+    return nh_launch_status(what);
 }
 
 // ---- Adam (torch.optim.Adam single-tensor step; train_nerf.py:141-143,261) -------------------------------------------

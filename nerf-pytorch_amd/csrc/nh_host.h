@@ -6,6 +6,8 @@
 #include "nh_device.h"
 
 void nh_set_error(const char* fmt, ...);
+// the argument checks shared by the two exposure entry points (elementwise.hip; the other one is in dataio.hip)
+int nh_exposure_check(const char* what, const int64_t* inds, int64_t n, int64_t hw, const float* expo, int num_views);
 
 #define NH_REQUIRE(cond, ...)          \
     do {                               \

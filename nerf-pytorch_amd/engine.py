@@ -25,7 +25,7 @@ import torch
 from . import _lib as L
 from . import backward_mode as BM
 from . import train_utils as TU
-from .cameras import Distortion, Intrinsics, check_device_vector
+from .cameras import Distortion, Exposure, Intrinsics, check_device_vector
 from .nerf_helpers import linspace01
 from .parallel import allreduce_gradients, shard_bounds
 
@@ -203,7 +203,8 @@ class TrainEngine:
             raise NotImplementedError("TrainEngine: %s with world size %d is not implemented (the pose / ray gradient of a "
                                       "data-parallel step would need its own all-reduce); run it with one rank" % (what, self.world))
 
-    def forward_backward(self, rays, target, ray_offset=0, global_rays=None, draws=None, ray_grad=None, frozen=False, step=None):
+    def forward_backward(self, rays, target, ray_offset=0, global_rays=None, draws=None, ray_grad=None, frozen=False, step=None,
+                         exposure=None):
         """rays: (n, 8|11) packed rows on the device; target: (n, >=3), row stride free (an RGBA image's [..., :3] view
         works).  Leaves the summed-over-this-rank gradient in self.grad and {coarse_mse, fine_mse, sum} in self.loss
         (device); with world > 1 the gradient all-reduces are in flight when this returns (optimizer_step waits).
@@ -222,10 +223,27 @@ class TrainEngine:
         parameter gradient: self.grad is not touched, no gradient is windowed or all-reduced; same streams, same two buffers.
         step: the counter the in-kernel draws are keyed by (default: step_count; the localisation steps pass localize_count).
         TrainEngine(backward="auto") is a policy of the training backward (its thresholds weigh the weight gradient's cost): a frozen
-        step leaves each net in the mode its last training step chose and counts nothing in backward_modes_used."""
+        step leaves each net in the mode its last training step chose and counts nothing in backward_modes_used.
+        exposure: None, or (X, inds, hw): a cameras.Exposure on the engine's device, the int64 global indices of the batch (one per ray,
+        what select_training_rays_views returned) and hw = height * width: both nets' losses are taken under X's per-view table
+        (nerfhip_mse_loss_views_fwd_bwd in place of the plain loss launch, same streams), and after the two streams have joined
+        X.backward(...) leaves d(loss)/d(table) in X.g_expo (three launches on the main stream, reading the engine's own rgb buffers).
+        The exposure sits behind the render: it asks for no ray gradient.  With frozen=True and no ray_grad the step is the
+        test-time fit: the two forwards, the two losses and the table gradient, no render backward.  One rank only."""
         self._check_inputs(rays, target)
-        if frozen and ray_grad is None:
-            raise RuntimeError("TrainEngine: forward_backward(frozen=True) computes the ray gradient alone: pass ray_grad=...")
+        if frozen and ray_grad is None and exposure is None:
+            raise RuntimeError("TrainEngine: forward_backward(frozen=True) computes the ray gradient alone: pass ray_grad=... "
+                               "(or exposure=...: the fit of the exposure table alone)")
+        ex_inds = ex_hw = None
+        if exposure is not None:
+            self._no_pose_grad_across_ranks("exposure")
+            exposure, ex_inds, ex_hw = exposure
+            self._check_exposure(exposure, None)
+            if (not isinstance(ex_inds, torch.Tensor) or ex_inds.device != self.dev or ex_inds.dtype != torch.int64
+                    or tuple(ex_inds.shape) != (rays.shape[0],) or not ex_inds.is_contiguous()):
+                raise RuntimeError("TrainEngine: exposure=(X, inds, hw) needs inds as a contiguous int64 (%d) tensor on %s"
+                                   % (rays.shape[0], self.dev))
+            ex_hw = int(ex_hw)
         if ray_grad is not None:
             self._no_pose_grad_across_ranks("ray_grad")
             if not check_device_vector(ray_grad, rays.shape, self.dev):
@@ -277,7 +295,13 @@ class TrainEngine:
         def net_pass(part, rgb, g_rgb, cot, loss, grad, model, tmp, g_rays, stream):
             """One net's loss, then its backward in the step's form, then its window gradients (behind its backward, ahead of its
             all-reduce), on `stream`."""
-            lib.mse_loss_fwd_bwd(rgb.data_ptr(), None, target.data_ptr(), tstride, n, gscale, g_rgb.data_ptr(), None, loss.data_ptr(), stream)
+            if exposure is None:
+                lib.mse_loss_fwd_bwd(rgb.data_ptr(), None, target.data_ptr(), tstride, n, gscale, g_rgb.data_ptr(), None, loss.data_ptr(), stream)
+            else:
+                lib.mse_loss_views_fwd_bwd(rgb.data_ptr(), None, target.data_ptr(), tstride, n, gscale, ex_inds.data_ptr(), ex_hw,
+                                           exposure.expo.data_ptr(), exposure.num_views, g_rgb.data_ptr(), None, loss.data_ptr(), stream)
+            if ray_grad is None and frozen:   # (the fit of the exposure table alone: no render backward)
+                return
             if ray_grad is None:
                 lib.render_bwd_parts(*bwd_head, C.byref(cot), *bwd_tail, part, stream)
             else:
@@ -320,6 +344,8 @@ class TrainEngine:
                 self.loss.copy_(self._loss_c)
             if self.backward == "auto" and not frozen:   # ({kept, total} of every net that ran over a list in the step just issued)
                 self._stats.request(((name, self._stats_words(name)) for name, m in self._nets if m.backward_compaction in BM.BUILDS_LIST), main)
+            if exposure is not None:   # (main stream, behind both nets' passes)
+                exposure.backward(b["rgb_c"], b["rgb_f"] if nf > 0 else None, target, ex_inds, ex_hw, gscale)
 
     # ---- backward="auto" (the policy and its thresholds: backward_mode.choose) ----------------------------------------------------
     @staticmethod
@@ -429,7 +455,7 @@ class TrainEngine:
         return self.loss
 
     def step_on_image(self, image, pose, height, width, focal_length, options, num_random_rays, lr=None, global_rays=None,
-                      pose_grad=None, intrinsics=None, distortion=None):
+                      pose_grad=None, intrinsics=None, distortion=None, exposure=None):
         """One whole iteration of the reference's loop body (train_nerf.py:210-270) on a resident training image:
         on-device selection of this rank's distinct pixels (ranks take disjoint slices of one permutation keyed by
         (seed, iteration)), their rays and targets, then `step`.  No host work besides launches.
@@ -443,7 +469,9 @@ class TrainEngine:
         torch.autograd.backward(pose_expr[:3, :4], pose_grad).  One rank only.
         intrinsics: None, or a cameras.Intrinsics on the engine's device: the rays are generated from its (fx, fy, cx, cy), read on
         the device, and the step learns them -- see step_on_views.  `focal_length` must still be passed: it fixes the NDC constants.
-        distortion: None, or a cameras.Distortion on the engine's device -- see step_on_views."""
+        distortion: None, or a cameras.Distortion on the engine's device -- see step_on_views.
+        exposure: refused -- a single image has no view axis for a per-view table: use step_on_views."""
+        self._no_exposure_on_image("step_on_image", exposure)
         if pose_grad is not None:
             self._no_pose_grad_across_ranks("pose_grad")
             self._check_pose_grads("pose_grad", pose_grad, (3, 4))
@@ -451,7 +479,7 @@ class TrainEngine:
                                        pose_grad, None, intrinsics, False, distortion)
 
     def step_on_views(self, images, poses, height, width, focal_length, options, num_random_rays, lr=None, global_rays=None,
-                      pose_grads=None, cameras=None, intrinsics=None, distortion=None):
+                      pose_grads=None, cameras=None, intrinsics=None, distortion=None, exposure=None):
         """step_on_image over a resident stack of views: this rank's rays are drawn from ALL of `images` (V, H, W, 3|4) with the
         rays of each generated from its own row of `poses` (V, >=3, 4) -- train_utils.select_training_rays_views --, then `step`.
         Same rank slicing (first = rank * n, or the shard_bounds slice of `global_rays`) over the permutation of V * H * W, same
@@ -472,12 +500,16 @@ class TrainEngine:
         rank only.
         distortion: None, or a cameras.Distortion on the engine's device: the rays are undistorted under its (k1, k2, p1, p2), read on
         the device, and the step learns them, with or without `intrinsics` and `cameras`: the same ONE VJP call also fills
-        distortion.g_dist, and distortion.step() follows intrinsics.step().  Alone it turns the ray gradient on.  One rank only."""
+        distortion.g_dist, and distortion.step() follows intrinsics.step().  Alone it turns the ray gradient on.  One rank only.
+        exposure: None, or a cameras.Exposure of V views on the engine's device: both losses are taken under its per-view colour gain
+        and offset (forward_backward(exposure=...)) and the step learns the table: X.backward() after the two streams joined,
+        X.step() last (after distortion.step()).  Alone or with any of the above.  It sits behind the render and does NOT turn the
+        ray gradient on: alone, the step is selection, forward_backward, optimizer_step, X.step().  One rank only."""
         return self._step_on_selection((height, width, focal_length, options), poses, images, True, num_random_rays, lr, global_rays,
-                                       pose_grads, cameras, intrinsics, False, distortion)
+                                       pose_grads, cameras, intrinsics, False, distortion, exposure)
 
     def localize_on_image(self, image, pose, height, width, focal_length, options, num_random_rays, pose_grad=None, intrinsics=None,
-                          distortion=None):
+                          distortion=None, exposure=None):
         """step_on_image(pose_grad=...) for FROZEN nets (camera localisation against a trained field): the same selection, forward and
         pose VJP, with the render backward w.r.t. the rays alone (forward_backward(frozen=True)) and no optimizer step.  Nothing of
         the nets or their optimiser moves -- flat_params, exp_avg, exp_avg_sq, grad, the packed images and step_count are what they
@@ -485,7 +517,9 @@ class TrainEngine:
         pose_grad: a contiguous float32 (3, 4) tensor on the engine's device, overwritten with d(loss)/d(pose[:3, :4]).  One rank only.
         intrinsics: None, or a cameras.Intrinsics (see step_on_views): its values are learned against the frozen field; then
         pose_grad may be None.
-        distortion: None, or a cameras.Distortion (see step_on_views), learned against the frozen field; then pose_grad may be None."""
+        distortion: None, or a cameras.Distortion (see step_on_views), learned against the frozen field; then pose_grad may be None.
+        exposure: refused -- a single image has no view axis for a per-view table: use localize_on_views."""
+        self._no_exposure_on_image("localize_on_image", exposure)
         self._no_pose_grad_across_ranks("localize_on_image")
         if pose_grad is None and intrinsics is None and distortion is None:
             raise RuntimeError("TrainEngine: localize_on_image needs pose_grad=... or intrinsics=... (or distortion=...)")
@@ -495,17 +529,21 @@ class TrainEngine:
                                        pose_grad, None, intrinsics, True, distortion)
 
     def localize_on_views(self, images, poses, height, width, focal_length, options, num_random_rays, pose_grads=None, cameras=None,
-                          intrinsics=None, distortion=None):
+                          intrinsics=None, distortion=None, exposure=None):
         """step_on_views for FROZEN nets (see localize_on_image): with pose_grads (V, 3, 4) the step writes d(loss)/d(poses[v, :3, :4])
         of every view; with cameras=T (then poses must be None and pose_grads must not be given) the table composes its poses, takes
         the gradients in its own buffer, pulls them back to its twists (T.backward()) and steps them (T.step()) -- the nets stay put.
         intrinsics: None, or a cameras.Intrinsics (see step_on_views): its values are learned against the frozen field, alone or
-        together with the poses.  distortion: None, or a cameras.Distortion, in the same way.  One rank only."""
+        together with the poses.  distortion: None, or a cameras.Distortion, in the same way.
+        exposure: None, or a cameras.Exposure (see step_on_views), fitted against the frozen field.  Alone it is the test-time fit of
+        a held-out view's exposure: the two forwards, the two losses under the table, the table gradient and X.step() -- no render
+        backward at all.  One rank only."""
         self._no_pose_grad_across_ranks("localize_on_views")
-        if cameras is None and pose_grads is None and intrinsics is None and distortion is None:
-            raise RuntimeError("TrainEngine: localize_on_views needs pose_grads=..., cameras=... or intrinsics=... (or distortion=...)")
+        if cameras is None and pose_grads is None and intrinsics is None and distortion is None and exposure is None:
+            raise RuntimeError("TrainEngine: localize_on_views needs pose_grads=..., cameras=... or intrinsics=... (or distortion=... "
+                               "or exposure=...)")
         return self._step_on_selection((height, width, focal_length, options), poses, images, True, num_random_rays, None, None,
-                                       pose_grads, cameras, intrinsics, True, distortion)
+                                       pose_grads, cameras, intrinsics, True, distortion, exposure)
 
     def _resolve_cameras(self, poses, pose_grads, cameras):
         """(poses, pose_grads) of a step over views: the caller's, checked; or, with cameras=T, the table's composed poses and its own
@@ -527,8 +565,23 @@ class TrainEngine:
     def _check_pose_grads(self, name, g, shape):
         check_device_vector(g, shape, self.dev, "TrainEngine: " + name)
 
+    @staticmethod
+    def _no_exposure_on_image(what, exposure):
+        if exposure is not None:
+            raise RuntimeError("TrainEngine: %s takes no exposure=...: a single image has no view axis for a per-view table (use "
+                               "the _on_views form with a stack of one)" % what)
+
+    def _check_exposure(self, exposure, num_views):
+        """exposure=X of a step: a cameras.Exposure on the engine's device, of `num_views` views (None: not checked)."""
+        if not isinstance(exposure, Exposure):
+            raise RuntimeError("TrainEngine: exposure must be a cameras.Exposure (got %s)" % type(exposure).__name__)
+        if exposure.dev != self.dev:
+            raise RuntimeError("TrainEngine: the exposure table lives on %s, the engine on %s" % (exposure.dev, self.dev))
+        if num_views is not None and exposure.num_views != num_views:
+            raise RuntimeError("TrainEngine: the exposure table holds %d views, the step draws from %d" % (exposure.num_views, num_views))
+
     def _step_on_selection(self, scene, poses, images, views, num_random_rays, lr, global_rays, pose_grads, cameras, intrinsics, frozen,
-                           distortion=None):
+                           distortion=None, exposure=None):
         """The step of step_on_image / step_on_views / localize_on_* behind their own argument checks.  scene: (height, width,
         focal_length, options); views: whether `poses` / `images` carry a view axis.  In launch order: the checks of intrinsics=I and
         distortion=D, then I.values() and D.values(); cameras=T checked, T.poses() (_resolve_cameras); this rank's slice of the
@@ -537,9 +590,14 @@ class TrainEngine:
         `pose_grads` (when asked), I.g_intr and D.g_dist, T.backward(), I.backward(), optimizer_step, T.step(), I.step(), D.step().
         frozen (localize_on_*): the ray gradient alone and no optimizer_step; the selection and the draws are keyed by
         localize_count, which advances.  Without intrinsics (distortion) no intrinsics (distortion) keyword is passed on: the step
-        reaches the entry points of the selection without them."""
+        reaches the entry points of the selection without them.
+        exposure=X (views only): checked first, ahead of intrinsics and distortion; forward_backward takes (X, the selection's indices, height * width) --
+        alone WITHOUT a ray gradient --, and X.step() comes last, after D.step()."""
         height, width, focal_length, options = scene
         kw, vjp_kw = {}, {}
+        if exposure is not None:
+            self._no_pose_grad_across_ranks("exposure")
+            self._check_exposure(exposure, images.shape[0] if isinstance(images, torch.Tensor) and images.dim() == 4 else None)
         if intrinsics is not None:
             if not isinstance(intrinsics, Intrinsics):
                 raise RuntimeError("TrainEngine: intrinsics must be a cameras.Intrinsics (got %s)" % type(intrinsics).__name__)
@@ -572,13 +630,17 @@ class TrainEngine:
         count = self.localize_count if frozen else self.step_count
         with torch.no_grad():
             rays, target, used = select(height, width, focal_length, poses, images, n, options, seed=self.seed, step=count, first=first, **kw)
-        if pose_grads is None and intrinsics is None and distortion is None:
+        want_rays = pose_grads is not None or intrinsics is not None or distortion is not None
+        if not want_rays and exposure is None:
             return self.step(rays, target, ray_offset=first, lr=lr, global_rays=global_rays)
-        self._ray_grad_bufs(n, own=True)
-        self.forward_backward(rays, target, first, global_rays, None, self._ray_grad, frozen, count)
-        vjp = TU.select_training_rays_views_bwd if views else TU.select_training_rays_bwd
-        with torch.cuda.device(self.dev):
-            vjp(height, width, focal_length, poses, used, self._ray_grad, options, self.ray_grad_coarse, out=pose_grads, **vjp_kw)
+        ex = None if exposure is None else (exposure, used, int(height) * int(width))
+        if want_rays:
+            self._ray_grad_bufs(n, own=True)
+        self.forward_backward(rays, target, first, global_rays, None, self._ray_grad if want_rays else None, frozen, count, ex)
+        if want_rays:
+            vjp = TU.select_training_rays_views_bwd if views else TU.select_training_rays_bwd
+            with torch.cuda.device(self.dev):
+                vjp(height, width, focal_length, poses, used, self._ray_grad, options, self.ray_grad_coarse, out=pose_grads, **vjp_kw)
         if cameras is not None:
             cameras.backward()
         if intrinsics is not None:
@@ -593,6 +655,8 @@ class TrainEngine:
             intrinsics.step()
         if distortion is not None:
             distortion.step()
+        if exposure is not None:
+            exposure.step()
         return self.loss
 
     @staticmethod

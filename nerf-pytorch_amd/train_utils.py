@@ -622,6 +622,78 @@ def select_training_rays_views_bwd(height, width, focal_length, poses, select_in
                        out_intrinsics, want_poses, distortion, out_distortion, distortion_mask)
 
 
+class _ExposureLoss(torch.autograd.Function):
+    """exposure_mse_loss as ONE node: the forward is the launch of nerfhip_mse_loss_views_fwd_bwd (which also leaves the two rgb
+    cotangents), the backward hands those out scaled by the incoming cotangents and, for a table that requires grad, calls
+    nerfhip_exposure_bwd."""
+
+    @staticmethod
+    def forward(ctx, rgb_coarse, rgb_fine, target, inds, hw, table):
+        lib = L.get_lib()
+        n = rgb_coarse.shape[0]
+        rc = rgb_coarse.detach().float().contiguous()
+        rf = None if rgb_fine is None else rgb_fine.detach().float().contiguous()
+        tgt = target.detach().float()
+        if tgt.dim() != 2 or tgt.shape[1] < 3 or tgt.stride(1) != 1:
+            tgt = tgt[..., :3].reshape(n, 3).contiguous()
+        tab = table.detach().float().contiguous()
+        if tab.dim() != 2 or tab.shape[1] != 6:
+            raise RuntimeError("exposure_mse_loss: table must be (V, 6) (got shape %s)" % (tuple(table.shape),))
+        ind = inds.to(torch.int64).contiguous()
+        mk = lambda *shape: torch.empty(shape, dtype=torch.float32, device=rc.device)  # noqa: E731
+        gc, gf, loss = mk(n, 3), (mk(n, 3) if rf is not None else None), mk(3)
+        with L.launch_on(rc, rf, tgt, ind, tab, gc, gf, loss) as st:
+            lib.mse_loss_views_fwd_bwd(rc.data_ptr(), rf.data_ptr() if rf is not None else None, tgt.data_ptr(), tgt.stride(0), n, 1.0,
+                                       ind.data_ptr(), int(hw), tab.data_ptr(), tab.shape[0], gc.data_ptr(),
+                                       gf.data_ptr() if gf is not None else None, loss.data_ptr(), st)
+        ctx.keep = (rc, rf, tgt, ind, int(hw), tab, gc, gf)
+        ctx.dtypes = (rgb_coarse.dtype, None if rgb_fine is None else rgb_fine.dtype, table.dtype, tuple(table.shape))
+        ctx.set_materialize_grads(False)
+        return loss[0], loss[1]
+
+    @staticmethod
+    def backward(ctx, g_lc, g_lf):
+        rc, rf, tgt, ind, hw, tab, gc, gf = ctx.keep
+        dt_c, dt_f, dt_t, tab_shape = ctx.dtypes
+        need = ctx.needs_input_grad
+        g_rc = g_rf = g_tab = None
+        if need[0] and g_lc is not None:
+            g_rc = (gc * g_lc).to(dt_c)
+        if rf is not None and need[1] and g_lf is not None:
+            g_rf = (gf * g_lf).to(dt_f)
+        if need[5]:
+            # the table gradient is linear in the two nets' terms.  `(coarse + fine).backward()` hands both outputs ONE cotangent
+            # tensor: known equal without reading it, so one call (cotangent 1: the entry point's bits).  Two tensors may still be
+            # equal; reading them would synchronise, so all three calls run and the device selects.
+            from .cameras import exposure_grad
+            zero = torch.zeros((), device=rc.device)
+            a = zero if g_lc is None else g_lc
+            b = zero if (g_lf is None or rf is None) else g_lf
+            if rf is None:
+                g_tab = exposure_grad(rc, None, tgt, ind, hw, tab) * a
+            elif a is b or (a.data_ptr() == b.data_ptr() and a.shape == b.shape and a.stride() == b.stride()):
+                g_tab = exposure_grad(rc, rf, tgt, ind, hw, tab) * a
+            else:
+                g_tab = torch.where(a == b, exposure_grad(rc, rf, tgt, ind, hw, tab) * a,
+                                    exposure_grad(rc, None, tgt, ind, hw, tab) * a + exposure_grad(rf, None, tgt, ind, hw, tab) * b)
+            g_tab = g_tab.reshape(tab_shape).to(dt_t)
+        return g_rc, g_rf, None, None, None, g_tab
+
+
+def exposure_mse_loss(rgb_coarse, rgb_fine, target, inds, hw, table):
+    """(coarse_mse, fine_mse) = (mse_loss(rgb_coarse', target), mse_loss(rgb_fine', target)) with rgb' = exp(s) * rgb + b under the
+    per-view exposure `table` (V, 6) -- the drop-in for the two mse_loss lines of the reference's loop (train_nerf.py:244-258) on a
+    batch drawn by select_training_rays_views: `inds` are the global indices it returned, hw = height * width.  rgb_fine=None is the
+    coarse-only net (fine_mse is then 0).  One autograd node, one launch in the forward; the backward gives the kernel's rgb
+    cotangents times the incoming cotangents (both 1, as in `(coarse + fine).backward()`: nerfhip_mse_loss_views_fwd_bwd's and
+    nerfhip_exposure_bwd's bits; anything else costs one multiply per element on top), and fills `table.grad` when the table requires
+    grad (Exposure.values() of an object stepped by hand, or a leaf of one's own optimiser).  No host synchronisation: when the two
+    outputs get one and the same cotangent tensor, as `(coarse + fine).backward()` gives them, the table gradient is ONE
+    nerfhip_exposure_bwd call; when they get two tensors it is three (both nets, and each net alone, scaled), selected on the device
+    by whether the two cotangents are equal."""
+    return _ExposureLoss.apply(rgb_coarse, rgb_fine, target, inds, hw, table)
+
+
 def select_cached_training_rays(cache_dict, num_random_rays, options, select_inds=None, seed=0, step=0, first=0):
     """The cached branch (train_nerf.py:175-194): rows of cache_dict["ray_bundle"] (2, ., 3) and of
     cache_dict["target"][..., :3], both already on the device."""
