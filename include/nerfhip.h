@@ -415,6 +415,69 @@ int nerfhip_render_grad_rays(nerfhip_plan_t plan_coarse, nerfhip_plan_t plan_fin
                              const float* params_coarse, const float* params_fine, void* tmp, int64_t tmp_bytes, float* g_rays,
                              nerfhip_stream_t stream);
 
+/* ---- occupancy grid: the inference render skips empty space (Instant-NGP / NerfAcc / PlenOctrees style) ------------------------
+ * One bit per cell of an axis-aligned box, built once from the trained density.  A sample whose point falls into an empty cell is
+ * never sent through the MLP: its raw row becomes the EMPTY ROW (0, 0, 0, NERFHIP_OCC_EMPTY_RAW), whose sigma_a =
+ * relu(raw[3] + noise) is exactly 0 -- a finite value on purpose: no 0 * inf can arise downstream.  Inference only.
+ *
+ * Cell of point p: i_a = (int)floorf((p_a - lo_a) * inv_a), inv_a = res_a / (hi_a - lo_a) formed once on the host in fp32 (as
+ * (float)res_a / (hi_a - lo_a)); bit index b = (i_z * res_y + i_y) * res_x + i_x lives in word b >> 5 at position b & 31.  The point
+ * is the one the MLP kernels encode: p_a = ro_a + rd_a * z (an fp32 multiply, then an fp32 add) of the packed ray row -- for NDC rays
+ * the NDC-space point.  A point outside the box counts as `outside` says; a sample with a NaN coordinate counts as occupied (it
+ * propagates as in the dense path).  1 <= res_a <= 512, res_x * res_y * res_z a multiple of 32, hi_a > lo_a. */
+#define NERFHIP_OCC_EMPTY_RAW (-1e30f)
+#define NERFHIP_OCC_MAX_RES 512
+typedef struct nerfhip_occ_grid {
+    const uint32_t* bits; /* dev [res_x * res_y * res_z / 32] */
+    float lo[3], hi[3];
+    int res[3];
+    int outside; /* a point outside the box: 0 = empty, 1 = occupied */
+} nerfhip_occ_grid;
+
+/* The per-sample predicate alone (tests, diagnostics): flags_u8 dev [n * S], 1 = the cell of sample (ray, s) is occupied.
+ * rays: dev [n, ray_stride]; z: dev [n, S]. */
+int nerfhip_occ_mark(const float* rays, int ray_stride, int64_t n, const float* z, int S, const nerfhip_occ_grid* grid,
+                     uint8_t* flags_u8, nerfhip_stream_t stream);
+
+/* One probe per cell of [cell_first, cell_first + cell_count) (both multiples of 32; cells in bit-index order) through the plan's
+ * ordinary inference forward; bit b |= (raw[3] of cell b's probe > tau).  Bits are only ever set: the caller zeroes `grid->bits`
+ * before the first pass (grid->bits is written, its const notwithstanding; every word has a single writer).  A NaN raw[3] sets
+ * nothing.  pass 0 probes the cell centre lo + (i + 0.5) * cell, cell_a = (hi_a - lo_a) / res_a in fp32; pass k > 0 probes
+ * lo + (i + u) * cell, u_a = draw (3 * (k * ncells + b) + a) of the uniform generator (nerfhip_rng_fill, NERFHIP_RNG_UNIFORM) under
+ * `seed` with stream id NERFHIP_OCC_RNG_STREAM, ncells = res_x * res_y * res_z.
+ * tmp (dev, 256-byte aligned, nerfhip_occ_update_tmp_bytes(cell_count)) holds, and keeps after the call:
+ *   offset 0                              probe rows [cell_count, 11]: packed ray rows (probe point, direction 0 0 0, near 0, far 0,
+ *                                         viewdir 0 0 1) -- with the depths below, the fused-input forward encodes exactly the probe
+ *   offset r = align256(cell_count * 44)  depths [cell_count], all 0
+ *   offset r + align256(cell_count * 4)   raw [cell_count, 4]: the forward's output rows */
+#define NERFHIP_OCC_RNG_STREAM 16
+int64_t nerfhip_occ_update_tmp_bytes(int64_t cell_count);
+int nerfhip_occ_update(nerfhip_plan_t plan, const float* packed, const nerfhip_occ_grid* grid, float tau, int pass, uint64_t seed,
+                       int64_t cell_first, int64_t cell_count, void* tmp, int64_t tmp_bytes, nerfhip_stream_t stream);
+
+/* bits_out: a cell is set if it or one of its six face neighbours is set in bits_in; no wrap-around at the box faces.
+ * bits_in != bits_out, both dev [res_x * res_y * res_z / 32]; res: host int[3]. */
+int nerfhip_occ_dilate(const uint32_t* bits_in, uint32_t* bits_out, const int* res, nerfhip_stream_t stream);
+
+/* nerfhip_render_fwd_parts for inference with empty-space skipping.  Per pass that runs: the samples whose cell is occupied are
+ * listed (ascending; the two-launch count / scatter scheme of the compacted backward, no atomics) and every other sample's raw row
+ * is set to the empty row; the MLP runs over the list alone and writes each result at its sample's own row (bit for bit the dense
+ * kernel's row); the compositing is the unchanged nerfhip_volume_render_fwd.  grid_coarse / grid_fine: host structs (they may be the
+ * same one), read during the call.  tmp: dev, 256-byte aligned, nerfhip_render_occ_tmp_bytes; after the call its first four int32 are
+ * {kept_coarse, total_coarse, kept_fine, total_fine} (a pass that did not run leaves its pair untouched).  The sample list of the
+ * LAST pass that ran stays behind them, for inspection: with Mmax = n_rays * (num_coarse + num_fine) and
+ * C = 16 * ceil(ceil(Mmax / 2048) / 16), int32 words 16 .. 16 + C - 1 are per-block counts and the list -- `kept` sample indices,
+ * ascending, padded with sample 0 up to the next multiple of 128 -- starts at word 16 + C.
+ * Refused (NERFHIP_ERR_ARG, nothing launched): training != 0; a NULL grid of a pass that runs; res out of range or the cell count no
+ * multiple of 32; hi <= lo; tmp too small; n_rays * samples >= 2^31; a 512-wide plan or one on the extended encoding registers. */
+int64_t nerfhip_render_occ_tmp_bytes(const nerfhip_render_cfg* cfg, int64_t n_rays);
+int nerfhip_render_fwd_occ(nerfhip_plan_t plan_coarse, nerfhip_plan_t plan_fine, const nerfhip_render_cfg* cfg,
+                           const float* rays, int64_t n_rays, const float* packed_coarse, const float* packed_fine,
+                           const float* t_vals, const float* u_det, const nerfhip_render_rand* rnd, uint64_t seed,
+                           uint64_t ray_offset, const nerfhip_render_out* out, void* workspace, int64_t workspace_bytes,
+                           int training, int parts, const nerfhip_occ_grid* grid_coarse, const nerfhip_occ_grid* grid_fine,
+                           void* tmp, int64_t tmp_bytes, nerfhip_stream_t stream);
+
 /* ---- loss + optimiser (train_nerf.py:244-270) ------------------------------------------------------------------ */
 /* mse_loss(rgb_coarse, target) + mse_loss(rgb_fine, target) and its cotangents; loss_out: dev float[3] =
  * {coarse_mse, fine_mse, sum}.  target rows have target_stride floats (RGB or RGBA; only [:3] is used). */

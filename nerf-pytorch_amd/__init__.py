@@ -6,11 +6,12 @@ Next to the path: on-device training-ray selection (train_utils.se
 select_training_rays_views; their cameras as se(3) twists on base poses: cameras.CameraTable / se3_poses), the 8-bit output stage (eval_utils) and the reference's .ckpt / .data formats (io_utils).  Dataset loaders, the YAML config
 tree and the CLI scripts of the reference are out of scope.
 """
-from . import eval_utils, io_utils, models  # noqa: F401
+from . import eval_utils, io_utils, models, occupancy  # noqa: F401
 from .cameras import CameraTable, Distortion, Exposure, Intrinsics, se3_poses  # noqa: F401
 from .cfg import AttrDict, make_options  # noqa: F401
 from .engine import TrainEngine  # noqa: F401
 from .models import FlexibleNeRFModel  # noqa: F401
+from .occupancy import OccupancyGrid  # noqa: F401
 from .nerf_helpers import (cumprod_exclusive, get_embedding_function, get_minibatches, get_ray_bundle,  # noqa: F401
                            get_rays_at_pixels, img2mse, meshgrid_xy, mse2psnr, ndc_rays, positional_encoding,
                            sample_pdf, sample_pdf_2, sample_pdf_with_indices)

@@ -43,6 +43,14 @@ class RenderCotangents(C.Structure):
                                    "g_depth_fine")]
 
 
+class OccGrid(C.Structure):
+    """nerfhip_occ_grid: a host struct naming the device bits, passed by pointer and read during the call."""
+    _fields_ = [("bits", c_f), ("lo", C.c_float * 3), ("hi", C.c_float * 3), ("res", C.c_int * 3), ("outside", C.c_int)]
+
+
+OCC_EMPTY_RAW = -1e30  # NERFHIP_OCC_EMPTY_RAW (as fp32)
+OCC_RNG_STREAM = 16    # NERFHIP_OCC_RNG_STREAM
+
 PRECISION_FP32 = 0  # NERFHIP_PRECISION_* (1 .. 4: round 3's bf16-piece plans, removed)
 PRECISION_F16X3, PRECISION_F16X3_FWD, PRECISION_F16X3_FWD_DGRAD, PRECISION_F16X3_TRAIN = 5, 6, 7, 8
 PART_COARSE, PART_FINE, PART_SHARED_BWD = 1, 2, 4
@@ -133,6 +141,14 @@ _PROTOS = {
     "nerfhip_render_grad_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RenderCfg), c_f, c_i64, c_f, c_f,
                                             C.POINTER(RenderRand), c_u64, c_u64, C.POINTER(RenderCotangents), c_f, c_i64,
                                             C.c_int, c_f, c_f, c_f, c_i64, c_f, c_f]),
+    "nerfhip_occ_mark": (C.c_int, [c_f, C.c_int, c_i64, c_f, C.c_int, C.POINTER(OccGrid), c_f, c_f]),
+    "nerfhip_occ_update_tmp_bytes": (c_i64, [c_i64]),
+    "nerfhip_occ_update": (C.c_int, [C.c_void_p, c_f, C.POINTER(OccGrid), C.c_float, C.c_int, c_u64, c_i64, c_i64, c_f, c_i64, c_f]),
+    "nerfhip_occ_dilate": (C.c_int, [c_f, c_f, C.POINTER(C.c_int), c_f]),
+    "nerfhip_render_occ_tmp_bytes": (c_i64, [C.POINTER(RenderCfg), c_i64]),
+    "nerfhip_render_fwd_occ": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RenderCfg), c_f, c_i64, c_f, c_f, c_f, c_f,
+                                          C.POINTER(RenderRand), c_u64, c_u64, C.POINTER(RenderOut), c_f, c_i64, C.c_int, C.c_int,
+                                          C.POINTER(OccGrid), C.POINTER(OccGrid), c_f, c_i64, c_f]),
     "nerfhip_mse_loss_fwd_bwd": (C.c_int, [c_f, c_f, c_f, C.c_int, c_i64, C.c_float, c_f, c_f, c_f, c_f]),
     "nerfhip_adam_step": (C.c_int, [c_f, c_f, c_f, c_f, c_i64, C.c_float, C.c_float, C.c_float, C.c_float, c_i64,
                                      C.c_float, c_f]),

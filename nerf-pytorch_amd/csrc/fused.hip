@@ -116,13 +116,29 @@ Pass net_pass(const Call& c, bool fine, nerfhip_plan* plan, const float* packed,
     return p;
 }
 
+// the occupancy grid of one pass of nerfhip_render_fwd_occ and the sample list it is culled through
+struct OccPass {
+    const nerfhip_occ_grid* grid;
+    NhCompact list;
+};
+
 // MLP over the pass's depths -> compositing.  (a training forward leaves in the stash what the plan's backward will read there:
 // nh_mlp_forward_training)
-int forward_pass(const Call& c, const Pass& p, int training, float* rgb, float* disp, float* acc, float* weights, float* depth) {
+// occ (inference only): mark / list / empty rows (nh_occ_list) -> the MLP over the listed samples alone, each result at its sample's
+// own raw row -> the same compositing
+int forward_pass(const Call& c, const Pass& p, int training, float* rgb, float* disp, float* acc, float* weights, float* depth,
+                 const OccPass* occ = nullptr) {
     const int64_t M = c.n * p.in.S;
     float* raw = (float*)(c.ws + p.w.raw);
-    const int rc = training ? nh_mlp_forward_training(p.plan, p.packed, p.in, M, raw, (float*)(c.ws + p.w.stash), c.stream)
-                            : nh_mlp_forward(p.plan, p.packed, p.in, M, raw, nullptr, c.stream);
+    int rc;
+    if (occ) {
+        rc = nh_occ_list(occ->grid, c.rays, c.cfg->ray_stride, p.in.z, p.in.S, M, raw, occ->list, c.stream);
+        if (rc) return rc;
+        rc = nh_mlp_forward_listed(p.plan, p.packed, p.in, M, raw, occ->list, c.stream);
+    } else {
+        rc = training ? nh_mlp_forward_training(p.plan, p.packed, p.in, M, raw, (float*)(c.ws + p.w.stash), c.stream)
+                      : nh_mlp_forward(p.plan, p.packed, p.in, M, raw, nullptr, c.stream);
+    }
     if (rc) return rc;
     return nerfhip_volume_render_fwd(raw, p.in.z, c.rays + 3, c.cfg->ray_stride, c.n, p.in.S, c.cfg->noise_std, p.noise, c.seed,
                                      p.rng_stream, c.ray_offset, c.cfg->white_background, rgb, disp, acc, weights, depth, c.stream);
@@ -216,11 +232,12 @@ extern "C" int nerfhip_render_workspace_region(nerfhip_plan_t plan_coarse, nerfh
     NH_REQUIRE(false, "render_workspace_region: unknown region '%s'", name);
 }
 
-extern "C" int nerfhip_render_fwd_parts(nerfhip_plan_t pc, nerfhip_plan_t pf, const nerfhip_render_cfg* cfg,
-                                        const float* rays, int64_t n, const float* packed_c, const float* packed_f,
-                                        const float* t_vals, const float* u_det, const nerfhip_render_rand* rnd,
-                                        uint64_t seed, uint64_t ray_offset, const nerfhip_render_out* out, void* workspace,
-                                        int64_t workspace_bytes, int training, int parts, nerfhip_stream_t stream) {
+// nerfhip_render_fwd_parts, and -- occ_c / occ_f: the passes' grids and lists, checked by the caller -- nerfhip_render_fwd_occ
+static int render_fwd(nerfhip_plan_t pc, nerfhip_plan_t pf, const nerfhip_render_cfg* cfg, const float* rays, int64_t n,
+                      const float* packed_c, const float* packed_f, const float* t_vals, const float* u_det,
+                      const nerfhip_render_rand* rnd, uint64_t seed, uint64_t ray_offset, const nerfhip_render_out* out, void* workspace,
+                      int64_t workspace_bytes, int training, int parts, nerfhip_stream_t stream, const OccPass* occ_c,
+                      const OccPass* occ_f) {
     int rc = check_cfg(pc, pf, cfg);
     if (rc) return rc;
     NH_REQUIRE(rays && packed_c && t_vals && out && workspace && n >= 0, "render_fwd: bad arguments");
@@ -242,7 +259,7 @@ extern "C" int nerfhip_render_fwd_parts(nerfhip_plan_t pc, nerfhip_plan_t pf, co
                                   seed, ray_offset, z_c, stream);
         if (rc) return rc;
         rc = forward_pass(c, net_pass(c, false, pc, packed_c, rnd, w), training, out->rgb_coarse, out->disp_coarse, out->acc_coarse, w_c,
-                          out->depth_coarse);
+                          out->depth_coarse, occ_c);
         if (rc) return rc;
     }
     if (cfg->num_fine > 0 && (parts & NERFHIP_PART_FINE)) {
@@ -254,10 +271,65 @@ extern "C" int nerfhip_render_fwd_parts(nerfhip_plan_t pc, nerfhip_plan_t pf, co
         if (rc) return rc;
         // (only the coarse compositing writes its weights: the fine depths were drawn from them)
         rc = forward_pass(c, net_pass(c, true, pf, packed_f, rnd, w), training, out->rgb_fine, out->disp_fine, out->acc_fine, nullptr,
-                          out->depth_fine);
+                          out->depth_fine, occ_f);
         if (rc) return rc;
     }
     return NERFHIP_OK;
+}
+
+extern "C" int nerfhip_render_fwd_parts(nerfhip_plan_t pc, nerfhip_plan_t pf, const nerfhip_render_cfg* cfg,
+                                        const float* rays, int64_t n, const float* packed_c, const float* packed_f,
+                                        const float* t_vals, const float* u_det, const nerfhip_render_rand* rnd,
+                                        uint64_t seed, uint64_t ray_offset, const nerfhip_render_out* out, void* workspace,
+                                        int64_t workspace_bytes, int training, int parts, nerfhip_stream_t stream) {
+    return render_fwd(pc, pf, cfg, rays, n, packed_c, packed_f, t_vals, u_det, rnd, seed, ray_offset, out, workspace, workspace_bytes,
+                      training, parts, stream, nullptr, nullptr);
+}
+
+// tmp of nerfhip_render_fwd_occ: one list area (nh_compact_view) for the larger pass -- the two passes run one after the other and
+// share its counts and list; the area's first 16 words are the statistics: words 0, 1 the coarse pass's {kept, total}, words 2, 3 the
+// fine pass's (each pass's NhCompact::stats points at its own pair)
+extern "C" int64_t nerfhip_render_occ_tmp_bytes(const nerfhip_render_cfg* cfg, int64_t n) {
+    if (!cfg || n < 0 || cfg->num_coarse < 1 || cfg->num_fine < 0) return -1;
+    const int64_t m = n * ((int64_t)cfg->num_coarse + cfg->num_fine);
+    return nh_compact_ints(m > 0 ? m : 1) * 4;
+}
+
+extern "C" int nerfhip_render_fwd_occ(nerfhip_plan_t pc, nerfhip_plan_t pf, const nerfhip_render_cfg* cfg, const float* rays,
+                                      int64_t n, const float* packed_c, const float* packed_f, const float* t_vals,
+                                      const float* u_det, const nerfhip_render_rand* rnd, uint64_t seed, uint64_t ray_offset,
+                                      const nerfhip_render_out* out, void* workspace, int64_t workspace_bytes, int training,
+                                      int parts, const nerfhip_occ_grid* grid_c, const nerfhip_occ_grid* grid_f, void* tmp,
+                                      int64_t tmp_bytes, nerfhip_stream_t stream) {
+    int rc = check_cfg(pc, pf, cfg);
+    if (rc) return rc;
+    NH_REQUIRE(training == 0,
+               "render_fwd_occ: an occupancy grid culls the inference render only (training = %d): the training forward and its backward "
+               "run dense",
+               training);
+    NH_REQUIRE(parts >= 1 && parts <= 3, "render_fwd_occ: parts must be a combination of NERFHIP_PART_COARSE | NERFHIP_PART_FINE");
+    NH_REQUIRE(n >= 0, "render_fwd_occ: bad arguments");
+    const bool coarse_runs = (parts & NERFHIP_PART_COARSE) != 0, fine_runs = cfg->num_fine > 0 && (parts & NERFHIP_PART_FINE);
+    if (coarse_runs) {
+        NH_REQUIRE(grid_c, "render_fwd_occ: grid_coarse is NULL");
+        if ((rc = nh_occ_check(grid_c, "render_fwd_occ")) != 0 || (rc = nh_mlp_listed_check(pc, "render_fwd_occ")) != 0) return rc;
+    }
+    if (fine_runs) {
+        NH_REQUIRE(grid_f, "render_fwd_occ: grid_fine is NULL");
+        if ((rc = nh_occ_check(grid_f, "render_fwd_occ")) != 0 || (rc = nh_mlp_listed_check(pf, "render_fwd_occ")) != 0) return rc;
+    }
+    const int64_t m_max = n * ((int64_t)cfg->num_coarse + cfg->num_fine);
+    NH_REQUIRE(m_max < ((int64_t)1 << 31), "render_fwd_occ: at most 2^31 - 1 sample points per pass (got %lld)", (long long)m_max);
+    const int64_t need = nerfhip_render_occ_tmp_bytes(cfg, n);
+    NH_REQUIRE(tmp && tmp_bytes >= need, "render_fwd_occ: tmp too small (%lld < %lld)", (long long)tmp_bytes, (long long)need);
+    OccPass oc, of;
+    oc.grid = grid_c;
+    oc.list = nh_compact_view((int*)tmp, m_max > 0 ? m_max : 1);
+    of.grid = grid_f;
+    of.list = oc.list;
+    of.list.stats = oc.list.stats + 2;
+    return render_fwd(pc, pf, cfg, rays, n, packed_c, packed_f, t_vals, u_det, rnd, seed, ray_offset, out, workspace, workspace_bytes, 0,
+                      parts, stream, &oc, &of);
 }
 
 extern "C" int nerfhip_render_fwd(nerfhip_plan_t pc, nerfhip_plan_t pf, const nerfhip_render_cfg* cfg, const float* rays,

@@ -146,6 +146,28 @@ static int mlp_forward_any(nerfhip_plan* p, const float* packed, const NhMlpInpu
     return nh_mlp16_forward(p, packed, in, M, out, stash, stream, list);
 }
 
+int nh_mlp_listed_check(const nerfhip_plan* p, const char* what) {
+    NH_REQUIRE(p, "%s: plan is NULL", what);
+    NH_REQUIRE(p->W <= 256, "%s: no listed forward for 512-wide plans: they render without an occupancy grid", what);
+    NH_REQUIRE(nh_prec_f16(p->precision) || p->krx == NH16_KRX,
+               "%s: no listed forward for plans on the extended encoding registers (num_encoding_fn_xyz > 10 or num_encoding_fn_dir > 4): "
+               "they render without an occupancy grid",
+               what);
+    return NERFHIP_OK;
+}
+
+int nh_mlp_forward_listed(nerfhip_plan* p, const float* packed, const NhMlpInput& in, int64_t M, float* out, const NhCompact& list,
+                          nerfhip_stream_t stream) {
+    const int rc = nh_mlp_listed_check(p, "mlp_fwd_listed");
+    if (rc) return rc;
+    NH_REQUIRE(packed && out && M > 0, "mlp_fwd_listed: bad arguments");
+    NH_REQUIRE(in.mode == 1 && p->freqs_set && in.rays && in.z && in.S > 0 && in.ray_stride >= (p->view ? 11 : 8),
+               "mlp_fwd_listed: bad fused input (rays + depths, after nerfhip_plan_set_freqs)");
+    if (p->precision != NERFHIP_PRECISION_FP32) return nh_mlp_forward_f16w_listed(p, packed, in, M, out, list, stream);
+    // (plans with a resident image, nh_r64.h, take the general kernel too: k_fwd64r walks no list)
+    return nh_mlp16_forward_listed(p, packed, in, M, out, list, stream);
+}
+
 int nh_mlp_forward_training(nerfhip_plan* p, const float* packed, const NhMlpInput& in, int64_t M, float* out, float* stash,
                             nerfhip_stream_t stream) {
     NH_REQUIRE(p && out && stash, "mlp_fwd: bad arguments");

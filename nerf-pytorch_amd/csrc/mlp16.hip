@@ -424,13 +424,17 @@ struct Fwd16Args {
 
 // TRAIN: the launch writes the activation stash (rows, encoding slots, ReLU masks) for the backward kernels
 // EXT: the extended encoding registers (num_encoding_fn_xyz > 10 or num_encoding_fn_dir > 4: nh_plan.h)
-template <int W, bool VIEW, bool TRAIN, bool EXT = false>
+// LIST: an INFERENCE forward over a sample list (the occupancy-culled render, occ/mlp16_occ.hip): slot c computes sample cidx[c] and writes
+// its raw row at THAT SAMPLE'S row of `out`; padding slots write nothing.  The default reproduces the kernels without it.
+template <int W, bool VIEW, bool TRAIN, bool EXT = false, bool LIST = false>
 NH_KERNEL void NH_LB(64 * Shape<W>::NW, Shape<W>::WAVES_PER_SIMD) k_mlp_fwd16(Fwd16Args a) {
+    static_assert(!(TRAIN && LIST), "a listed inference forward writes no stash");
+    constexpr bool WALK = TRAIN || LIST;  // the launch may walk a list
     constexpr int KH = W / 4, TW = W / 16, KX = EXT ? NH16_KRX_EXT : NH16_KRX, KD = EXT ? NH16_KRD_EXT : NH16_KRD;
     constexpr int NW = Shape<W>::NW, MW = Shape<W>::MW;
     // (a launch over a list: a workgroup whose slots are all behind it has nothing to do)
-    const int n_slots = (TRAIN && a.cidx) ? nh_uload_i32(a.cstats, NH_CSTAT_ACTIVE) : 0;
-    if (TRAIN && a.cidx && (int64_t)blockIdx.x * (NW * 16) >= (int64_t)n_slots) return;
+    const int n_slots = (WALK && a.cidx) ? nh_uload_i32(a.cstats, NH_CSTAT_ACTIVE) : 0;
+    if (WALK && a.cidx && (int64_t)blockIdx.x * (NW * 16) >= (int64_t)n_slots) return;
     NH_DYN_LDS(lds_raw);
     nh_clk_begin(a.clk, (unsigned long long*)(lds_raw + Lds<W>::BYTES));
     Ctx cx;
@@ -454,11 +458,11 @@ NH_KERNEL void NH_LB(64 * Shape<W>::NW, Shape<W>::WAVES_PER_SIMD) k_mlp_fwd16(Fw
     const int64_t m = tile * 32 + js;
     bool valid = m < a.M;
     int64_t mc = valid ? m : a.M - 1;  // the sample this lane computes
-    if (TRAIN && a.cidx) {              // (slot m of a list: its sample; padding slots compute sample cidx[m] = 0 and are never read)
+    if (WALK && a.cidx) {               // (slot m of a list: its sample; padding slots compute sample cidx[m] = 0 and are never read)
         valid = m < (int64_t)n_slots;
         mc = (int64_t)a.cidx[m];
     }
-    const int m_i = (int)m;  // (the host checks M < 2^31)
+    const int m_i = LIST ? (int)mc : (int)m;  // the row of `out` this lane writes (the host checks M < 2^31)
     const NhPackedOffsets& po = a.off;
 
     // the first weights travel to LDS while the encodings are computed
@@ -756,7 +760,7 @@ NH_KERNEL void NH_LB(64 * Shape<W>::NW, Shape<W>::WAVES_PER_SIMD) k_mlp_dgrad16(
 
 }  // namespace
 
-#if defined(NH_PHASE_TIMING) && !defined(NH16_W512_TU) && !defined(NH16_EXT_TU)
+#if defined(NH_PHASE_TIMING) && !defined(NH16_W512_TU) && !defined(NH16_EXT_TU) && !defined(NH16_OCC_TU)
 extern "C" int nerfhip_debug_phases16(unsigned long long* host16, int reset) {
     (void)hipMemcpyFromSymbol(host16, HIP_SYMBOL(g_phase16), sizeof(unsigned long long) * 16);
     if (reset) {
@@ -771,7 +775,8 @@ extern "C" int nerfhip_debug_phases16(unsigned long long* host16, int reset) {
 // The 512-wide instantiations (three kernels, ~2.5 minutes of compile time) live in their own translation unit,
 // mlp16_w512.hip, which includes this file with NH16_W512_TU defined: it compiles the same templates for W = 512 only and
 // exports nh_mlp16_forward_w512 / nh_mlp16_dgrad_w512; this unit holds the widths 64 / 128 / 256 and the dispatch.
-// mlp16_ext.hip (NH16_EXT_TU) likewise holds the forward kernels with the extended encoding registers, every width.
+// mlp16_ext.hip (NH16_EXT_TU) likewise holds the forward kernels with the extended encoding registers, every width, and
+// occ/mlp16_occ.hip (NH16_OCC_TU) the LIST instantiations of the forward kernel (widths 64 / 128 / 256).
 namespace {
 
 void fill_fwd_args(nerfhip_plan* p, const float* packed, const NhMlpInput& in, int64_t M, float* out, float* stash, Fwd16Args& a,
@@ -861,7 +866,36 @@ int nh_mlp16_dgrad_w512(nerfhip_plan* p, const float* packed, const float* g_out
 int nh_mlp16_forward_ext(nerfhip_plan* p, const float* packed, const NhMlpInput& in, int64_t M, float* out, float* stash,
                          nerfhip_stream_t stream, const NhCompact* list);
 
-#if defined(NH16_EXT_TU)
+#if defined(NH16_OCC_TU)
+// the listed inference forward, widths 64 / 128 / 256 (occ/mlp16_occ.hip)
+int nh_mlp16_forward_listed(nerfhip_plan* p, const float* packed, const NhMlpInput& in, int64_t M, float* out, const NhCompact& list,
+                            nerfhip_stream_t stream) {
+    NH_REQUIRE(M > 0 && M < ((int64_t)1 << 31), "mlp_fwd_listed: 1 .. 2^31 - 1 sample points per call (got %lld)", (long long)M);
+    NH_REQUIRE(out && list.idx && list.stats, "mlp_fwd_listed: bad arguments");
+    NH_REQUIRE(p->krx == NH16_KRX && p->W <= 256, "mlp_fwd_listed: no listed kernel for this plan");
+    Fwd16Args a;
+    fill_fwd_args(p, packed, in, M, out, nullptr, a);
+    a.cidx = list.idx;
+    a.cstats = list.stats;
+    const int64_t groups = nh_ceil_div(M, 128);
+    int rc = NERFHIP_OK;
+#define NH_FWD16_L(WW, VV)                                                                                                       \
+    {                                                                                                                            \
+        rc = nh_lds_limit(k_mlp_fwd16<WW, VV, false, false, true>, Lds<WW>::BYTES_ALL);                                          \
+        if (rc) return rc;                                                                                                       \
+        NH_LAUNCH((k_mlp_fwd16<WW, VV, false, false, true>), groups * (8 / Shape<WW>::NW), 64 * Shape<WW>::NW, Lds<WW>::BYTES_ALL, \
+                  stream, a);                                                                                                    \
+    }
+    if (p->W == 256 && p->view) NH_FWD16_L(256, true)
+    else if (p->W == 256) NH_FWD16_L(256, false)
+    else if (p->W == 128 && p->view) NH_FWD16_L(128, true)
+    else if (p->W == 128) NH_FWD16_L(128, false)
+    else if (p->view) NH_FWD16_L(64, true)
+    else NH_FWD16_L(64, false)
+#undef NH_FWD16_L
+    return nh_launch_status("mlp_fwd16_listed");
+}
+#elif defined(NH16_EXT_TU)
 // every width with the extended encoding registers (mlp16_ext.hip)
 int nh_mlp16_forward_ext(nerfhip_plan* p, const float* packed, const NhMlpInput& in, int64_t M, float* out, float* stash,
                          nerfhip_stream_t stream, const NhCompact* list) {

@@ -507,11 +507,14 @@ struct FwdWArgs {
 
 // TRAIN: the launch also writes the activation stash -- encoding slots, every layer's fp32 output rows (plain values), ReLU masks -- in
 // the format k_mlp_dgrad16 / k_mlp_dgrad_f16x3w / k_wgrad / k_wgrad_f16x3 read
-template <int W, bool VIEW, bool TRAIN>
+// LIST: an INFERENCE forward over a sample list (the occupancy-culled render, occ/mlp_f16w_occ.hip): slot c computes sample cidx[c] and
+// writes its raw row at THAT SAMPLE'S row of `out`; padding slots write nothing.  The default reproduces the kernels without it.
+template <int W, bool VIEW, bool TRAIN, bool LIST = false>
 NH_KERNEL void NH_LB(512, 2) k_mlp_fwd_f16x3w(FwdWArgs a) {
+    static_assert(!(TRAIN && LIST), "a listed inference forward writes no stash");
     constexpr int TW = WShape<W>::TW, KB = WShape<W>::KB, BUF = WShape<W>::BUF, CB = WShape<W>::CB;
     // (a launch over a list: its groups are the list's; a workgroup without one has nothing to stream)
-    const bool listed = TRAIN && a.cidx;
+    const bool listed = (TRAIN || LIST) && a.cidx;
     const int n_slots = listed ? nh_uload_i32(a.cstats, NH_CSTAT_ACTIVE) : 0;
     const int64_t groups = listed ? (int64_t)((n_slots + 127) >> 7) : a.groups;
     if ((int64_t)blockIdx.x >= groups) return;
@@ -545,6 +548,7 @@ NH_KERNEL void NH_LB(512, 2) k_mlp_fwd_f16x3w(FwdWArgs a) {
             valid = m < (int64_t)n_slots;
             mc = (int64_t)a.cidx[m];
         }
+        const int64_t mo = LIST ? mc : m;  // the row of `out` this lane writes
         // training: this sample's row of a stash region ([32-sample tile][sample][rows]; whole groups are written, clamped samples
         // included), and this lane's mask words ([16-sample wave tile][mask][64 lanes][2 words])
         const int64_t tile32 = grp * 4 + (cx.wave >> 1);
@@ -639,7 +643,7 @@ NH_KERNEL void NH_LB(512, 2) k_mlp_fwd_f16x3w(FwdWArgs a) {
                 r4.y = raw_of(acc[0][1], s);
                 r4.z = raw_of(acc[0][2], s);
                 r4.w = alpha;
-                *(float4*)(a.out + (size_t)m * 4) = r4;
+                *(float4*)(a.out + (size_t)mo * 4) = r4;
             }
         } else {
             const MaskW in_bits = bits;
@@ -653,7 +657,7 @@ NH_KERNEL void NH_LB(512, 2) k_mlp_fwd_f16x3w(FwdWArgs a) {
                 r4.y = raw_of(acc[0][1], s);
                 r4.z = raw_of(acc[0][2], s);
                 r4.w = raw_of(acc[0][3], s);
-                *(float4*)(a.out + (size_t)m * 4) = r4;
+                *(float4*)(a.out + (size_t)mo * 4) = r4;
             }
         }
     }  // (groups of this workgroup)
@@ -822,14 +826,8 @@ NH_KERNEL void NH_LB(512, 2) k_mlp_dgrad_f16x3w(DgradWArgs a) {
     regions_end(cx, a.rmax);
 }
 
-}  // namespace
-
-int nh_mlp_forward_f16w(nerfhip_plan* p, const float* packed, const NhMlpInput& in, int64_t M, float* out, float* stash,
-                        nerfhip_stream_t stream, const NhCompact* list) {
-    NH_REQUIRE(M < ((int64_t)1 << 31), "mlp_fwd: at most 2^31 - 1 sample points per call (got %lld)", (long long)M);
-    NH_REQUIRE(out || (list && stash), "mlp_fwd: out is NULL");
-    NH_REQUIRE(nh_prec_f16(p->precision), "mlp_fwd_f16w: not an fp16-piece plan");
-    FwdWArgs a;
+// what every forward launch's arguments share (the stash, its region maxima and the list are the caller's)
+void fill_fwdw_args(nerfhip_plan* p, const float* packed, const NhMlpInput& in, int64_t M, float* out, FwdWArgs& a) {
     memset(&a, 0, sizeof(a));
     a.packed = packed;
     a.packed_bytes = (unsigned)(p->packed_floats * 4);
@@ -837,13 +835,6 @@ int nh_mlp_forward_f16w(nerfhip_plan* p, const float* packed, const NhMlpInput& 
     a.L = p->L;
     a.skip = p->skip;
     a.M = M;
-    a.stash = stash;
-    // (plans whose large weight-gradient blocks run on the fp16 MFMAs: the stash's region maxima, zeroed here)
-    a.rmax = (stash && !p->bjobs.empty()) ? (unsigned*)(stash + nh_stash_floats(p, nh_ceil_div(M, 128) * 4)) : nullptr;
-    if (a.rmax) {
-        const int rc0 = nh_zero_words(a.rmax, NH_RMAX_WORDS, stream);
-        if (rc0) return rc0;
-    }
     a.sl = p->stash;
     a.nt = nh_ceil_div(M, 128) * 4;
     a.mode = in.mode;
@@ -863,10 +854,66 @@ int nh_mlp_forward_f16w(nerfhip_plan* p, const float* packed, const NhMlpInput& 
     a.Lx = p->cfg.num_encoding_fn_xyz;
     a.Ld = p->view ? p->cfg.num_encoding_fn_dir : 0;
     a.out = out;
+    a.groups = nh_ceil_div(M, 128);
+}
+
+}  // namespace
+
+// The LIST instantiations of the forward kernel live in a translation unit of their own, occ/mlp_f16w_occ.hip, which includes this file
+// with NHW_OCC_TU defined: it compiles the same templates for the listed inference forward only and exports
+// nh_mlp_forward_f16w_listed; this unit holds every other kernel.
+#if defined(NHW_OCC_TU)
+int nh_mlp_forward_f16w_listed(nerfhip_plan* p, const float* packed, const NhMlpInput& in, int64_t M, float* out, const NhCompact& list,
+                               nerfhip_stream_t stream) {
+    NH_REQUIRE(M > 0 && M < ((int64_t)1 << 31), "mlp_fwd_listed: 1 .. 2^31 - 1 sample points per call (got %lld)", (long long)M);
+    NH_REQUIRE(out && list.idx && list.stats, "mlp_fwd_listed: bad arguments");
+    NH_REQUIRE(nh_prec_f16(p->precision), "mlp_fwd_f16w: not an fp16-piece plan");
+    FwdWArgs a;
+    fill_fwdw_args(p, packed, in, M, out, a);
+    a.cidx = list.idx;
+    a.cstats = list.stats;
+    // as many workgroups as are resident at once (the dense launch's grid: the list's length is known on the device alone)
+    const int64_t resident = (int64_t)nh_compute_units();
+    const int64_t grid = a.groups < resident ? a.groups : resident;
+    int rc = NERFHIP_OK;
+#define NH_FWDW_L(WW, VV)                                                                                                          \
+    {                                                                                                                              \
+        rc = nh_lds_limit(k_mlp_fwd_f16x3w<WW, VV, false, true>, WShape<WW>::LDS_BYTES + RM_LDS);                                  \
+        if (rc) return rc;                                                                                                         \
+        NH_LAUNCH_NAMED("k_mlp_fwd_f16x3w<" #WW ", " #VV ", false, true>", (k_mlp_fwd_f16x3w<WW, VV, false, true>), grid, 512,     \
+                        WShape<WW>::LDS_BYTES + RM_LDS, stream, a);                                                                \
+    }
+    if (p->W == 256 && p->view) NH_FWDW_L(256, true)
+    else if (p->W == 256) NH_FWDW_L(256, false)
+    else if (p->W == 128 && p->view) NH_FWDW_L(128, true)
+    else if (p->W == 128) NH_FWDW_L(128, false)
+    else if (p->W == 64 && p->view) NH_FWDW_L(64, true)
+    else if (p->W == 64) NH_FWDW_L(64, false)
+    else {
+        nh_set_error("mlp_fwd_listed: no f16x3 kernel for kernel width %d", p->W);
+        return NERFHIP_ERR_UNSUPPORTED;
+    }
+#undef NH_FWDW_L
+    return nh_launch_status("mlp_fwd_f16w_listed");
+}
+#else
+int nh_mlp_forward_f16w(nerfhip_plan* p, const float* packed, const NhMlpInput& in, int64_t M, float* out, float* stash,
+                        nerfhip_stream_t stream, const NhCompact* list) {
+    NH_REQUIRE(M < ((int64_t)1 << 31), "mlp_fwd: at most 2^31 - 1 sample points per call (got %lld)", (long long)M);
+    NH_REQUIRE(out || (list && stash), "mlp_fwd: out is NULL");
+    NH_REQUIRE(nh_prec_f16(p->precision), "mlp_fwd_f16w: not an fp16-piece plan");
+    FwdWArgs a;
+    fill_fwdw_args(p, packed, in, M, out, a);
+    a.stash = stash;
+    // (plans whose large weight-gradient blocks run on the fp16 MFMAs: the stash's region maxima, zeroed here)
+    a.rmax = (stash && !p->bjobs.empty()) ? (unsigned*)(stash + nh_stash_floats(p, nh_ceil_div(M, 128) * 4)) : nullptr;
+    if (a.rmax) {
+        const int rc0 = nh_zero_words(a.rmax, NH_RMAX_WORDS, stream);
+        if (rc0) return rc0;
+    }
     a.cidx = (list && stash) ? list->idx : nullptr;
     a.cstats = (list && stash) ? list->stats : nullptr;
-    const int64_t groups = nh_ceil_div(M, 128);
-    a.groups = groups;
+    const int64_t groups = a.groups;
     // as many workgroups as are resident at once: one 8-wave workgroup per CU (256-wide nets: its LDS; 128-wide: its 173-202 VGPRs)
     const int64_t resident = (int64_t)nh_compute_units();
     const int64_t grid = groups < resident ? groups : resident;
@@ -944,3 +991,4 @@ int nh_mlp_dgrad_f16w(nerfhip_plan* p, const float* packed, const float* g_out, 
 #undef NH_BWDW
     return nh_launch_status("mlp_dgrad_f16w");
 }
+#endif  // NHW_OCC_TU

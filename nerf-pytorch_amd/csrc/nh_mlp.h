@@ -31,6 +31,25 @@ int nh_compact_build(const float* g_out, int64_t M, const NhCompact& c, nerfhip_
 
 int nh_mlp_forward(nerfhip_plan* p, const float* packed, const NhMlpInput& in, int64_t M, float* out, float* stash,
                    nerfhip_stream_t stream);
+// The inference forward over a sample list (the occupancy-culled render, fused.hip): slot c computes sample list.idx[c] and writes its
+// raw row AT THAT SAMPLE'S OWN ROW of `out` -- bit for bit the dense inference forward's row; rows of samples not listed are not
+// touched.  fp32 plans of kernel width 64 / 128 / 256 (those with a resident image, nh_r64.h, included: the general kernel runs) and
+// fp16-piece plans; 512-wide plans and the extended encoding registers are refused.  (occ/mlp16_occ.hip / occ/mlp_f16w_occ.hip: the LIST
+// instantiations of the two forward kernels, in translation units of their own.)
+int nh_mlp_forward_listed(nerfhip_plan* p, const float* packed, const NhMlpInput& in, int64_t M, float* out, const NhCompact& list,
+                          nerfhip_stream_t stream);
+int nh_mlp_listed_check(const nerfhip_plan* p, const char* what);  // the refusals above, before anything is launched
+int nh_mlp16_forward_listed(nerfhip_plan* p, const float* packed, const NhMlpInput& in, int64_t M, float* out, const NhCompact& list,
+                            nerfhip_stream_t stream);
+int nh_mlp_forward_f16w_listed(nerfhip_plan* p, const float* packed, const NhMlpInput& in, int64_t M, float* out, const NhCompact& list,
+                               nerfhip_stream_t stream);
+
+// occ/occupancy.hip: checks a caller's grid (`what` names the entry point in the message); lists the occupied samples of a pass into
+// `list` (ascending, padded, stats = {kept, total}) and writes the empty row into `raw` for every other sample
+int nh_occ_check(const nerfhip_occ_grid* g, const char* what);
+int nh_occ_list(const nerfhip_occ_grid* g, const float* rays, int ray_stride, const float* z, int S, int64_t M, float* raw,
+                const NhCompact& list, nerfhip_stream_t stream);
+
 // What a backward over M sample points of a plan does, and so what its training forward leaves in the stash: resolved in ONE place,
 // nh_bwd_flow (mlp.hip; the table of the six modes of nerfhip_plan_set_bwd_compaction is its comment).
 struct NhBwdFlow {

@@ -73,7 +73,8 @@ def png_bytes(img):
 
 
 def render_pose_rows(height, width, focal_length, pose, model_coarse, model_fine, options, encode_position_fn=None,
-                     encode_direction_fn=None, rank=0, world_size=1, mode="validation", intrinsics=None, distortion=None):
+                     encode_direction_fn=None, rank=0, world_size=1, mode="validation", intrinsics=None, distortion=None,
+                     occupancy=None):
     """One pose of the render loop of eval_nerf.py (:158-176), ray-sharded (BASELINE config 5): rank `rank` of
     `world_size` generates and renders only ITS contiguous block of image rows (parallel.shard_bounds) -- rays are
     independent, so no rank ever needs another rank's data and there is no collective; the concatenation of the ranks'
@@ -82,7 +83,9 @@ def render_pose_rows(height, width, focal_length, pose, model_coarse, model_fine
     (rows, width, .).  The nets render under their current encoding window (FlexibleNeRFModel.set_encoding_window), if one is set.
     intrinsics: None, or a float32 device tensor (fx, fy, cx, cy), e.g. Intrinsics.values(): the rays are generated from it in
     place of `focal_length` and the image centre (`focal_length` still fixes the NDC constants).
-    distortion: None, or a float32 device tensor (k1, k2, p1, p2), e.g. Distortion.values(): the rays are undistorted under it."""
+    distortion: None, or a float32 device tensor (k1, k2, p1, p2), e.g. Distortion.values(): the rays are undistorted under it.
+    occupancy: None, or an occupancy.OccupancyGrid: samples in its empty cells skip the MLPs (inference only: call under
+    torch.no_grad() with mode="validation")."""
     from .nerf_helpers import get_rays_at_pixels
     from .parallel import shard_bounds
     from .train_utils import run_one_iter_of_nerf
@@ -92,7 +95,8 @@ def render_pose_rows(height, width, focal_length, pose, model_coarse, model_fine
                                 distortion=distortion)
     shape = (hi - lo, int(width), 3)
     out = run_one_iter_of_nerf(height, width, focal_length, model_coarse, model_fine, ro.view(shape), rd.view(shape), options,
-                               mode=mode, encode_position_fn=encode_position_fn, encode_direction_fn=encode_direction_fn)
+                               mode=mode, encode_position_fn=encode_position_fn, encode_direction_fn=encode_direction_fn,
+                               **({} if occupancy is None else {"occupancy": occupancy}))
     return out, (lo, hi)
 
 

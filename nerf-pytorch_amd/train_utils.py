@@ -232,7 +232,7 @@ class _FusedRender(torch.autograd.Function):
         return g_rays
 
 
-def _predict_fused(ray_batch, model_coarse, model_fine, opts):
+def _predict_fused(ray_batch, model_coarse, model_fine, opts, occupancy=None):
     rays_grad = bool(ray_batch.requires_grad and torch.is_grad_enabled())
     rays = ray_batch.contiguous().float() if rays_grad else ray_batch.detach().contiguous().float()
     n = rays.shape[0]
@@ -253,6 +253,13 @@ def _predict_fused(ray_batch, model_coarse, model_fine, opts):
             raise RuntimeError("a frozen model (set_frozen) has a parameter that requires grad: freeze the parameters "
                                "(p.requires_grad_(False)) or call set_frozen(False)")
     training = torch.is_grad_enabled() and (rays_grad or any(p.requires_grad for p in pc + pf))
+    if occupancy is not None:
+        if training:
+            raise NotImplementedError(_OCC_TRAIN_MSG)
+        from .occupancy import render_fwd_occ
+        outs = render_fwd_occ(rays, model_coarse, model_fine if nf > 0 else None, cfg_tuple, (t_rand, noise_c, u, noise_f), occupancy)
+        rgb_c, disp_c, acc_c, _, rgb_f, disp_f, acc_f, _ = outs
+        return (rgb_c, disp_c, acc_c, rgb_f, disp_f, acc_f) if nf > 0 else (rgb_c, disp_c, acc_c, None, None, None)
     outs = _FusedRender.apply(rays, model_coarse, model_fine if nf > 0 else None, cfg_tuple,
                               (t_rand, noise_c, u, noise_f), training, rays_grad, *pc, *pf)
     rgb_c, disp_c, acc_c, depth_c, rgb_f, disp_f, acc_f, depth_f = outs
@@ -267,12 +274,30 @@ def _predict_fused(ray_batch, model_coarse, model_fine, opts):
     return rgb_c, disp_c, acc_c, None, None, None
 
 
+_OCC_TRAIN_MSG = ("an occupancy grid culls the inference render only: pass occupancy= with mode=\"validation\" under torch.no_grad() "
+                  "(the training forward and its backward run dense)")
+
+
+def _predict_culled(ray_batch, model_coarse, model_fine, opts, encode_position_fn, encode_direction_fn, occupancy):
+    """A ray chunk through the fused render with an occupancy grid (the caller has checked the mode)."""
+    if not _fusable(model_coarse, model_fine, encode_position_fn, encode_direction_fn, opts.num_fine):
+        raise NotImplementedError("an occupancy grid needs the fused render (FlexibleNeRFModel nets and their own embedding functions)")
+    return _predict_fused(ray_batch, model_coarse, model_fine, opts, occupancy)
+
+
 def predict_and_render_radiance(ray_batch, model_coarse, model_fine, options, mode="train", encode_position_fn=None,
-                                encode_direction_fn=None):
-    """nerf/train_utils.py:28-127.  Returns (rgb_coarse, disp_coarse, acc_coarse, rgb_fine, disp_fine, acc_fine)."""
+                                encode_direction_fn=None, occupancy=None):
+    """nerf/train_utils.py:28-127.  Returns (rgb_coarse, disp_coarse, acc_coarse, rgb_fine, disp_fine, acc_fine).
+    occupancy: None, or an occupancy.OccupancyGrid -- with mode="validation" and no gradient wanted, the samples in its empty cells
+    skip the MLPs (nerfhip_render_fwd_occ) and the chunk's counts are added to the grid's view_counts; in train mode it raises
+    NotImplementedError."""
     if not ray_batch.is_cuda:
         raise RuntimeError("predict_and_render_radiance needs CUDA (HIP) tensors: nerf_pytorch_amd has no CPU path")
     opts = getattr(options.nerf, mode)
+    if occupancy is not None:
+        if mode != "validation":
+            raise NotImplementedError(_OCC_TRAIN_MSG)
+        return _predict_culled(ray_batch, model_coarse, model_fine, opts, encode_position_fn, encode_direction_fn, occupancy)
     if _fusable(model_coarse, model_fine, encode_position_fn, encode_direction_fn, opts.num_fine):
         return _predict_fused(ray_batch, model_coarse, model_fine, opts)
 
@@ -717,8 +742,9 @@ def select_cached_training_rays(cache_dict, num_random_rays, options, select_ind
 
 
 def run_one_iter_of_nerf(height, width, focal_length, model_coarse, model_fine, ray_origins, ray_directions, options,
-                         mode="train", encode_position_fn=None, encode_direction_fn=None):
-    """nerf/train_utils.py:130-202."""
+                         mode="train", encode_position_fn=None, encode_direction_fn=None, occupancy=None):
+    """nerf/train_utils.py:130-202.  occupancy: see predict_and_render_radiance (mode="validation" only); the grid's view_counts
+    are zeroed first, so that after the call they are the sums over every ray chunk of this call."""
     if not ray_directions.is_cuda:
         raise RuntimeError("run_one_iter_of_nerf needs CUDA (HIP) tensors: nerf_pytorch_amd has no CPU path")
     restore_shapes = [ray_directions.shape, ray_directions.shape[:-1], ray_directions.shape[:-1]]
@@ -726,9 +752,17 @@ def run_one_iter_of_nerf(height, width, focal_length, model_coarse, model_fine, 
         restore_shapes += restore_shapes
     rays = pack_rays(ray_origins, ray_directions, options, height, width, focal_length)
     batches = get_minibatches(rays, chunksize=getattr(options.nerf, mode).chunksize)
-    pred = [predict_and_render_radiance(batch, model_coarse, model_fine, options,
-                                        encode_position_fn=encode_position_fn,
-                                        encode_direction_fn=encode_direction_fn) for batch in batches]
+    if occupancy is not None:
+        if mode != "validation":
+            raise NotImplementedError(_OCC_TRAIN_MSG)
+        occupancy.view_counts.zero_()
+        # (the options block the dense call below reads: like the reference, this function renders under `mode`'s DEFAULT)
+        pred = [_predict_culled(batch, model_coarse, model_fine, options.nerf.train, encode_position_fn, encode_direction_fn, occupancy)
+                for batch in batches]
+    else:
+        pred = [predict_and_render_radiance(batch, model_coarse, model_fine, options,
+                                            encode_position_fn=encode_position_fn,
+                                            encode_direction_fn=encode_direction_fn) for batch in batches]
     synthesized_images = list(zip(*pred))
     synthesized_images = [torch.cat(image, dim=0) if image[0] is not None else None for image in synthesized_images]
     if mode == "validation":
