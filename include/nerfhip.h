@@ -418,7 +418,7 @@ int nerfhip_render_grad_rays(nerfhip_plan_t plan_coarse, nerfhip_plan_t plan_fin
 /* ---- occupancy grid: the inference render skips empty space (Instant-NGP / NerfAcc / PlenOctrees style) ------------------------
  * One bit per cell of an axis-aligned box, built once from the trained density.  A sample whose point falls into an empty cell is
  * never sent through the MLP: its raw row becomes the EMPTY ROW (0, 0, 0, NERFHIP_OCC_EMPTY_RAW), whose sigma_a =
- * relu(raw[3] + noise) is exactly 0 -- a finite value on purpose: no 0 * inf can arise downstream.  Inference only.
+ * relu(raw[3] + noise) is exactly 0 -- a finite value on purpose: no 0 * inf can arise downstream.  (In training: further below.)
  *
  * Cell of point p: i_a = (int)floorf((p_a - lo_a) * inv_a), inv_a = res_a / (hi_a - lo_a) formed once on the host in fp32 (as
  * (float)res_a / (hi_a - lo_a)); bit index b = (i_z * res_y + i_y) * res_x + i_x lives in word b >> 5 at position b & 31.  The point
@@ -477,6 +477,46 @@ int nerfhip_render_fwd_occ(nerfhip_plan_t plan_coarse, nerfhip_plan_t plan_fine,
                            uint64_t ray_offset, const nerfhip_render_out* out, void* workspace, int64_t workspace_bytes,
                            int training, int parts, const nerfhip_occ_grid* grid_coarse, const nerfhip_occ_grid* grid_fine,
                            void* tmp, int64_t tmp_bytes, nerfhip_stream_t stream);
+
+/* ---- occupancy grid in training: the culled training forward, and a density grid that follows the nets -------------------------
+ * nerfhip_render_fwd_occ_train: nerfhip_render_fwd_occ as the forward of a TRAINING step.  Arguments as nerfhip_render_fwd_occ, with
+ * training = 1 or 2 naming the workspace layout as in nerfhip_render_fwd_parts; tmp and its four count words as in the inference call.
+ * It exists for plans whose training forward leaves nothing in the stash -- backward modes 2 (recompute), 3 (fused) and 4 (fused over
+ * the list) of nerfhip_plan_set_bwd_compaction: that forward is the inference forward, so the listed forward gives each kept sample's
+ * raw row bit for bit.  The backward entry points (nerfhip_render_bwd_parts, nerfhip_render_bwd) are used as they are: a culled
+ * sample's row is the empty row, its weight is exactly 0 and its d(loss)/d(raw) row exactly zero, so the list of a compacted
+ * backward (modes 2, 4) drops it by itself and the second forward runs over kept samples only -- the backward IS the gradient of the
+ * culled render.  Mode 3 is correct as well (the culled samples contribute exact zeros) but walks every sample: it saves no backward
+ * work.  Refused (NERFHIP_ERR_ARG, nothing launched): everything nerfhip_render_fwd_occ refuses except `training`; training not 1
+ * or 2; a pass that runs whose plan is in mode 0, 1 or 5, is inference-only (NERFHIP_PRECISION_F16X3), or has more sample points
+ * than the recomputing flow takes (ceil(M / 128) * 128 * 1024 >= 2^32). */
+int nerfhip_render_fwd_occ_train(nerfhip_plan_t plan_coarse, nerfhip_plan_t plan_fine, const nerfhip_render_cfg* cfg,
+                                 const float* rays, int64_t n_rays, const float* packed_coarse, const float* packed_fine,
+                                 const float* t_vals, const float* u_det, const nerfhip_render_rand* rnd, uint64_t seed,
+                                 uint64_t ray_offset, const nerfhip_render_out* out, void* workspace, int64_t workspace_bytes,
+                                 int training, int parts, const nerfhip_occ_grid* grid_coarse, const nerfhip_occ_grid* grid_fine,
+                                 void* tmp, int64_t tmp_bytes, nerfhip_stream_t stream);
+
+/* The density grid (Instant-NGP's update rule): dens, dev fp32 [ncells], 16-byte aligned, one value per cell in bit-index order.
+ * nerfhip_occ_density_update: probes and draws are EXACTLY those of nerfhip_occ_update -- same `pass` / counter rule, same tmp
+ * (nerfhip_occ_update_tmp_bytes(cell_count)) with the same layout kept after the call --, then for every cell b of the range
+ *     dens[b] = fmaxf(dens[b] * decay, s),   s = raw[3] > 0 ? raw[3] : 0   (a NaN raw[3]: s = 0, so dens[b] * decay stays)
+ * with one writer per cell (a thread takes four consecutive cells: 16-byte loads and stores).  grid: the box and the resolution are
+ * read; grid->bits is neither read nor written (it may be NULL).  decay in [0, 1].
+ * nerfhip_occ_density_bits: bit b of bits_out (dev [ncells / 32], every word written by its single writer) = dens[b] > thr,
+ * thr = min(tau, mean(dens)) -- a grid that is still nearly empty of density does not cull everything.  The mean is a two-stage sum
+ * in a fixed order, in fp64: one partial per workgroup of 4096 cells, then one workgroup over the partials in index order; rounded to
+ * fp32 once.  tmp (dev, 256-byte aligned, nerfhip_occ_density_bits_tmp_bytes(res)) keeps after the call: offset 0: thr (one float);
+ * offset 256: the partials (doubles).  res: host int[3].
+ * Refused (NERFHIP_ERR_ARG, nothing launched): a resolution out of range or a cell count no multiple of 32; hi <= lo; a cell range
+ * that is not 32-aligned or leaves the grid; pass outside 0 .. 4095; decay outside [0, 1] or NaN; a NaN tau; a NULL or misaligned
+ * pointer; tmp too small. */
+int nerfhip_occ_density_update(nerfhip_plan_t plan, const float* packed, const nerfhip_occ_grid* grid, float* dens, float decay,
+                               int pass, uint64_t seed, int64_t cell_first, int64_t cell_count, void* tmp, int64_t tmp_bytes,
+                               nerfhip_stream_t stream);
+int64_t nerfhip_occ_density_bits_tmp_bytes(const int* res);
+int nerfhip_occ_density_bits(const float* dens, const int* res, float tau, uint32_t* bits_out, void* tmp, int64_t tmp_bytes,
+                             nerfhip_stream_t stream);
 
 /* ---- loss + optimiser (train_nerf.py:244-270) ------------------------------------------------------------------ */
 /* mse_loss(rgb_coarse, target) + mse_loss(rgb_fine, target) and its cotangents; loss_out: dev float[3] =

@@ -149,6 +149,13 @@ _PROTOS = {
     "nerfhip_render_fwd_occ": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RenderCfg), c_f, c_i64, c_f, c_f, c_f, c_f,
                                           C.POINTER(RenderRand), c_u64, c_u64, C.POINTER(RenderOut), c_f, c_i64, C.c_int, C.c_int,
                                           C.POINTER(OccGrid), C.POINTER(OccGrid), c_f, c_i64, c_f]),
+    "nerfhip_render_fwd_occ_train": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RenderCfg), c_f, c_i64, c_f, c_f, c_f, c_f,
+                                                C.POINTER(RenderRand), c_u64, c_u64, C.POINTER(RenderOut), c_f, c_i64, C.c_int, C.c_int,
+                                                C.POINTER(OccGrid), C.POINTER(OccGrid), c_f, c_i64, c_f]),
+    "nerfhip_occ_density_update": (C.c_int, [C.c_void_p, c_f, C.POINTER(OccGrid), c_f, C.c_float, C.c_int, c_u64, c_i64, c_i64, c_f, c_i64,
+                                              c_f]),
+    "nerfhip_occ_density_bits_tmp_bytes": (c_i64, [C.POINTER(C.c_int)]),
+    "nerfhip_occ_density_bits": (C.c_int, [c_f, C.POINTER(C.c_int), C.c_float, c_f, c_f, c_i64, c_f]),
     "nerfhip_mse_loss_fwd_bwd": (C.c_int, [c_f, c_f, c_f, C.c_int, c_i64, C.c_float, c_f, c_f, c_f, c_f]),
     "nerfhip_adam_step": (C.c_int, [c_f, c_f, c_f, c_f, c_i64, C.c_float, C.c_float, C.c_float, C.c_float, c_i64,
                                      C.c_float, c_f]),

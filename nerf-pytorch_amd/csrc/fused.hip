@@ -124,8 +124,9 @@ struct OccPass {
 
 // MLP over the pass's depths -> compositing.  (a training forward leaves in the stash what the plan's backward will read there:
 // nh_mlp_forward_training)
-// occ (inference only): mark / list / empty rows (nh_occ_list) -> the MLP over the listed samples alone, each result at its sample's
-// own raw row -> the same compositing
+// occ: mark / list / empty rows (nh_occ_list) -> the MLP over the listed samples alone, each result at its sample's own raw row -> the
+// same compositing.  With `training` too (nerfhip_render_fwd_occ_train): the caller has checked that this plan's training forward
+// leaves nothing in the stash, so the listed inference forward is that training forward on the kept samples
 int forward_pass(const Call& c, const Pass& p, int training, float* rgb, float* disp, float* acc, float* weights, float* depth,
                  const OccPass* occ = nullptr) {
     const int64_t M = c.n * p.in.S;
@@ -232,7 +233,8 @@ extern "C" int nerfhip_render_workspace_region(nerfhip_plan_t plan_coarse, nerfh
     NH_REQUIRE(false, "render_workspace_region: unknown region '%s'", name);
 }
 
-// nerfhip_render_fwd_parts, and -- occ_c / occ_f: the passes' grids and lists, checked by the caller -- nerfhip_render_fwd_occ
+// nerfhip_render_fwd_parts, and -- occ_c / occ_f: the passes' grids and lists, checked by the caller -- nerfhip_render_fwd_occ and
+// nerfhip_render_fwd_occ_train
 static int render_fwd(nerfhip_plan_t pc, nerfhip_plan_t pf, const nerfhip_render_cfg* cfg, const float* rays, int64_t n,
                       const float* packed_c, const float* packed_f, const float* t_vals, const float* u_det,
                       const nerfhip_render_rand* rnd, uint64_t seed, uint64_t ray_offset, const nerfhip_render_out* out, void* workspace,
@@ -295,6 +297,48 @@ extern "C" int64_t nerfhip_render_occ_tmp_bytes(const nerfhip_render_cfg* cfg, i
     return nh_compact_ints(m > 0 ? m : 1) * 4;
 }
 
+// what nerfhip_render_fwd_occ and nerfhip_render_fwd_occ_train share: the checks of the grids, the plans and tmp, then render_fwd with
+// one list area behind both passes.  training != 0 (the _train entry point): a pass that runs must be one whose training forward
+// leaves nothing in the stash (nh_bwd_flow: recompute, no register-image stash) -- that forward IS the inference forward, so the
+// listed one stands in for it, and the plan's backward recomputes from the forward's input over its own list
+static int render_fwd_occ_any(const char* what, nerfhip_plan_t pc, nerfhip_plan_t pf, const nerfhip_render_cfg* cfg, const float* rays,
+                              int64_t n, const float* packed_c, const float* packed_f, const float* t_vals, const float* u_det,
+                              const nerfhip_render_rand* rnd, uint64_t seed, uint64_t ray_offset, const nerfhip_render_out* out,
+                              void* workspace, int64_t workspace_bytes, int training, int parts, const nerfhip_occ_grid* grid_c,
+                              const nerfhip_occ_grid* grid_f, void* tmp, int64_t tmp_bytes, nerfhip_stream_t stream) {
+    int rc;
+    NH_REQUIRE(parts >= 1 && parts <= 3, "%s: parts must be a combination of NERFHIP_PART_COARSE | NERFHIP_PART_FINE", what);
+    NH_REQUIRE(n >= 0, "%s: bad arguments", what);
+    const bool coarse_runs = (parts & NERFHIP_PART_COARSE) != 0, fine_runs = cfg->num_fine > 0 && (parts & NERFHIP_PART_FINE);
+    for (int fine = 0; fine < 2; ++fine) {
+        if (!(fine ? fine_runs : coarse_runs)) continue;
+        const nerfhip_occ_grid* g = fine ? grid_f : grid_c;
+        nerfhip_plan* p = fine ? pf : pc;
+        NH_REQUIRE(g, "%s: grid_%s is NULL", what, fine ? "fine" : "coarse");
+        if ((rc = nh_occ_check(g, what)) != 0 || (rc = nh_mlp_listed_check(p, what)) != 0) return rc;
+        if (training) {
+            const NhBwdFlow f = nh_bwd_flow(p, n * ((int64_t)cfg->num_coarse + (fine ? cfg->num_fine : 0)), true, false);
+            NH_REQUIRE(f.recompute && !f.reg_image,
+                       "%s: the %s plan's training forward leaves a stash (backward mode %d of nerfhip_plan_set_bwd_compaction, or an "
+                       "inference-only plan, or too many sample points for the recomputing flow): the culled training forward works "
+                       "with modes 2 (recompute), 3 (fused) and 4 (fused over the list)",
+                       what, fine ? "fine" : "coarse", p->bwd_compact);
+        }
+    }
+    const int64_t m_max = n * ((int64_t)cfg->num_coarse + cfg->num_fine);
+    NH_REQUIRE(m_max < ((int64_t)1 << 31), "%s: at most 2^31 - 1 sample points per pass (got %lld)", what, (long long)m_max);
+    const int64_t need = nerfhip_render_occ_tmp_bytes(cfg, n);
+    NH_REQUIRE(tmp && tmp_bytes >= need, "%s: tmp too small (%lld < %lld)", what, (long long)tmp_bytes, (long long)need);
+    OccPass oc, of;
+    oc.grid = grid_c;
+    oc.list = nh_compact_view((int*)tmp, m_max > 0 ? m_max : 1);
+    of.grid = grid_f;
+    of.list = oc.list;
+    of.list.stats = oc.list.stats + 2;
+    return render_fwd(pc, pf, cfg, rays, n, packed_c, packed_f, t_vals, u_det, rnd, seed, ray_offset, out, workspace, workspace_bytes,
+                      training, parts, stream, &oc, &of);
+}
+
 extern "C" int nerfhip_render_fwd_occ(nerfhip_plan_t pc, nerfhip_plan_t pf, const nerfhip_render_cfg* cfg, const float* rays,
                                       int64_t n, const float* packed_c, const float* packed_f, const float* t_vals,
                                       const float* u_det, const nerfhip_render_rand* rnd, uint64_t seed, uint64_t ray_offset,
@@ -307,29 +351,22 @@ extern "C" int nerfhip_render_fwd_occ(nerfhip_plan_t pc, nerfhip_plan_t pf, cons
                "render_fwd_occ: an occupancy grid culls the inference render only (training = %d): the training forward and its backward "
                "run dense",
                training);
-    NH_REQUIRE(parts >= 1 && parts <= 3, "render_fwd_occ: parts must be a combination of NERFHIP_PART_COARSE | NERFHIP_PART_FINE");
-    NH_REQUIRE(n >= 0, "render_fwd_occ: bad arguments");
-    const bool coarse_runs = (parts & NERFHIP_PART_COARSE) != 0, fine_runs = cfg->num_fine > 0 && (parts & NERFHIP_PART_FINE);
-    if (coarse_runs) {
-        NH_REQUIRE(grid_c, "render_fwd_occ: grid_coarse is NULL");
-        if ((rc = nh_occ_check(grid_c, "render_fwd_occ")) != 0 || (rc = nh_mlp_listed_check(pc, "render_fwd_occ")) != 0) return rc;
-    }
-    if (fine_runs) {
-        NH_REQUIRE(grid_f, "render_fwd_occ: grid_fine is NULL");
-        if ((rc = nh_occ_check(grid_f, "render_fwd_occ")) != 0 || (rc = nh_mlp_listed_check(pf, "render_fwd_occ")) != 0) return rc;
-    }
-    const int64_t m_max = n * ((int64_t)cfg->num_coarse + cfg->num_fine);
-    NH_REQUIRE(m_max < ((int64_t)1 << 31), "render_fwd_occ: at most 2^31 - 1 sample points per pass (got %lld)", (long long)m_max);
-    const int64_t need = nerfhip_render_occ_tmp_bytes(cfg, n);
-    NH_REQUIRE(tmp && tmp_bytes >= need, "render_fwd_occ: tmp too small (%lld < %lld)", (long long)tmp_bytes, (long long)need);
-    OccPass oc, of;
-    oc.grid = grid_c;
-    oc.list = nh_compact_view((int*)tmp, m_max > 0 ? m_max : 1);
-    of.grid = grid_f;
-    of.list = oc.list;
-    of.list.stats = oc.list.stats + 2;
-    return render_fwd(pc, pf, cfg, rays, n, packed_c, packed_f, t_vals, u_det, rnd, seed, ray_offset, out, workspace, workspace_bytes, 0,
-                      parts, stream, &oc, &of);
+    return render_fwd_occ_any("render_fwd_occ", pc, pf, cfg, rays, n, packed_c, packed_f, t_vals, u_det, rnd, seed, ray_offset, out,
+                              workspace, workspace_bytes, 0, parts, grid_c, grid_f, tmp, tmp_bytes, stream);
+}
+
+extern "C" int nerfhip_render_fwd_occ_train(nerfhip_plan_t pc, nerfhip_plan_t pf, const nerfhip_render_cfg* cfg, const float* rays,
+                                            int64_t n, const float* packed_c, const float* packed_f, const float* t_vals,
+                                            const float* u_det, const nerfhip_render_rand* rnd, uint64_t seed, uint64_t ray_offset,
+                                            const nerfhip_render_out* out, void* workspace, int64_t workspace_bytes, int training,
+                                            int parts, const nerfhip_occ_grid* grid_c, const nerfhip_occ_grid* grid_f, void* tmp,
+                                            int64_t tmp_bytes, nerfhip_stream_t stream) {
+    int rc = check_cfg(pc, pf, cfg);
+    if (rc) return rc;
+    NH_REQUIRE(training == 1 || training == 2,
+               "render_fwd_occ_train: training must be 1 (two sets of backward buffers) or 2 (shared), got %d", training);
+    return render_fwd_occ_any("render_fwd_occ_train", pc, pf, cfg, rays, n, packed_c, packed_f, t_vals, u_det, rnd, seed, ray_offset, out,
+                              workspace, workspace_bytes, training, parts, grid_c, grid_f, tmp, tmp_bytes, stream);
 }
 
 extern "C" int nerfhip_render_fwd(nerfhip_plan_t pc, nerfhip_plan_t pf, const nerfhip_render_cfg* cfg, const float* rays,

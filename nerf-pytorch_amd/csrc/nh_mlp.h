@@ -47,6 +47,14 @@ int nh_mlp_forward_f16w_listed(nerfhip_plan* p, const float* packed, const NhMlp
 // occ/occupancy.hip: checks a caller's grid (`what` names the entry point in the message); lists the occupied samples of a pass into
 // `list` (ascending, padded, stats = {kept, total}) and writes the empty row into `raw` for every other sample
 int nh_occ_check(const nerfhip_occ_grid* g, const char* what);
+int nh_occ_check_box(const nerfhip_occ_grid* g, const char* what);  // the same without the bits: resolution and box
+int nh_occ_check_res(const int* res, const char* what);
+// ... and the probe-and-forward part of nerfhip_occ_update, which nerfhip_occ_density_update (occ/occ_train.hip) shares: the checks
+// of plan, pass and cell range; then tmp, the probes and the plan's inference forward over them (*raw: the output rows inside tmp)
+int nh_occ_probe_check(const char* what, nerfhip_plan_t plan, const float* packed, const nerfhip_occ_grid* grid, int pass,
+                       int64_t cell_first, int64_t cell_count);
+int nh_occ_probe_run(const char* what, nerfhip_plan_t plan, const float* packed, const nerfhip_occ_grid* grid, int pass, uint64_t seed,
+                     int64_t cell_first, int64_t cell_count, void* tmp, int64_t tmp_bytes, nerfhip_stream_t stream, float** raw);
 int nh_occ_list(const nerfhip_occ_grid* g, const float* rays, int ray_stride, const float* z, int S, int64_t M, float* raw,
                 const NhCompact& list, nerfhip_stream_t stream);
 

@@ -4,7 +4,8 @@
 // occupied cell -- the count / scatter kernels of nh_list.h, which compact.hip uses with another predicate: ascending sample index, no
 // atomics -- and writes the empty row (0, 0, 0, NERFHIP_OCC_EMPTY_RAW) for every other sample in the scatter launch; the MLP then runs
 // over the list alone (the LIST instantiations of the forward kernels).  The grid itself is built by nerfhip_occ_update (one probe per
-// cell through the plan's ordinary fused-input forward, S = 1) and nerfhip_occ_dilate.
+// cell through the plan's ordinary fused-input forward, S = 1) and nerfhip_occ_dilate.  The probe-and-forward part is shared with the
+// density grid of training (occ_train.hip): nh_occ_probe_check / nh_occ_probe_run.
 #include "../nh_list.h"
 #include "../nh_occ.h"
 
@@ -141,9 +142,16 @@ NhOccGrid device_grid(const nerfhip_occ_grid* g) {
 
 }  // namespace
 
+int nh_occ_check_res(const int* res, const char* what) { return check_res(res, what); }
+
 int nh_occ_check(const nerfhip_occ_grid* g, const char* what) {
     NH_REQUIRE(g, "%s: the occupancy grid is NULL", what);
     NH_REQUIRE(g->bits, "%s: the occupancy grid has no bits", what);
+    return nh_occ_check_box(g, what);
+}
+
+int nh_occ_check_box(const nerfhip_occ_grid* g, const char* what) {
+    NH_REQUIRE(g, "%s: the occupancy grid is NULL", what);
     const int rc = check_res(g->res, what);
     if (rc) return rc;
     for (int a = 0; a < 3; ++a)
@@ -179,21 +187,24 @@ extern "C" int64_t nerfhip_occ_update_tmp_bytes(int64_t cell_count) {
     return align256(cell_count * 44) + align256(cell_count * 4) + align256(cell_count * 16);
 }
 
-extern "C" int nerfhip_occ_update(nerfhip_plan_t plan, const float* packed, const nerfhip_occ_grid* grid, float tau, int pass,
-                                  uint64_t seed, int64_t cell_first, int64_t cell_count, void* tmp, int64_t tmp_bytes,
-                                  nerfhip_stream_t stream) {
-    int rc = nh_occ_check(grid, "occ_update");
-    if (rc) return rc;
-    NH_REQUIRE(plan && packed, "occ_update: plan / packed is NULL");
+// The probe-and-forward part of nerfhip_occ_update, shared with nerfhip_occ_density_update (occ_train.hip).  nh_occ_probe_check: the
+// plan, the pass and the cell range (the grid's box is the caller's to check); nh_occ_probe_run: tmp, then one probe per cell of the
+// range and the plan's inference forward over them -- *raw: the output rows inside tmp (the layout of include/nerfhip.h)
+int nh_occ_probe_check(const char* what, nerfhip_plan_t plan, const float* packed, const nerfhip_occ_grid* grid, int pass,
+                       int64_t cell_first, int64_t cell_count) {
+    NH_REQUIRE(plan && packed, "%s: plan / packed is NULL", what);
     const int64_t ncells = (int64_t)grid->res[0] * grid->res[1] * grid->res[2];
-    NH_REQUIRE(pass >= 0 && pass < 4096, "occ_update: pass must be 0 .. 4095 (got %d)", pass);
+    NH_REQUIRE(pass >= 0 && pass < 4096, "%s: pass must be 0 .. 4095 (got %d)", what, pass);
     NH_REQUIRE(cell_first >= 0 && cell_count >= 0 && cell_first % 32 == 0 && cell_count % 32 == 0 && cell_first + cell_count <= ncells,
-               "occ_update: cells [%lld, %lld + %lld) must be multiples of 32 inside the grid's %lld cells", (long long)cell_first,
+               "%s: cells [%lld, %lld + %lld) must be multiples of 32 inside the grid's %lld cells", what, (long long)cell_first,
                (long long)cell_first, (long long)cell_count, (long long)ncells);
-    NH_REQUIRE(tau == tau, "occ_update: tau is NaN");
-    if (cell_count == 0) return NERFHIP_OK;
+    return NERFHIP_OK;
+}
+
+int nh_occ_probe_run(const char* what, nerfhip_plan_t plan, const float* packed, const nerfhip_occ_grid* grid, int pass, uint64_t seed,
+                     int64_t cell_first, int64_t cell_count, void* tmp, int64_t tmp_bytes, nerfhip_stream_t stream, float** raw_out) {
     const int64_t need = nerfhip_occ_update_tmp_bytes(cell_count);
-    NH_REQUIRE(tmp && tmp_bytes >= need, "occ_update: tmp too small (%lld < %lld)", (long long)tmp_bytes, (long long)need);
+    NH_REQUIRE(tmp && tmp_bytes >= need, "%s: tmp too small (%lld < %lld)", what, (long long)tmp_bytes, (long long)need);
     ProbeArgs a;
     memset(&a, 0, sizeof(a));
     for (int ax = 0; ax < 3; ++ax) {
@@ -203,14 +214,14 @@ extern "C" int nerfhip_occ_update(nerfhip_plan_t plan, const float* packed, cons
     }
     a.pass = pass;
     a.seed = seed;
-    a.ncells = ncells;
+    a.ncells = (int64_t)grid->res[0] * grid->res[1] * grid->res[2];
     a.cell_first = cell_first;
     a.cell_count = cell_count;
     a.rows = (float*)tmp;
     a.z = (float*)((char*)tmp + align256(cell_count * 44));
     float* const raw = (float*)((char*)a.z + align256(cell_count * 4));
     NH_LAUNCH(k_occ_probe, nh_ceil_div(cell_count, 256), 256, 0, stream, a);
-    rc = nh_launch_status("occ_probe");
+    int rc = nh_launch_status("occ_probe");
     if (rc) return rc;
     NhMlpInput in;
     memset(&in, 0, sizeof(in));
@@ -219,7 +230,21 @@ extern "C" int nerfhip_occ_update(nerfhip_plan_t plan, const float* packed, cons
     in.ray_stride = 11;
     in.z = a.z;
     in.S = 1;
-    rc = nh_mlp_forward(plan, packed, in, cell_count, raw, nullptr, stream);
+    *raw_out = raw;
+    return nh_mlp_forward(plan, packed, in, cell_count, raw, nullptr, stream);
+}
+
+extern "C" int nerfhip_occ_update(nerfhip_plan_t plan, const float* packed, const nerfhip_occ_grid* grid, float tau, int pass,
+                                  uint64_t seed, int64_t cell_first, int64_t cell_count, void* tmp, int64_t tmp_bytes,
+                                  nerfhip_stream_t stream) {
+    int rc = nh_occ_check(grid, "occ_update");
+    if (rc) return rc;
+    rc = nh_occ_probe_check("occ_update", plan, packed, grid, pass, cell_first, cell_count);
+    if (rc) return rc;
+    NH_REQUIRE(tau == tau, "occ_update: tau is NaN");
+    if (cell_count == 0) return NERFHIP_OK;
+    float* raw = nullptr;
+    rc = nh_occ_probe_run("occ_update", plan, packed, grid, pass, seed, cell_first, cell_count, tmp, tmp_bytes, stream, &raw);
     if (rc) return rc;
     const int64_t nwords = cell_count / 32;
     NH_LAUNCH(k_occ_or, nh_ceil_div(nwords, 256), 256, 0, stream, (const float*)raw, nwords, tau,

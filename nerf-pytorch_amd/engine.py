@@ -16,6 +16,10 @@ backward.  Default: two streams for nets narrower than 256 (measured +3.5 %), on
 Data parallelism (BASELINE config 3): one process per GPU, weights replicated, each rank renders its own N/G rays;
 the only exchange is the all-reduce (sum) of the 2 x 595,844-float gradient (one collective per net), scaled by 1/G
 inside the Adam kernel.  Every rank applies the identical update, so no parameter broadcast is needed after step 0.
+
+Occupancy grid (`occupancy=`, one rank): from a warm-up on both forwards are nerfhip_render_fwd_occ_train through
+the grid (main stream, one list area), the nets' backwards run in a mode that keeps no stash, and every few optimizer steps the
+grid's density is updated from the images just packed.
 """
 import ctypes as C
 import math
@@ -33,7 +37,8 @@ from .parallel import allreduce_gradients, shard_bounds
 class TrainEngine:
     def __init__(self, model_coarse, model_fine, num_coarse, num_fine, perturb=True, lindisp=False, white_background=False,
                  noise_std=0.0, lr=5e-3, betas=(0.9, 0.999), eps=1e-8, seed=0, process_group=None, world_size=None,
-                 rank=None, overlap=None, always_reduce=False, backward=None, window=None, total_steps=None):
+                 rank=None, overlap=None, always_reduce=False, backward=None, window=None, total_steps=None, occupancy=None,
+                 occupancy_warmup=256, occupancy_every=16):
         self.lib = L.get_lib()
         self.mc, self.mf = model_coarse, model_fine if num_fine > 0 else None
         self.dev = model_coarse.flat_params.device
@@ -88,6 +93,24 @@ class TrainEngine:
         # compacted steps reported (read back asynchronously: no host synchronisation), see _choose_backward_modes
         self.backward = backward
         self._nets = tuple((name, m) for name, m in (("coarse", self.mc), ("fine", self.mf)) if m is not None)
+        # occupancy grid in training (None: the step as it always was).  From step `occupancy_warmup` on the two
+        # forwards are nerfhip_render_fwd_occ_train through `occupancy` (an occupancy.OccupancyGrid; both on the main stream, ONE
+        # engine-owned list area), every net's backward runs in a mode whose training forward leaves no stash ("recompute", or
+        # "fused_compact" where the net has the fused backward), and every `occupancy_every`-th optimizer_step -- during the warm-up
+        # already -- updates the grid from the nets just packed (grid.update_density; a grid without a density is left as it is)
+        self.occupancy, self.occupancy_warmup, self.occupancy_every = occupancy, int(occupancy_warmup), int(occupancy_every)
+        self._occ_tmp, self._occ_tb = None, 0
+        if occupancy is not None:
+            if world_size > 1:
+                raise NotImplementedError("TrainEngine: occupancy=... with world size %d is not implemented; run it with one rank"
+                                          % world_size)
+            if self.occupancy_every < 1 or self.occupancy_warmup < 0:
+                raise ValueError("TrainEngine: occupancy_every must be >= 1 and occupancy_warmup >= 0")
+            if occupancy.bits.device != self.dev:
+                raise RuntimeError("TrainEngine: the occupancy grid lives on %s, the engine on %s" % (occupancy.bits.device, self.dev))
+            if backward not in (None, "auto") and BM.parse(backward) not in (BM.RECOMPUTE, BM.FUSED_COMPACT):
+                raise ValueError("TrainEngine: occupancy=... culls the training forward of a backward that keeps no stash and walks a "
+                                 "sample list: backward must be None, 'auto', 'recompute' or 'fused_compact' (got %r)" % (backward,))
         if backward not in (None, "auto"):
             mode = BM.parse(backward)   # (ValueError for anything that is not a mode)
             for _, m in self._nets:
@@ -151,6 +174,9 @@ class TrainEngine:
         self._wsb = wsb
         self._ws_n = n
         mk = lambda *s: torch.empty(s, dtype=torch.float32, device=self.dev)  # noqa: E731
+        if self.occupancy is not None:   # (the list area of the culled forwards; its first four words: occupancy_counts)
+            self._occ_tb = lib.render_occ_tmp_bytes(C.byref(self.cfg), n)
+            self._occ_tmp = torch.zeros(self._occ_tb // 4 + 64, dtype=torch.int32, device=self.dev)
         self._bufs = dict(rgb_c=mk(n, 3), rgb_f=mk(n, 3), g_c=mk(n, 3), g_f=mk(n, 3), disp_c=mk(n), acc_c=mk(n),
                           disp_f=mk(n), acc_f=mk(n))
 
@@ -231,6 +257,10 @@ class TrainEngine:
         The exposure sits behind the render: it asks for no ray gradient.  With frozen=True and no ray_grad the step is the
         test-time fit: the two forwards, the two losses and the table gradient, no render backward.  One rank only."""
         self._check_inputs(rays, target)
+        if self.occupancy is not None and (ray_grad is not None or frozen):
+            raise NotImplementedError("TrainEngine: a step with a ray gradient (pose, camera, intrinsics or distortion gradients) or a "
+                                      "frozen step (localize_*) is not implemented with occupancy=...: the ray gradient of the culled "
+                                      "render is not covered")
         if frozen and ray_grad is None and exposure is None:
             raise RuntimeError("TrainEngine: forward_backward(frozen=True) computes the ray gradient alone: pass ray_grad=... "
                                "(or exposure=...: the fit of the exposure table alone)")
@@ -251,8 +281,11 @@ class TrainEngine:
                                    % (tuple(rays.shape), self.dev))
         lib, n = self.lib, rays.shape[0]
         gscale = 1.0 if global_rays is None else float(n) * self.world / float(global_rays)
+        culled = self._occupancy_active()
         if self.backward == "auto" and not frozen:
             self._choose_backward_modes()
+        elif culled and self.backward is None:
+            self._set_culled_modes(count=False)
         if self._set_window():   # (optimizer_step packed for this step already; only a step_count or schedule changed by hand gets here)
             self.repack()
         self._prepare(n)
@@ -313,6 +346,11 @@ class TrainEngine:
             if not frozen:
                 model._window_grads(grad, model._window_w, stream)
 
+        if culled:   # (the grid's struct is read during the call; one list area serves both forwards: both run on the main stream)
+            occ = C.byref(self.occupancy._struct())
+            fwd = lambda part, stream: lib.render_fwd_occ_train(*fwd_args, part, occ, occ, self._occ_tmp.data_ptr(), self._occ_tb, stream)  # noqa: E731
+        else:
+            fwd = lambda part, stream: lib.render_fwd_parts(*fwd_args, part, stream)  # noqa: E731
         coarse = (L.PART_COARSE, b["rgb_c"], b["g_c"], cot_c, self._loss_c, gc, self.mc, tmp_c, g_rays_c)
         fine = (L.PART_FINE, b["rgb_f"], b["g_f"], cot_f, self._loss_f, gf, self.mf, tmp_f, ray_grad)
         self._pending = []
@@ -320,7 +358,7 @@ class TrainEngine:
             main, side = self._streams()
             st = main.cuda_stream
             two = self.overlap and nf > 0
-            lib.render_fwd_parts(*fwd_args, L.PART_COARSE, st)
+            fwd(L.PART_COARSE, st)
             if two:   # the coarse net's pass next to the fine forward and backward
                 e1, e2 = self._ev
                 e1.record(main)
@@ -328,7 +366,7 @@ class TrainEngine:
                 net_pass(*coarse, side.cuda_stream)
                 e2.record(side)
             if nf > 0:
-                lib.render_fwd_parts(*fwd_args, L.PART_FINE, st)
+                fwd(L.PART_FINE, st)
                 net_pass(*fine, st)
                 if self._reduce and not frozen:  # in flight while the coarse backward computes
                     self._pending.append(allreduce_gradients(gf, self.pg, async_op=True, single_rank=True))
@@ -357,12 +395,34 @@ class TrainEngine:
         words per net have arrived on the host (an asynchronous copy behind that step's backward; polled, never waited for); a net that
         runs dense produces none, so every backward_mode.PROBE_EVERY-th step runs compacted to look again."""
         self._stats.poll()
+        if self._occupancy_active():   # (the culled forward fixes the modes; they are counted, and their statistics read, as ever)
+            return self._set_culled_modes(count=True)
         probe = self.step_count % BM.PROBE_EVERY == 0
         for name, m in self._nets:
             mode = BM.choose(self._zero_frac[name], m.training_precision != "fp32", m.fused_backward_available(), probe)
             if m.backward_compaction != mode:
                 m._apply_backward(mode)
             self.backward_modes_used[name][mode] += 1
+
+    def _occupancy_active(self):
+        """Whether the step about to run culls its samples through the grid (from step `occupancy_warmup` on)."""
+        return self.occupancy is not None and self.step_count >= self.occupancy_warmup
+
+    def _set_culled_modes(self, count):
+        """The backward modes of a culled step (backward=None / "auto"): each net recomputes over its list -- in the fused kernel where
+        it has one."""
+        for name, m in self._nets:
+            mode = BM.FUSED_COMPACT if m.fused_backward_available() else BM.RECOMPUTE
+            if m.backward_compaction != mode:
+                m._apply_backward(mode)
+            if count:
+                self.backward_modes_used[name][mode] += 1
+
+    @property
+    def occupancy_counts(self):
+        """{kept_coarse, total_coarse, kept_fine, total_fine} of the last culled step's forwards: an int32 device view of the list
+        area's first four words (no copy, no sync; zeros before the first culled step); None without a grid."""
+        return None if self._occ_tmp is None else self._occ_tmp[:4]
 
     def _stats_words(self, name):
         """The two statistics words of net `name` in the workspace of the last step."""
@@ -447,6 +507,11 @@ class TrainEngine:
                               st)
         self._set_window()   # (the window of the step that follows: its images are packed here)
         self.repack()
+        g = self.occupancy
+        if g is not None and g.density is not None and self.step_count % self.occupancy_every == 0:
+            # (the engine's own plans and the images just packed: no second pack; on the stream of the step -- the next forward follows it)
+            g.update_density(((self.mc._plan, self.packed_c), (self.mf._plan if self.mf is not None else None, self.packed_f)),
+                             self.step_count // self.occupancy_every)
 
     def step(self, rays, target, ray_offset=0, lr=None, global_rays=None, draws=None, ray_grad=None):
         """One full training iteration.  Returns the device tensor {coarse_mse, fine_mse, sum} (no host sync)."""

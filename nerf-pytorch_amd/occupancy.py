@@ -1,6 +1,10 @@
 """Occupancy grid of the inference render: one bit per cell of a box around the scene, built once from the trained density
 (Instant-NGP / NerfAcc / PlenOctrees style).  A sample whose point falls into an empty cell is never sent through the MLPs
-(include/nerfhip.h "occupancy grid").  Inference only.
+(include/nerfhip.h "occupancy grid").
+
+In training the grid is kept alive while the nets change: OccupancyGrid.for_training starts from an all-ones grid with a
+zero density per cell, TrainEngine(..., occupancy=grid) culls its steps' samples through it from a warm-up on and calls
+grid.update_density every few steps (decayed running maximum of the probed density, thresholded at min(threshold, mean density)).
 
     grid = OccupancyGrid.from_models(model_coarse, model_fine, aabb=((-1.5, -1.5, -1.5), (1.5, 1.5, 1.5)))
     with torch.no_grad():
@@ -47,6 +51,10 @@ class OccupancyGrid:
         if bits.dtype != torch.int32 or bits.numel() != words or not bits.is_contiguous():
             raise ValueError("bits: a contiguous int32 tensor of %d words" % words)
         self.bits = bits
+        self.density = None     # fp32 [num_cells] on the device: the density grid of training (for_training / update_density), else None
+        self.update_count = 0   # update_density calls so far: the next one probes with pass 1 + update_count mod 4095
+        self._scratch = None    # update_density's buffers (second bits buffer, the two tmp areas), made on first use
+        self.last_threshold = None   # after update_density: a device view of min(threshold, mean density) of that call
         self.last_counts = torch.zeros(4, dtype=torch.int32, device=bits.device)
         self.view_counts = torch.zeros(4, dtype=torch.int64, device=bits.device)
 
@@ -96,6 +104,63 @@ class OccupancyGrid:
             grid.bits = out
         return grid
 
+    @classmethod
+    def for_training(cls, aabb, resolution=128, outside=False, device="cuda"):
+        """The grid a training run starts from: every bit set (nothing is culled until update_density has seen the nets) and a zero
+        density per cell."""
+        res = _resolution(resolution)
+        ncells = res[0] * res[1] * res[2]
+        grid = cls(torch.full((ncells // 32,), -1, dtype=torch.int32, device=device), aabb, res, outside)
+        grid.density = torch.zeros(ncells, dtype=torch.float32, device=grid.bits.device)
+        return grid
+
+    def update_slab(self, step, fraction=0.25):
+        """(first cell, cell count) of the slab update_density(step=...) probes: the grid is cut into ceil(1 / fraction) contiguous,
+        32-aligned slabs and call `step` takes slab step mod that number -- any ceil(1 / fraction) consecutive steps cover the grid."""
+        if not 0.0 < float(fraction) <= 1.0:
+            raise ValueError("fraction must lie in (0, 1] (got %r)" % (fraction,))
+        nslabs = int(-(-1.0 // float(fraction)))
+        slab = -(-(self.num_cells // 32) // nslabs) * 32
+        first = (int(step) % nslabs) * slab
+        return min(first, self.num_cells), max(0, min(slab, self.num_cells - first))
+
+    def update_density(self, plans_and_packed, step, decay=0.95, threshold=0.01, fraction=0.25, dilate=1, seed=0, chunk_cells=1 << 20):
+        """One update of the density grid and, from it, of the bits (Instant-NGP's rule), on the current stream, with no host
+        synchronisation.  plans_and_packed: (plan, packed image) pairs of the nets to probe (TrainEngine passes its own training
+        plans and the images its optimizer step just packed).  step: the index of this update in the caller's schedule
+        (TrainEngine: step_count // occupancy_every): it picks the slab of update_slab(step, fraction), one jittered probe per cell
+        of it (pass 1 + update_count mod 4095 of nerfhip_occ_update's counter rule).  There
+            density = max(density * decay, max over the nets of relu(sigma))            (nerfhip_occ_density_update)
+        and then, over the whole grid, bit = density > min(threshold, mean(density)) (nerfhip_occ_density_bits), dilated `dilate`
+        times across faces.  `bits` changes through `density` alone."""
+        if self.density is None:
+            raise RuntimeError("OccupancyGrid.update_density needs a density grid: build the grid with OccupancyGrid.for_training")
+        lib = L.get_lib()
+        first, count = self.update_slab(step, fraction)
+        chunk = max(32, min(int(chunk_cells), max(count, 32)) // 32 * 32)
+        res = (C.c_int * 3)(*self.resolution)
+        dev = self.bits.device
+        if self._scratch is None or self._scratch[0] != chunk:
+            tb, bb = int(lib.occ_update_tmp_bytes(chunk)), int(lib.occ_density_bits_tmp_bytes(res))
+            self._scratch = (chunk, torch.empty_like(self.bits), torch.empty(tb // 4 + 64, dtype=torch.float32, device=dev), tb,
+                             torch.empty(bb // 4 + 64, dtype=torch.float32, device=dev), bb)
+        _, alt, tmp, tb, btmp, bb = self._scratch
+        g = self._struct()
+        k = 1 + self.update_count % 4095
+        nets = [(plan, packed) for plan, packed in plans_and_packed if plan is not None]
+        with L.launch_on(self.bits, self.density, tmp, *[packed for _, packed in nets]) as st:
+            for i, (plan, packed) in enumerate(nets):   # (the first net decays; the others only raise: the max over the nets)
+                for c0 in range(first, first + count, chunk):
+                    lib.occ_density_update(plan, packed.data_ptr(), C.byref(g), self.density.data_ptr(), float(decay) if i == 0 else 1.0,
+                                           k, int(seed), c0, min(chunk, first + count - c0), tmp.data_ptr(), tb, st)
+            cur, other = (self.bits, alt) if int(dilate) % 2 == 0 else (alt, self.bits)   # (the last write lands in self.bits)
+            lib.occ_density_bits(self.density.data_ptr(), res, float(threshold), cur.data_ptr(), btmp.data_ptr(), bb, st)
+            for _ in range(int(dilate)):
+                lib.occ_dilate(cur.data_ptr(), other.data_ptr(), res, st)
+                cur, other = other, cur
+        self.last_threshold = btmp[:1]   # (a device view of min(threshold, mean density): no copy, no sync)
+        self.update_count += 1
+
     def occupied_fraction(self):
         """Set cells / cells (a host sync)."""
         b = self.bits.view(torch.uint8)
@@ -104,8 +169,12 @@ class OccupancyGrid:
 
     # ---- checkpoints ---------------------------------------------------------------------------------------------------
     def state_dict(self):
-        return {"bits": self.bits.detach().cpu().clone(), "aabb": torch.tensor(self.aabb, dtype=torch.float32),
-                "resolution": torch.tensor(self.resolution, dtype=torch.int32), "outside": torch.tensor(int(self.outside))}
+        state = {"bits": self.bits.detach().cpu().clone(), "aabb": torch.tensor(self.aabb, dtype=torch.float32),
+                 "resolution": torch.tensor(self.resolution, dtype=torch.int32), "outside": torch.tensor(int(self.outside))}
+        if self.density is not None:   # (a grid of training: its density and the count its probes' pass numbers follow)
+            state["density"] = self.density.detach().cpu().clone()
+            state["update_count"] = torch.tensor(int(self.update_count))
+        return state
 
     def load_state_dict(self, state):
         aabb = _aabb(tuple(tuple(float(v) for v in row) for row in state["aabb"].tolist()))
@@ -113,7 +182,13 @@ class OccupancyGrid:
         bits = state["bits"].to(device=self.bits.device, dtype=torch.int32).contiguous()
         if bits.numel() != res[0] * res[1] * res[2] // 32:
             raise ValueError("state_dict: %d words of bits for resolution %r" % (bits.numel(), res))
+        density = None
+        if "density" in state:
+            density = state["density"].to(device=self.bits.device, dtype=torch.float32).contiguous()
+            if density.numel() != res[0] * res[1] * res[2]:
+                raise ValueError("state_dict: %d density values for resolution %r" % (density.numel(), res))
         self.aabb, self.resolution, self.outside, self.bits = aabb, res, bool(int(state["outside"])), bits
+        self.density, self.update_count, self._scratch = density, int(state.get("update_count", 0)), None
         return self
 
     @classmethod
