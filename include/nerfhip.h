@@ -329,7 +329,9 @@ int64_t nerfhip_render_workspace_bytes(nerfhip_plan_t plan_coarse, nerfhip_plan_
  * name = "z_coarse" [n,nc] (nerf/train_utils.py:58-65), "raw_coarse" [n,nc,4] (run_network's output, :70-77),
  * "weights_coarse" [n,nc] (:86), "z_fine" [n,nc+nf] (:103-105), "raw_fine" [n,nc+nf,4] (:108-115).  The reference
  * function returns none of them; the parity tests read the sample depths to count inverse-CDF index flips.
- * Training layouts also name "bwd_scratch_coarse" / "bwd_scratch_fine": the scratch each net's backward runs in. */
+ * Training layouts also name "bwd_scratch_coarse" / "bwd_scratch_fine": the scratch each net's backward runs in, and
+ * "bwd_g_raw_coarse" [n,nc,4] / "bwd_g_raw_fine" [n,nc+nf,4]: d(loss)/d(raw) as the net's compositing backward left it (training = 2:
+ * the two share one buffer, which holds the rows of the net whose backward ran last). */
 int nerfhip_render_workspace_region(nerfhip_plan_t plan_coarse, nerfhip_plan_t plan_fine, const nerfhip_render_cfg* cfg,
                                     int64_t n_rays, int training, const char* name, int64_t* offset, int64_t* bytes);
 
@@ -398,6 +400,55 @@ int nerfhip_render_bwd_rays(nerfhip_plan_t plan_coarse, nerfhip_plan_t plan_fine
                             const nerfhip_render_cotangents* g, void* workspace, int64_t workspace_bytes,
                             float* g_params_coarse, float* g_params_fine, int parts, const float* params_coarse,
                             const float* params_fine, void* tmp, int64_t tmp_bytes, float* g_rays, nerfhip_stream_t stream);
+
+/* The two backward entry points above with a cotangent of the RAY WEIGHTS w_i = alpha_i T_i of each pass as well (losses on the
+ * distribution of weights along a ray: nerfhip_spread_loss below): g_weights_coarse dev [n, num_coarse], g_weights_fine dev
+ * [n, num_coarse + num_fine], each NULL = 0.  They reach the compositing backward as nerfhip_volume_render_bwd's g_weights; a pass
+ * runs if any of its four cotangents is given.  The first six members are nerfhip_render_cotangents; with both weight cotangents NULL
+ * each call is, bit for bit, the entry point it extends. */
+typedef struct nerfhip_render_cotangents_w {
+    const float* g_rgb_coarse;
+    const float* g_acc_coarse;
+    const float* g_depth_coarse;
+    const float* g_rgb_fine;
+    const float* g_acc_fine;
+    const float* g_depth_fine;
+    const float* g_weights_coarse; /* [n, num_coarse]            */
+    const float* g_weights_fine;   /* [n, num_coarse + num_fine] */
+} nerfhip_render_cotangents_w;
+int nerfhip_render_bwd_parts_w(nerfhip_plan_t plan_coarse, nerfhip_plan_t plan_fine, const nerfhip_render_cfg* cfg,
+                               const float* rays, int64_t n_rays, const float* packed_coarse, const float* packed_fine,
+                               const nerfhip_render_rand* rnd, uint64_t seed, uint64_t ray_offset,
+                               const nerfhip_render_cotangents_w* g, void* workspace, int64_t workspace_bytes,
+                               float* g_params_coarse, float* g_params_fine, int parts, nerfhip_stream_t stream);
+int nerfhip_render_bwd_rays_w(nerfhip_plan_t plan_coarse, nerfhip_plan_t plan_fine, const nerfhip_render_cfg* cfg,
+                              const float* rays, int64_t n_rays, const float* packed_coarse, const float* packed_fine,
+                              const nerfhip_render_rand* rnd, uint64_t seed, uint64_t ray_offset,
+                              const nerfhip_render_cotangents_w* g, void* workspace, int64_t workspace_bytes,
+                              float* g_params_coarse, float* g_params_fine, int parts, const float* params_coarse,
+                              const float* params_fine, void* tmp, int64_t tmp_bytes, float* g_rays, nerfhip_stream_t stream);
+
+/* ---- ray-weight spread loss (mip-NeRF 360's L_dist, Barron et al. 2022, eq. 15) ------------------------------------------------
+ * ("Distortion" names the lens in this library; this regulariser measures the SPREAD of a ray's weights.)  For one ray of a pass with
+ * s samples, depths z_0 <= ... <= z_{s-1}, and near, far = columns 6, 7 of its packed row:
+ *     inv   = far > near ? 1 / (far - near) : 0
+ *     s_i   = (z_i - near) inv
+ *     e_i   = s_{i+1} for i < s - 1,   e_{s-1} = max(s_{s-1}, 1)          (the last sample owns [z_{s-1}, far])
+ *     m_i   = (s_i + e_i) / 2,         delta_i = e_i - s_i                 (formed in fp64 from the fp32 depths)
+ *     w_i   = alpha_i T_i exactly as the compositing forms it (nerfhip_volume_render_fwd's weights, bit for bit: the same noise
+ *             draws -- noise_std, noise, seed, rng_stream, ray_offset -- and fp64 transmittance scan)
+ *     L     = sum_i sum_j w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 delta_i
+ *     dL/dw_i = 2 [m_i (W_<i - W_>i) - (WM_<i - WM_>i)] + (2/3) w_i delta_i,
+ *             W_<i = sum_{j<i} w_j, WM_<i = sum_{j<i} w_j m_j, likewise _>i   (valid because m ascends; ties are harmless)
+ * The depths are constants (the reference detaches the fine samples; the coarse ones do not depend on parameters): the gradient
+ * reaches the nets through w alone.  A ray with inv = 0 has L = 0 and a zero gradient; NaN propagates.  O(s) per ray: prefix and
+ * suffix sums in fp64, a fixed order of summation (no atomics), each output rounded to fp32 once.
+ * raw dev [n,s,4], z dev [n,s], rays dev [n, ray_stride >= 8]; loss (optional) dev [n]: the unscaled L of each ray; g_weights
+ * (optional) dev [n,s] = scale_ray dL/dw_i, scale_ray = scale * (g_loss ? g_loss[ray] : 1), g_loss dev [n] or NULL -- the cotangent
+ * nerfhip_volume_render_bwd and the _w entry points above take.  At least one output; 1 <= s <= 8192; n == 0 launches nothing. */
+int nerfhip_spread_loss(const float* raw, const float* z, const float* rays, int ray_stride, int64_t n, int s, float noise_std,
+                        const float* noise, uint64_t seed, uint32_t rng_stream, uint64_t ray_offset, float scale,
+                        const float* g_loss, float* loss, float* g_weights, nerfhip_stream_t stream);
 
 /* d(loss)/d(rays) ALONE, for frozen nets (camera localisation against a trained field): nerfhip_render_bwd_rays' contract -- parts,
  * NERFHIP_PART_SHARED_BWD, the first pass that runs overwrites g_rays and the second accumulates, params_* = the flat vectors the

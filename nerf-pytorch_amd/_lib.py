@@ -43,6 +43,11 @@ class RenderCotangents(C.Structure):
                                    "g_depth_fine")]
 
 
+class RenderCotangentsW(C.Structure):
+    """nerfhip_render_cotangents_w: RenderCotangents and the cotangents of the two passes' ray weights."""
+    _fields_ = RenderCotangents._fields_ + [(n, c_f) for n in ("g_weights_coarse", "g_weights_fine")]
+
+
 class OccGrid(C.Structure):
     """nerfhip_occ_grid: a host struct naming the device bits, passed by pointer and read during the call."""
     _fields_ = [("bits", c_f), ("lo", C.c_float * 3), ("hi", C.c_float * 3), ("res", C.c_int * 3), ("outside", C.c_int)]
@@ -137,6 +142,14 @@ _PROTOS = {
     "nerfhip_render_bwd_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RenderCfg), c_f, c_i64, c_f, c_f,
                                            C.POINTER(RenderRand), c_u64, c_u64, C.POINTER(RenderCotangents), c_f, c_i64,
                                            c_f, c_f, C.c_int, c_f, c_f, c_f, c_i64, c_f, c_f]),
+    "nerfhip_render_bwd_parts_w": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RenderCfg), c_f, c_i64, c_f, c_f,
+                                              C.POINTER(RenderRand), c_u64, c_u64, C.POINTER(RenderCotangentsW), c_f, c_i64,
+                                              c_f, c_f, C.c_int, c_f]),
+    "nerfhip_render_bwd_rays_w": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RenderCfg), c_f, c_i64, c_f, c_f,
+                                             C.POINTER(RenderRand), c_u64, c_u64, C.POINTER(RenderCotangentsW), c_f, c_i64,
+                                             c_f, c_f, C.c_int, c_f, c_f, c_f, c_i64, c_f, c_f]),
+    "nerfhip_spread_loss": (C.c_int, [c_f, c_f, c_f, C.c_int, c_i64, C.c_int, C.c_float, c_f, c_u64, c_u32, c_u64, C.c_float,
+                                       c_f, c_f, c_f, c_f]),
     "nerfhip_render_grad_rays_tmp_bytes": (c_i64, [C.c_void_p, C.c_void_p, C.POINTER(RenderCfg), c_i64]),
     "nerfhip_render_grad_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RenderCfg), c_f, c_i64, c_f, c_f,
                                             C.POINTER(RenderRand), c_u64, c_u64, C.POINTER(RenderCotangents), c_f, c_i64,

@@ -96,6 +96,7 @@ struct Pass {
     NetSpace w;
     // the backward's: the net's cotangents, its gradient buffer, its flat parameters (the ray gradient reads them)
     const float *g_rgb, *g_depth, *g_acc;
+    const float* g_weights;  // [n, in.S] cotangent of the ray weights, or NULL (the _w entry points: backward_pass alone reads it)
     float* g_params;
     const float* params;
 };
@@ -156,7 +157,7 @@ int backward_pass(const Call& c, const Pass& q, void* tmp, int64_t tmp_bytes, fl
     float* scratch = (float*)(c.ws + q.w.scratch);
     float* g_norm = g_rays ? (float*)(c.ws + q.w.gnorm) : nullptr;
     int rc = nh_volume_render_bwd((const float*)(c.ws + q.w.raw), q.in.z, c.rays + 3, c.cfg->ray_stride, c.n, q.in.S, c.cfg->noise_std,
-                                  q.noise, c.seed, q.rng_stream, c.ray_offset, c.cfg->white_background, q.g_rgb, q.g_depth, q.g_acc, nullptr,
+                                  q.noise, c.seed, q.rng_stream, c.ray_offset, c.cfg->white_background, q.g_rgb, q.g_depth, q.g_acc, q.g_weights,
                                   g_raw, g_norm, c.stream);
     if (rc) return rc;
     rc = nh_mlp_backward(p, q.packed, &q.in, g_raw, M, (float*)(c.ws + q.w.stash), scratch, q.w.scratch_bytes, q.g_params,
@@ -215,13 +216,14 @@ extern "C" int nerfhip_render_workspace_region(nerfhip_plan_t plan_coarse, nerfh
     NH_REQUIRE(name && offset && bytes && n_rays >= 0, "render_workspace_region: bad arguments");
     const Workspace w = layout(plan_coarse, plan_fine, cfg, n_rays, training);
     // (training layouts: each net's backward scratch -- nerfhip_plan_bwd_stats_offset points into it)
-    static const char* const names[2][4] = {{"z_coarse", "raw_coarse", "weights_coarse", "bwd_scratch_coarse"},
-                                            {"z_fine", "raw_fine", nullptr, "bwd_scratch_fine"}};
+    // (... and the d(loss)/d(raw) rows its compositing backward writes)
+    static const char* const names[2][5] = {{"z_coarse", "raw_coarse", "weights_coarse", "bwd_scratch_coarse", "bwd_g_raw_coarse"},
+                                            {"z_fine", "raw_fine", nullptr, "bwd_scratch_fine", "bwd_g_raw_fine"}};
     for (int fine = 0; fine < 2; ++fine) {
         const NetSpace& s = fine ? w.f : w.c;
         const int64_t M = n_rays * (cfg->num_coarse + (fine ? cfg->num_fine : 0));
-        const int64_t off[4] = {s.z, s.raw, s.weights, s.scratch}, size[4] = {M * 4, M * 16, M * 4, s.scratch_bytes};
-        for (int i = 0; i < 4; ++i)
+        const int64_t off[5] = {s.z, s.raw, s.weights, s.scratch, s.g_raw}, size[5] = {M * 4, M * 16, M * 4, s.scratch_bytes, M * 16};
+        for (int i = 0; i < 5; ++i)
             if (names[fine][i] && strcmp(name, names[fine][i]) == 0) {
                 NH_REQUIRE(!fine || cfg->num_fine > 0, "render_workspace_region: %s needs num_fine > 0", name);
                 NH_REQUIRE(training || strncmp(name, "bwd_", 4) != 0, "render_workspace_region: %s exists in a training layout only", name);
@@ -389,12 +391,13 @@ extern "C" int64_t nerfhip_render_bwd_rays_tmp_bytes(nerfhip_plan_t pc, nerfhip_
     return b;
 }
 
-extern "C" int nerfhip_render_bwd_rays(nerfhip_plan_t pc, nerfhip_plan_t pf, const nerfhip_render_cfg* cfg, const float* rays,
-                                       int64_t n, const float* packed_c, const float* packed_f, const nerfhip_render_rand* rnd,
-                                       uint64_t seed, uint64_t ray_offset, const nerfhip_render_cotangents* g, void* workspace,
-                                       int64_t workspace_bytes, float* g_params_c, float* g_params_f, int parts,
-                                       const float* params_c, const float* params_f, void* tmp, int64_t tmp_bytes,
-                                       float* g_rays, nerfhip_stream_t stream) {
+// nerfhip_render_bwd_rays / _parts and their _w forms: gw_c / gw_f are the cotangents of the two passes' ray weights (NULL = none; a
+// weight cotangent alone is enough for a pass to run)
+static int render_bwd(nerfhip_plan_t pc, nerfhip_plan_t pf, const nerfhip_render_cfg* cfg, const float* rays, int64_t n,
+                      const float* packed_c, const float* packed_f, const nerfhip_render_rand* rnd, uint64_t seed, uint64_t ray_offset,
+                      const nerfhip_render_cotangents* g, const float* gw_c, const float* gw_f, void* workspace,
+                      int64_t workspace_bytes, float* g_params_c, float* g_params_f, int parts, const float* params_c,
+                      const float* params_f, void* tmp, int64_t tmp_bytes, float* g_rays, nerfhip_stream_t stream) {
     int rc = check_cfg(pc, pf, cfg);
     if (rc) return rc;
     NH_REQUIRE(rays && packed_c && g && workspace && n > 0, "render_bwd: bad arguments");
@@ -407,20 +410,22 @@ extern "C" int nerfhip_render_bwd_rays(nerfhip_plan_t pc, nerfhip_plan_t pf, con
     const Call c = {cfg, rays, n, seed, ray_offset, (char*)workspace, stream};
     int wrote_rays = 0;  // the first pass that runs overwrites g_rays, the second accumulates
     if (cfg->num_fine > 0 && (parts & NERFHIP_PART_FINE)) {
-        NH_REQUIRE(packed_f && g_params_f && (g->g_rgb_fine || g->g_acc_fine || g->g_depth_fine),
+        NH_REQUIRE(packed_f && g_params_f && (g->g_rgb_fine || g->g_acc_fine || g->g_depth_fine || gw_f),
                    "render_bwd: fine arguments missing");
         Pass fine = net_pass(c, true, pf, packed_f, rnd, w);
         fine.g_rgb = g->g_rgb_fine, fine.g_depth = g->g_depth_fine, fine.g_acc = g->g_acc_fine;
+        fine.g_weights = gw_f;
         fine.g_params = g_params_f, fine.params = params_f;
         rc = backward_pass(c, fine, tmp, tmp_bytes, g_rays, wrote_rays);
         if (rc) return rc;
         wrote_rays = g_rays != nullptr;
     }
     if (parts & NERFHIP_PART_COARSE) {
-        NH_REQUIRE(g_params_c && (g->g_rgb_coarse || g->g_acc_coarse || g->g_depth_coarse),
+        NH_REQUIRE(g_params_c && (g->g_rgb_coarse || g->g_acc_coarse || g->g_depth_coarse || gw_c),
                    "render_bwd: coarse arguments missing");
         Pass coarse = net_pass(c, false, pc, packed_c, rnd, w);
         coarse.g_rgb = g->g_rgb_coarse, coarse.g_depth = g->g_depth_coarse, coarse.g_acc = g->g_acc_coarse;
+        coarse.g_weights = gw_c;
         coarse.g_params = g_params_c, coarse.params = params_c;
         rc = backward_pass(c, coarse, tmp, tmp_bytes, g_rays, wrote_rays);
         if (rc) return rc;
@@ -428,13 +433,46 @@ extern "C" int nerfhip_render_bwd_rays(nerfhip_plan_t pc, nerfhip_plan_t pf, con
     return NERFHIP_OK;
 }
 
+extern "C" int nerfhip_render_bwd_rays(nerfhip_plan_t pc, nerfhip_plan_t pf, const nerfhip_render_cfg* cfg, const float* rays,
+                                       int64_t n, const float* packed_c, const float* packed_f, const nerfhip_render_rand* rnd,
+                                       uint64_t seed, uint64_t ray_offset, const nerfhip_render_cotangents* g, void* workspace,
+                                       int64_t workspace_bytes, float* g_params_c, float* g_params_f, int parts,
+                                       const float* params_c, const float* params_f, void* tmp, int64_t tmp_bytes,
+                                       float* g_rays, nerfhip_stream_t stream) {
+    return render_bwd(pc, pf, cfg, rays, n, packed_c, packed_f, rnd, seed, ray_offset, g, nullptr, nullptr, workspace, workspace_bytes,
+                      g_params_c, g_params_f, parts, params_c, params_f, tmp, tmp_bytes, g_rays, stream);
+}
+
 extern "C" int nerfhip_render_bwd_parts(nerfhip_plan_t pc, nerfhip_plan_t pf, const nerfhip_render_cfg* cfg,
                                         const float* rays, int64_t n, const float* packed_c, const float* packed_f,
                                         const nerfhip_render_rand* rnd, uint64_t seed, uint64_t ray_offset,
                                         const nerfhip_render_cotangents* g, void* workspace, int64_t workspace_bytes,
                                         float* g_params_c, float* g_params_f, int parts, nerfhip_stream_t stream) {
-    return nerfhip_render_bwd_rays(pc, pf, cfg, rays, n, packed_c, packed_f, rnd, seed, ray_offset, g, workspace, workspace_bytes,
-                                   g_params_c, g_params_f, parts, nullptr, nullptr, nullptr, 0, nullptr, stream);
+    return render_bwd(pc, pf, cfg, rays, n, packed_c, packed_f, rnd, seed, ray_offset, g, nullptr, nullptr, workspace, workspace_bytes,
+                      g_params_c, g_params_f, parts, nullptr, nullptr, nullptr, 0, nullptr, stream);
+}
+
+// the _w forms: the same routine with the weight cotangents of the extended struct (its first six members are
+// nerfhip_render_cotangents, in order)
+extern "C" int nerfhip_render_bwd_rays_w(nerfhip_plan_t pc, nerfhip_plan_t pf, const nerfhip_render_cfg* cfg, const float* rays,
+                                         int64_t n, const float* packed_c, const float* packed_f, const nerfhip_render_rand* rnd,
+                                         uint64_t seed, uint64_t ray_offset, const nerfhip_render_cotangents_w* g, void* workspace,
+                                         int64_t workspace_bytes, float* g_params_c, float* g_params_f, int parts,
+                                         const float* params_c, const float* params_f, void* tmp, int64_t tmp_bytes,
+                                         float* g_rays, nerfhip_stream_t stream) {
+    NH_REQUIRE(g, "render_bwd: bad arguments");
+    const nerfhip_render_cotangents g6 = {g->g_rgb_coarse, g->g_acc_coarse, g->g_depth_coarse, g->g_rgb_fine, g->g_acc_fine, g->g_depth_fine};
+    return render_bwd(pc, pf, cfg, rays, n, packed_c, packed_f, rnd, seed, ray_offset, &g6, g->g_weights_coarse, g->g_weights_fine,
+                      workspace, workspace_bytes, g_params_c, g_params_f, parts, params_c, params_f, tmp, tmp_bytes, g_rays, stream);
+}
+
+extern "C" int nerfhip_render_bwd_parts_w(nerfhip_plan_t pc, nerfhip_plan_t pf, const nerfhip_render_cfg* cfg,
+                                          const float* rays, int64_t n, const float* packed_c, const float* packed_f,
+                                          const nerfhip_render_rand* rnd, uint64_t seed, uint64_t ray_offset,
+                                          const nerfhip_render_cotangents_w* g, void* workspace, int64_t workspace_bytes,
+                                          float* g_params_c, float* g_params_f, int parts, nerfhip_stream_t stream) {
+    return nerfhip_render_bwd_rays_w(pc, pf, cfg, rays, n, packed_c, packed_f, rnd, seed, ray_offset, g, workspace, workspace_bytes,
+                                     g_params_c, g_params_f, parts, nullptr, nullptr, nullptr, 0, nullptr, stream);
 }
 
 extern "C" int nerfhip_render_bwd(nerfhip_plan_t pc, nerfhip_plan_t pf, const nerfhip_render_cfg* cfg, const float* rays,

@@ -20,6 +20,9 @@ inside the Adam kernel.  Every rank applies the identical update, so no paramete
 Occupancy grid (`occupancy=`, one rank): from a warm-up on both forwards are nerfhip_render_fwd_occ_train through
 the grid (main stream, one list area), the nets' backwards run in a mode that keeps no stash, and every few optimizer steps the
 grid's density is updated from the images just packed.
+
+Ray-weight spread loss (mip-NeRF 360's L_dist; `spread=`): a net with a weight lambda > 0 gets one nerfhip_spread_loss
+launch between its loss and its backward, on the same stream, and the _w form of that backward; `spread_losses` reads the means.
 """
 import ctypes as C
 import math
@@ -38,7 +41,7 @@ class TrainEngine:
     def __init__(self, model_coarse, model_fine, num_coarse, num_fine, perturb=True, lindisp=False, white_background=False,
                  noise_std=0.0, lr=5e-3, betas=(0.9, 0.999), eps=1e-8, seed=0, process_group=None, world_size=None,
                  rank=None, overlap=None, always_reduce=False, backward=None, window=None, total_steps=None, occupancy=None,
-                 occupancy_warmup=256, occupancy_every=16):
+                 occupancy_warmup=256, occupancy_every=16, spread=None):
         self.lib = L.get_lib()
         self.mc, self.mf = model_coarse, model_fine if num_fine > 0 else None
         self.dev = model_coarse.flat_params.device
@@ -115,6 +118,20 @@ class TrainEngine:
             mode = BM.parse(backward)   # (ValueError for anything that is not a mode)
             for _, m in self._nets:
                 m.set_backward_compaction(mode)
+        # ray-weight spread loss (mip-NeRF 360's L_dist): None / 0 -- the step as it always was, launch for launch; a
+        # float or (lambda_coarse, lambda_fine) -- a net with lambda > 0 adds lambda * mean_ray(L) to its loss: after its forward one
+        # nerfhip_spread_loss on the stream its backward runs on, over the raw rows and depths the forward left in the workspace, then
+        # the _w form of its backward with the engine-owned weight cotangent
+        if spread is None:
+            spread = (0.0, 0.0)
+        elif isinstance(spread, (int, float)):
+            spread = (float(spread), float(spread))
+        else:
+            spread = tuple(float(v) for v in spread)
+        if len(spread) != 2 or not all(v >= 0.0 and math.isfinite(v) for v in spread):
+            raise ValueError("TrainEngine: spread must be None, a finite weight >= 0 or a pair (coarse, fine) of them (got %r)" % (spread,))
+        self.spread = (spread[0], spread[1] if self.mf is not None else 0.0)
+        self._spread_bufs = None   # per net with lambda > 0: (weight cotangent [n, S], per-ray loss [n]), sized in _prepare
         self._stats = BM.StatsReader(("coarse", "fine"))
         self._zero_frac = self._stats.frac   # last known fraction of all-zero d(loss)/d(raw) rows per net (updated in place)
         # steps run dense / compacted / recomputed / fused / fused over the list / fused over the stash, per net ("auto")
@@ -179,6 +196,16 @@ class TrainEngine:
             self._occ_tmp = torch.zeros(self._occ_tb // 4 + 64, dtype=torch.int32, device=self.dev)
         self._bufs = dict(rgb_c=mk(n, 3), rgb_f=mk(n, 3), g_c=mk(n, 3), g_f=mk(n, 3), disp_c=mk(n), acc_c=mk(n),
                           disp_f=mk(n), acc_f=mk(n))
+        if any(self.spread):   # (the regions the spread kernel reads, and what it writes)
+            self._spread_bufs = {}
+            for fine, tag, S in ((0, "coarse", self.cfg.num_coarse), (1, "fine", self.cfg.num_coarse + self.cfg.num_fine)):
+                if self.spread[fine] > 0.0:
+                    offs = []
+                    for name in ("raw_", "z_"):
+                        off, nb = C.c_int64(), C.c_int64()
+                        lib.render_workspace_region(self.mc._plan, plan_f, C.byref(self.cfg), n, 1, (name + tag).encode(), C.byref(off), C.byref(nb))
+                        offs.append(off.value)
+                    self._spread_bufs[fine] = (mk(n, S), torch.zeros(n, dtype=torch.float32, device=self.dev), offs[0], offs[1], S)
 
     def workspace_bytes(self):
         return 0 if self._ws is None else self._wsb
@@ -257,6 +284,9 @@ class TrainEngine:
         The exposure sits behind the render: it asks for no ray gradient.  With frozen=True and no ray_grad the step is the
         test-time fit: the two forwards, the two losses and the table gradient, no render backward.  One rank only."""
         self._check_inputs(rays, target)
+        if frozen and any(self.spread):
+            raise ValueError("TrainEngine: a frozen step (localize_*, the exposure fit) with spread > 0 makes no sense: the spread loss "
+                             "regularises the nets, and a frozen step updates none")
         if self.occupancy is not None and (ray_grad is not None or frozen):
             raise NotImplementedError("TrainEngine: a step with a ray gradient (pose, camera, intrinsics or distortion gradients) or a "
                                       "frozen step (localize_*) is not implemented with occupancy=...: the ray gradient of the culled "
@@ -327,7 +357,19 @@ class TrainEngine:
 
         def net_pass(part, rgb, g_rgb, cot, loss, grad, model, tmp, g_rays, stream):
             """One net's loss, then its backward in the step's form, then its window gradients (behind its backward, ahead of its
-            all-reduce), on `stream`."""
+            all-reduce), on `stream`.  With a spread weight: the spread kernel between the loss and the backward, and the backward's
+            _w form."""
+            fine = int(part == L.PART_FINE)
+            w = "_w" if self.spread[fine] > 0.0 else ""
+            if w:
+                gw, sl, raw_off, z_off, S = self._spread_bufs[fine]
+                noise = None if draws is None or draws[1 + 2 * fine] is None else draws[1 + 2 * fine].data_ptr()
+                # (scale: lambda / n under the loss launch's grad_scale convention -- the total is the mse terms + lambda * mean_ray(L))
+                lib.spread_loss(self._ws.data_ptr() + raw_off, self._ws.data_ptr() + z_off, rays.data_ptr(), self.stride, n, S,
+                                self.cfg.noise_std, noise, seed, 1 + 2 * fine, ray_offset, self.spread[fine] * gscale / n, None,
+                                sl.data_ptr(), gw.data_ptr(), stream)
+                six = [getattr(cot, k) for k, _ in L.RenderCotangents._fields_]
+                cot = L.RenderCotangentsW(*six, None if fine else gw.data_ptr(), gw.data_ptr() if fine else None)
             if exposure is None:
                 lib.mse_loss_fwd_bwd(rgb.data_ptr(), None, target.data_ptr(), tstride, n, gscale, g_rgb.data_ptr(), None, loss.data_ptr(), stream)
             else:
@@ -336,13 +378,13 @@ class TrainEngine:
             if ray_grad is None and frozen:   # (the fit of the exposure table alone: no render backward)
                 return
             if ray_grad is None:
-                lib.render_bwd_parts(*bwd_head, C.byref(cot), *bwd_tail, part, stream)
+                getattr(lib, "render_bwd_parts" + w)(*bwd_head, C.byref(cot), *bwd_tail, part, stream)
             else:
                 rays_tail = (part, pc_flat, pf_flat, tmp.data_ptr(), tmpb, g_rays.data_ptr(), stream)
                 if frozen:   # (no parameter gradient: the workspace alone, no gradient slices)
                     lib.render_grad_rays(*bwd_head, C.byref(cot), *bwd_tail[:2], *rays_tail)
                 else:
-                    lib.render_bwd_rays(*bwd_head, C.byref(cot), *bwd_tail, *rays_tail)
+                    getattr(lib, "render_bwd_rays" + w)(*bwd_head, C.byref(cot), *bwd_tail, *rays_tail)
             if not frozen:
                 model._window_grads(grad, model._window_w, stream)
 
@@ -423,6 +465,14 @@ class TrainEngine:
         """{kept_coarse, total_coarse, kept_fine, total_fine} of the last culled step's forwards: an int32 device view of the list
         area's first four words (no copy, no sync; zeros before the first culled step); None without a grid."""
         return None if self._occ_tmp is None else self._occ_tmp[:4]
+
+    @property
+    def spread_losses(self):
+        """(coarse, fine): the mean over the last step's rays of each net's unscaled spread loss L, as device scalars formed on demand
+        from the per-ray buffers the spread kernel wrote (no host synchronisation); None for a net without a spread weight or before
+        the first step."""
+        b = self._spread_bufs or {}
+        return tuple(b[fine][1].mean() if fine in b else None for fine in (0, 1))
 
     def _stats_words(self, name):
         """The two statistics words of net `name` in the workspace of the last step."""

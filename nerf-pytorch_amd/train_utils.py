@@ -78,12 +78,17 @@ class _FusedRender(torch.autograd.Function):
 
     The workspace (activation stash, ~4.8 MB per ray for the 8x256 nets) is allocated per call from torch's caching
     allocator and owned by the autograd node: several nodes may be alive at once (run_one_iter_of_nerf renders a batch
-    in ray chunks and backpropagates afterwards), so it must not be shared between calls."""
+    in ray chunks and backpropagates afterwards), so it must not be shared between calls.
+
+    With the `spread` flag (the seventh entry of cfg_tuple) the node has two more differentiable outputs: the per-ray spread loss of
+    each pass's ray weights (nerfhip_spread_loss; None for the fine pass without a fine net).  Its forward runs the kernel for the
+    losses alone; its backward runs it again with the incoming per-ray cotangents as g_loss and hands the weight cotangents to the _w
+    form of the render backward.  The flag is pinned at the forward, as the backward mode is."""
 
     @staticmethod
     def forward(ctx, rays, model_c, model_f, cfg_tuple, rand, training, rays_grad, *params):
         lib = L.get_lib()
-        nc, nf, perturb, lindisp, white, noise_std = cfg_tuple
+        nc, nf, perturb, lindisp, white, noise_std, spread = cfg_tuple
         n, stride = rays.shape
         dev = rays.device
         cfg = L.RenderCfg(nc, nf, int(bool(perturb)), int(bool(lindisp)), int(bool(white)), float(noise_std), stride)
@@ -131,10 +136,37 @@ class _FusedRender(torch.autograd.Function):
         ctx.frozen = bool(training and rays_grad and model_c.frozen and (nf == 0 or model_f.frozen))
         ctx.n_params = len(params)
         ctx.mark_non_differentiable(bufs["disp_coarse"], bufs["disp_fine"])
-        return tuple(bufs[k] for k in names)
+        ctx.spread = bool(spread)
+        if not spread:
+            return tuple(bufs[k] for k in names)
+        if ctx.frozen:
+            raise ValueError("spread=True on frozen nets (set_frozen) makes no sense: the spread loss regularises the nets")
+        sp = [torch.empty(n, dtype=torch.float32, device=dev) for _ in range(2 if nf > 0 else 1)]
+        with L.launch_on(rays, ws, *sp) as st:
+            for fine, out_sp in enumerate(sp):
+                _FusedRender._spread(lib, ctx.keep, fine, None, out_sp, None, st)
+        return tuple(bufs[k] for k in names) + (sp[0], sp[1] if nf > 0 else None)
 
     @staticmethod
-    def backward(ctx, g_rgb_c, g_disp_c, g_acc_c, g_depth_c, g_rgb_f, g_disp_f, g_acc_f, g_depth_f):
+    def _spread(lib, keep, fine, g_loss, loss, g_weights, st):
+        """nerfhip_spread_loss of one pass over the raw rows and depths the node's forward left in its workspace."""
+        rays, model_c, model_f, cfg, rand, ws, wsb, _, _, training, _ = keep
+        n = rays.shape[0]
+        plan_c = model_c._plan if training else model_c._inference_plan()
+        plan_f = (model_f._plan if training else model_f._inference_plan()) if cfg.num_fine > 0 else None
+        offs = []
+        for name in (b"raw_fine", b"z_fine") if fine else (b"raw_coarse", b"z_coarse"):
+            off, nb = C.c_int64(), C.c_int64()
+            lib.render_workspace_region(plan_c, plan_f, C.byref(cfg), n, 2 if training else 0, name, C.byref(off), C.byref(nb))
+            offs.append(ws.data_ptr() + off.value)
+        noise = rand[3 if fine else 1]
+        lib.spread_loss(offs[0], offs[1], rays.data_ptr(), rays.shape[1], n, cfg.num_coarse + (cfg.num_fine if fine else 0), cfg.noise_std,
+                        None if noise is None else noise.data_ptr(), 0, 3 if fine else 1, 0, 1.0,
+                        None if g_loss is None else g_loss.data_ptr(), None if loss is None else loss.data_ptr(),
+                        None if g_weights is None else g_weights.data_ptr(), st)
+
+    @staticmethod
+    def backward(ctx, g_rgb_c, g_disp_c, g_acc_c, g_depth_c, g_rgb_f, g_disp_f, g_acc_f, g_depth_f, *g_spread):
         lib = L.get_lib()
         rays, model_c, model_f, cfg, rand, ws, wsb, packed_c, packed_f, training, flats = ctx.keep
         if not training:
@@ -145,9 +177,10 @@ class _FusedRender(torch.autograd.Function):
         keep = [None if g is None else g.contiguous().float()
                 for g in (g_rgb_c, g_acc_c, g_depth_c, g_rgb_f, g_acc_f, g_depth_f)]
         parts = 0
-        if any(k is not None for k in keep[:3]):
+        g_sp = [None if g is None else g.contiguous().float() for g in g_spread] + [None, None]
+        if any(k is not None for k in keep[:3]) or g_sp[0] is not None:
             parts |= L.PART_COARSE
-        if nf > 0 and any(k is not None for k in keep[3:]):
+        if nf > 0 and (any(k is not None for k in keep[3:]) or g_sp[1] is not None):
             parts |= L.PART_FINE
         if ctx.frozen:
             return (_FusedRender._frozen_backward(ctx, keep, parts),) + (None,) * (6 + ctx.n_params)
@@ -156,6 +189,14 @@ class _FusedRender(torch.autograd.Function):
         g_rays = torch.zeros_like(rays) if flats is not None else None
         if parts:
             cot = L.RenderCotangents(*[None if k is None else k.data_ptr() for k in keep])
+            bwd_rays = lib.render_bwd_rays
+            gw = [None, None]
+            if ctx.spread and (g_sp[0] is not None or g_sp[1] is not None):   # (the weight cotangents of the passes whose spread a loss touched)
+                for fine in (0, 1):
+                    if g_sp[fine] is not None:
+                        gw[fine] = torch.empty((n, cfg.num_coarse + (nf if fine else 0)), dtype=torch.float32, device=dev)
+                cot = L.RenderCotangentsW(*[None if k is None else k.data_ptr() for k in keep], *[None if g is None else g.data_ptr() for g in gw])
+                bwd_rays = lib.render_bwd_rays_w
             rr = L.RenderRand(*[None if r is None else r.data_ptr() for r in rand])
             plan_f = model_f._plan if nf > 0 else None
             tmp, tmpb = None, 0
@@ -175,15 +216,18 @@ class _FusedRender(torch.autograd.Function):
                     lib.plan_set_bwd_compaction(plan, was)
             try:
                 with L.launch_on(rays, ws, gpc, gpf, tmp, *[k for k in keep if k is not None]) as st:
+                    for fine in (0, 1):
+                        if gw[fine] is not None:
+                            _FusedRender._spread(lib, ctx.keep, fine, g_sp[fine], None, gw[fine], st)
                     for part in passes:
-                        lib.render_bwd_rays(model_c._plan, plan_f, C.byref(cfg), rays.data_ptr(), n,
-                                            packed_c.data_ptr(), packed_f.data_ptr() if nf > 0 else None, C.byref(rr), 0, 0,
-                                            C.byref(cot), ws.data_ptr(), wsb, gpc.data_ptr(),
-                                            gpf.data_ptr() if gpf is not None else None, part | L.PART_SHARED_BWD,
-                                            flats[0].data_ptr() if flats is not None else None,
-                                            flats[1].data_ptr() if (flats is not None and flats[1] is not None) else None,
-                                            tmp.data_ptr() if tmp is not None else None, tmpb,
-                                            g_rays.data_ptr() if g_rays is not None else None, st)
+                        bwd_rays(model_c._plan, plan_f, C.byref(cfg), rays.data_ptr(), n,
+                                 packed_c.data_ptr(), packed_f.data_ptr() if nf > 0 else None, C.byref(rr), 0, 0,
+                                 C.byref(cot), ws.data_ptr(), wsb, gpc.data_ptr(),
+                                 gpf.data_ptr() if gpf is not None else None, part | L.PART_SHARED_BWD,
+                                 flats[0].data_ptr() if flats is not None else None,
+                                 flats[1].data_ptr() if (flats is not None and flats[1] is not None) else None,
+                                 tmp.data_ptr() if tmp is not None else None, tmpb,
+                                 g_rays.data_ptr() if g_rays is not None else None, st)
                         # (the words in the shared buffers: the coarse net's behind a pass that ran it -- it runs last --, the fine net's
                         # only between the two passes)
                         model, net, mode = (model_c, "coarse", ctx.bwd_modes[0]) if part & L.PART_COARSE else (model_f, "fine", ctx.bwd_modes[1])
@@ -232,7 +276,7 @@ class _FusedRender(torch.autograd.Function):
         return g_rays
 
 
-def _predict_fused(ray_batch, model_coarse, model_fine, opts, occupancy=None):
+def _predict_fused(ray_batch, model_coarse, model_fine, opts, occupancy=None, spread=False):
     rays_grad = bool(ray_batch.requires_grad and torch.is_grad_enabled())
     rays = ray_batch.contiguous().float() if rays_grad else ray_batch.detach().contiguous().float()
     n = rays.shape[0]
@@ -260,9 +304,10 @@ def _predict_fused(ray_batch, model_coarse, model_fine, opts, occupancy=None):
         outs = render_fwd_occ(rays, model_coarse, model_fine if nf > 0 else None, cfg_tuple, (t_rand, noise_c, u, noise_f), occupancy)
         rgb_c, disp_c, acc_c, _, rgb_f, disp_f, acc_f, _ = outs
         return (rgb_c, disp_c, acc_c, rgb_f, disp_f, acc_f) if nf > 0 else (rgb_c, disp_c, acc_c, None, None, None)
-    outs = _FusedRender.apply(rays, model_coarse, model_fine if nf > 0 else None, cfg_tuple,
+    outs = _FusedRender.apply(rays, model_coarse, model_fine if nf > 0 else None, cfg_tuple + (bool(spread),),
                               (t_rand, noise_c, u, noise_f), training, rays_grad, *pc, *pf)
-    rgb_c, disp_c, acc_c, depth_c, rgb_f, disp_f, acc_f, depth_f = outs
+    rgb_c, disp_c, acc_c, depth_c, rgb_f, disp_f, acc_f, depth_f = outs[:8]
+    tail = tuple(outs[8:])   # (spread=True: the two per-ray spread losses)
     if rgb_c.requires_grad:
         # disparity re-derived from the differentiable depth / accumulation maps with the reference's own torch ops
         # (volume_rendering_utils.py:46-48: same values as the kernel's, and autograd covers a loss on it)
@@ -270,8 +315,8 @@ def _predict_fused(ray_batch, model_coarse, model_fine, opts, occupancy=None):
         if nf > 0:
             disp_f = 1.0 / torch.max(1e-10 * torch.ones_like(depth_f), depth_f / acc_f)
     if nf > 0:
-        return rgb_c, disp_c, acc_c, rgb_f, disp_f, acc_f
-    return rgb_c, disp_c, acc_c, None, None, None
+        return (rgb_c, disp_c, acc_c, rgb_f, disp_f, acc_f) + tail
+    return (rgb_c, disp_c, acc_c, None, None, None) + tail
 
 
 _OCC_TRAIN_MSG = ("an occupancy grid culls the inference render only: pass occupancy= with mode=\"validation\" under torch.no_grad() "
@@ -286,20 +331,27 @@ def _predict_culled(ray_batch, model_coarse, model_fine, opts, encode_position_f
 
 
 def predict_and_render_radiance(ray_batch, model_coarse, model_fine, options, mode="train", encode_position_fn=None,
-                                encode_direction_fn=None, occupancy=None):
+                                encode_direction_fn=None, occupancy=None, spread=False):
     """nerf/train_utils.py:28-127.  Returns (rgb_coarse, disp_coarse, acc_coarse, rgb_fine, disp_fine, acc_fine).
+    spread: True (train mode on the fused path only; anything else raises ValueError) -- the tuple gains two trailing tensors, the
+    per-ray spread loss of each pass's ray weights (mip-NeRF 360's L_dist; include/nerfhip.h nerfhip_spread_loss): spread_coarse (n) and
+    spread_fine (n; None without a fine net), both differentiable w.r.t. the nets.
     occupancy: None, or an occupancy.OccupancyGrid -- with mode="validation" and no gradient wanted, the samples in its empty cells
     skip the MLPs (nerfhip_render_fwd_occ) and the chunk's counts are added to the grid's view_counts; in train mode it raises
     NotImplementedError."""
     if not ray_batch.is_cuda:
         raise RuntimeError("predict_and_render_radiance needs CUDA (HIP) tensors: nerf_pytorch_amd has no CPU path")
     opts = getattr(options.nerf, mode)
+    if spread and (mode != "train" or occupancy is not None
+                   or not _fusable(model_coarse, model_fine, encode_position_fn, encode_direction_fn, opts.num_fine)):
+        raise ValueError("spread=True needs mode=\"train\" on the fused render (FlexibleNeRFModel nets and their own embedding functions, "
+                         "no occupancy grid)")
     if occupancy is not None:
         if mode != "validation":
             raise NotImplementedError(_OCC_TRAIN_MSG)
         return _predict_culled(ray_batch, model_coarse, model_fine, opts, encode_position_fn, encode_direction_fn, occupancy)
     if _fusable(model_coarse, model_fine, encode_position_fn, encode_direction_fn, opts.num_fine):
-        return _predict_fused(ray_batch, model_coarse, model_fine, opts)
+        return _predict_fused(ray_batch, model_coarse, model_fine, opts, spread=spread)
 
     # generic composition (arbitrary networks / encoders), mirroring the reference step by step
     lib = L.get_lib()
@@ -742,11 +794,14 @@ def select_cached_training_rays(cache_dict, num_random_rays, options, select_ind
 
 
 def run_one_iter_of_nerf(height, width, focal_length, model_coarse, model_fine, ray_origins, ray_directions, options,
-                         mode="train", encode_position_fn=None, encode_direction_fn=None, occupancy=None):
+                         mode="train", encode_position_fn=None, encode_direction_fn=None, occupancy=None, spread=False):
     """nerf/train_utils.py:130-202.  occupancy: see predict_and_render_radiance (mode="validation" only); the grid's view_counts
-    are zeroed first, so that after the call they are the sums over every ray chunk of this call."""
+    are zeroed first, so that after the call they are the sums over every ray chunk of this call.
+    spread: see predict_and_render_radiance (mode="train" only): two trailing per-ray tensors, spread_coarse and spread_fine."""
     if not ray_directions.is_cuda:
         raise RuntimeError("run_one_iter_of_nerf needs CUDA (HIP) tensors: nerf_pytorch_amd has no CPU path")
+    if spread and mode != "train":
+        raise ValueError("spread=True needs mode=\"train\"")
     restore_shapes = [ray_directions.shape, ray_directions.shape[:-1], ray_directions.shape[:-1]]
     if model_fine:
         restore_shapes += restore_shapes
@@ -762,7 +817,7 @@ def run_one_iter_of_nerf(height, width, focal_length, model_coarse, model_fine, 
     else:
         pred = [predict_and_render_radiance(batch, model_coarse, model_fine, options,
                                             encode_position_fn=encode_position_fn,
-                                            encode_direction_fn=encode_direction_fn) for batch in batches]
+                                            encode_direction_fn=encode_direction_fn, **({"spread": True} if spread else {})) for batch in batches]
     synthesized_images = list(zip(*pred))
     synthesized_images = [torch.cat(image, dim=0) if image[0] is not None else None for image in synthesized_images]
     if mode == "validation":
