@@ -2,8 +2,6 @@
 policy that picks among them from the fraction of all-zero d(loss)/d(raw) rows, and the read-back of the two statistics words
 {kept, total} a backward over a sample list leaves in its scratch.  What FlexibleNeRFModel.set_backward_compaction,
 TrainEngine(backward=...) and the autograd node of the fused render (train_utils._FusedRender) share."""
-import ctypes as C
-
 import torch
 
 NAMES = ("dense", "compact", "recompute", "fused", "fused_compact", "fused_stash")   # (a mode's code is its index)
@@ -54,13 +52,10 @@ def fold(prev, kept, total):
     return 1.0 - kept / float(total) if (0 <= kept <= total and total > 0) else prev
 
 
-def stats_words(lib, plan_c, plan_f, cfg, n, layout, net, ws):
-    """The int32 view of {kept, total} of net "coarse" / "fine" in `ws`, the workspace of a render of n rays (RenderCfg cfg) in
-    workspace layout `layout` (1: TrainEngine, 2: the autograd node)."""
-    plan, samples = (plan_c, cfg.num_coarse) if net == "coarse" else (plan_f, cfg.num_coarse + cfg.num_fine)
-    off, nb = C.c_int64(), C.c_int64()
-    lib.render_workspace_region(plan_c, plan_f, C.byref(cfg), n, layout, ("bwd_scratch_" + net).encode(), C.byref(off), C.byref(nb))
-    so = (off.value + lib.plan_bwd_stats_offset(plan, n * samples)) // 4
+def stats_words(call, net, ws):
+    """The int32 view of {kept, total} of net "coarse" / "fine" in `ws`, the workspace tensor of the render `call` (a
+    render_call.RenderCall in a training layout)."""
+    so = call.stats_offset(net) // 4
     return ws.view(torch.int32)[so:so + 2]
 
 

@@ -24,7 +24,6 @@ grid's density is updated from the images just packed.
 Ray-weight spread loss (mip-NeRF 360's L_dist; `spread=`): a net with a weight lambda > 0 gets one nerfhip_spread_loss
 launch between its loss and its backward, on the same stream, and the _w form of that backward; `spread_losses` reads the means.
 """
-import ctypes as C
 import math
 
 import torch
@@ -34,6 +33,7 @@ from . import backward_mode as BM
 from . import train_utils as TU
 from .cameras import Distortion, Exposure, Intrinsics, check_device_vector
 from .nerf_helpers import linspace01
+from .render_call import RenderCall
 from .parallel import allreduce_gradients, shard_bounds
 
 
@@ -86,6 +86,7 @@ class TrainEngine:
         self._pending = []      # in-flight gradient all-reduces of the current step
         self._ws = None
         self._ws_n = -1
+        self.render_call = None   # the last step's render_call.RenderCall (addresses of that step's buffers; engine-owned workspace)
         self._bufs = None
         # buffers of a step with a ray gradient, sized in _ray_grad_bufs: the coarse net's part of d(loss)/d(rays) (forward_backward),
         # one backward tmp per net with its size in bytes, the step routine's own ray gradient (the fine net's part)
@@ -182,30 +183,21 @@ class TrainEngine:
     def _prepare(self, n):
         if self._ws_n == n:
             return
-        lib = self.lib
         plan_f = self.mf._plan if self.mf is not None else None
-        wsb = lib.render_workspace_bytes(self.mc._plan, plan_f, C.byref(self.cfg), n, 1)
-        if wsb < 0:
-            raise L.NerfHipError(lib.last_error().decode())
-        self._ws = torch.empty(wsb // 4 + 1, dtype=torch.float32, device=self.dev)
-        self._wsb = wsb
+        self._wsb = RenderCall.workspace_bytes(self.lib, self.mc._plan, plan_f, self.cfg, n, 1)
+        self._ws = torch.empty(self._wsb // 4 + 1, dtype=torch.float32, device=self.dev)
         self._ws_n = n
+        self._regions = {}   # (the workspace offsets the steps' RenderCalls look up: asked once per n)
         mk = lambda *s: torch.empty(s, dtype=torch.float32, device=self.dev)  # noqa: E731
         if self.occupancy is not None:   # (the list area of the culled forwards; its first four words: occupancy_counts)
-            self._occ_tb = lib.render_occ_tmp_bytes(C.byref(self.cfg), n)
+            self._occ_tb = RenderCall.occ_tmp_bytes(self.lib, self.cfg, n)
             self._occ_tmp = torch.zeros(self._occ_tb // 4 + 64, dtype=torch.int32, device=self.dev)
         self._bufs = dict(rgb_c=mk(n, 3), rgb_f=mk(n, 3), g_c=mk(n, 3), g_f=mk(n, 3), disp_c=mk(n), acc_c=mk(n),
                           disp_f=mk(n), acc_f=mk(n))
-        if any(self.spread):   # (the regions the spread kernel reads, and what it writes)
-            self._spread_bufs = {}
-            for fine, tag, S in ((0, "coarse", self.cfg.num_coarse), (1, "fine", self.cfg.num_coarse + self.cfg.num_fine)):
-                if self.spread[fine] > 0.0:
-                    offs = []
-                    for name in ("raw_", "z_"):
-                        off, nb = C.c_int64(), C.c_int64()
-                        lib.render_workspace_region(self.mc._plan, plan_f, C.byref(self.cfg), n, 1, (name + tag).encode(), C.byref(off), C.byref(nb))
-                        offs.append(off.value)
-                    self._spread_bufs[fine] = (mk(n, S), torch.zeros(n, dtype=torch.float32, device=self.dev), offs[0], offs[1], S)
+        if any(self.spread):   # (what the spread kernel writes)
+            S = (self.cfg.num_coarse, self.cfg.num_coarse + self.cfg.num_fine)
+            self._spread_bufs = {fine: (mk(n, S[fine]), torch.zeros(n, dtype=torch.float32, device=self.dev))
+                                 for fine in (0, 1) if self.spread[fine] > 0.0}
 
     def workspace_bytes(self):
         return 0 if self._ws is None else self._wsb
@@ -242,10 +234,7 @@ class TrainEngine:
         if self._rg_n != n:
             plan_f = self.mf._plan if self.mf is not None else None
             # (one tmp serves both forms of the step: the trainable one's and the frozen one's, whichever is larger)
-            tb = max(self.lib.render_bwd_rays_tmp_bytes(self.mc._plan, plan_f, C.byref(self.cfg), n),
-                     self.lib.render_grad_rays_tmp_bytes(self.mc._plan, plan_f, C.byref(self.cfg), n))
-            if tb < 0:
-                raise L.NerfHipError(self.lib.last_error().decode())
+            tb = max(RenderCall.tmp_bytes(self.lib, self.mc._plan, plan_f, self.cfg, n))
             self.ray_grad_coarse = mk(n, self.stride) if self.mf is not None else None
             self._rg_tmp = (mk(tb // 4 + 4), mk(tb // 4 + 4) if self.mf is not None else None, tb)
             self._rg_n = n
@@ -322,30 +311,29 @@ class TrainEngine:
         b = self._bufs
         nf = self.cfg.num_fine
         plan_f = self.mf._plan if self.mf is not None else None
-        out = L.RenderOut(b["rgb_c"].data_ptr(), b["disp_c"].data_ptr(), b["acc_c"].data_ptr(), None,
-                          b["rgb_f"].data_ptr() if nf > 0 else None, b["disp_f"].data_ptr() if nf > 0 else None,
-                          b["acc_f"].data_ptr() if nf > 0 else None, None)
+        out = (b["rgb_c"].data_ptr(), b["disp_c"].data_ptr(), b["acc_c"].data_ptr(), None,
+               b["rgb_f"].data_ptr() if nf > 0 else None, b["disp_f"].data_ptr() if nf > 0 else None,
+               b["acc_f"].data_ptr() if nf > 0 else None, None)
         seed = self.seed + (self.step_count if step is None else step) * 0x9E3779B97F4A7C15 & 0xFFFFFFFFFFFFFFFF
-        pf = self.packed_f.data_ptr() if nf > 0 else None
         gc = self.grad[:self.nc_params]
         gf = self.grad[self.nc_params:] if nf > 0 else None
         tstride = target.stride(0)
-        cot_c = L.RenderCotangents(b["g_c"].data_ptr(), None, None, None, None, None)
-        cot_f = L.RenderCotangents(None, None, None, b["g_f"].data_ptr() if nf > 0 else None, None, None)
-        rr = None
+        cot_c = (b["g_c"].data_ptr(), None, None, None, None, None)
+        cot_f = (None, None, None, b["g_f"].data_ptr() if nf > 0 else None, None, None)
+        rand = None
         if draws is not None:
             shapes = ((n, self.cfg.num_coarse), (n, self.cfg.num_coarse), (n, nf), (n, self.cfg.num_coarse + nf))
             for d, shp in zip(draws, shapes):
                 if d is not None and (d.device != self.dev or d.dtype != torch.float32 or tuple(d.shape) != shp or not d.is_contiguous()):
                     raise RuntimeError("TrainEngine: a random-draw tensor must be contiguous float32 %s on %s" % (shp, self.dev))
             self._draws = tuple(draws)  # (kept alive until the next step: the backward kernels read them again)
-            rr = C.byref(L.RenderRand(*[None if d is None else d.data_ptr() for d in draws]))
-        fwd_args = (self.mc._plan, plan_f, C.byref(self.cfg), rays.data_ptr(), n, self.packed_c.data_ptr(), pf,
-                    self.t_vals.data_ptr(), self.u_det.data_ptr() if nf > 0 else None, rr, seed, ray_offset,
-                    C.byref(out), self._ws.data_ptr(), self._wsb, 1)
-        bwd_head = (self.mc._plan, plan_f, C.byref(self.cfg), rays.data_ptr(), n, self.packed_c.data_ptr(), pf, rr, seed,
-                    ray_offset)
-        bwd_tail = (self._ws.data_ptr(), self._wsb, gc.data_ptr(), gf.data_ptr() if gf is not None else None)
+            rand = [None if d is None else d.data_ptr() for d in draws]
+        # (the step's render: layout 1 -- the two nets' backwards may run at the same time --, the offsets of _prepare's workspace)
+        call = self.render_call = RenderCall(lib, self.mc._plan, plan_f, self.cfg, rays.data_ptr(), n, self.packed_c.data_ptr(),
+                                             self.packed_f.data_ptr() if nf > 0 else None, self.t_vals.data_ptr(),
+                                             self.u_det.data_ptr() if nf > 0 else None, rand, seed, ray_offset, 1, self._ws.data_ptr(),
+                                             self._wsb, self._regions)
+        g_params = (gc.data_ptr(), gf.data_ptr() if gf is not None else None)
         tmp_c = tmp_f = g_rays_c = None
         if ray_grad is not None:
             g_rays_c, (tmp_c, tmp_f, tmpb) = self._ray_grad_bufs(n)
@@ -360,16 +348,12 @@ class TrainEngine:
             all-reduce), on `stream`.  With a spread weight: the spread kernel between the loss and the backward, and the backward's
             _w form."""
             fine = int(part == L.PART_FINE)
-            w = "_w" if self.spread[fine] > 0.0 else ""
-            if w:
-                gw, sl, raw_off, z_off, S = self._spread_bufs[fine]
-                noise = None if draws is None or draws[1 + 2 * fine] is None else draws[1 + 2 * fine].data_ptr()
+            g_weights = None
+            if self.spread[fine] > 0.0:
+                gw, sl = self._spread_bufs[fine]
                 # (scale: lambda / n under the loss launch's grad_scale convention -- the total is the mse terms + lambda * mean_ray(L))
-                lib.spread_loss(self._ws.data_ptr() + raw_off, self._ws.data_ptr() + z_off, rays.data_ptr(), self.stride, n, S,
-                                self.cfg.noise_std, noise, seed, 1 + 2 * fine, ray_offset, self.spread[fine] * gscale / n, None,
-                                sl.data_ptr(), gw.data_ptr(), stream)
-                six = [getattr(cot, k) for k, _ in L.RenderCotangents._fields_]
-                cot = L.RenderCotangentsW(*six, None if fine else gw.data_ptr(), gw.data_ptr() if fine else None)
+                call.spread(fine, self.spread[fine] * gscale / n, None, sl.data_ptr(), gw.data_ptr(), stream)
+                g_weights = (None, gw.data_ptr()) if fine else (gw.data_ptr(), None)
             if exposure is None:
                 lib.mse_loss_fwd_bwd(rgb.data_ptr(), None, target.data_ptr(), tstride, n, gscale, g_rgb.data_ptr(), None, loss.data_ptr(), stream)
             else:
@@ -377,22 +361,17 @@ class TrainEngine:
                                            exposure.expo.data_ptr(), exposure.num_views, g_rgb.data_ptr(), None, loss.data_ptr(), stream)
             if ray_grad is None and frozen:   # (the fit of the exposure table alone: no render backward)
                 return
-            if ray_grad is None:
-                getattr(lib, "render_bwd_parts" + w)(*bwd_head, C.byref(cot), *bwd_tail, part, stream)
-            else:
-                rays_tail = (part, pc_flat, pf_flat, tmp.data_ptr(), tmpb, g_rays.data_ptr(), stream)
-                if frozen:   # (no parameter gradient: the workspace alone, no gradient slices)
-                    lib.render_grad_rays(*bwd_head, C.byref(cot), *bwd_tail[:2], *rays_tail)
-                else:
-                    getattr(lib, "render_bwd_rays" + w)(*bwd_head, C.byref(cot), *bwd_tail, *rays_tail)
+            # (frozen: no parameter gradient -- the ray gradient alone)
+            rays_args = None if ray_grad is None else (pc_flat, pf_flat, tmp.data_ptr(), tmpb, g_rays.data_ptr())
+            call.backward(cot, g_params, part, stream, g_weights, rays_args, frozen)
             if not frozen:
                 model._window_grads(grad, model._window_w, stream)
 
+        occ = None
         if culled:   # (the grid's struct is read during the call; one list area serves both forwards: both run on the main stream)
-            occ = C.byref(self.occupancy._struct())
-            fwd = lambda part, stream: lib.render_fwd_occ_train(*fwd_args, part, occ, occ, self._occ_tmp.data_ptr(), self._occ_tb, stream)  # noqa: E731
-        else:
-            fwd = lambda part, stream: lib.render_fwd_parts(*fwd_args, part, stream)  # noqa: E731
+            grid = self.occupancy._struct()
+            occ = (grid, grid, self._occ_tmp.data_ptr(), self._occ_tb)
+        fwd = lambda part, stream: call.forward(out, part, stream, occ)  # noqa: E731
         coarse = (L.PART_COARSE, b["rgb_c"], b["g_c"], cot_c, self._loss_c, gc, self.mc, tmp_c, g_rays_c)
         fine = (L.PART_FINE, b["rgb_f"], b["g_f"], cot_f, self._loss_f, gf, self.mf, tmp_f, ray_grad)
         self._pending = []
@@ -476,7 +455,7 @@ class TrainEngine:
 
     def _stats_words(self, name):
         """The two statistics words of net `name` in the workspace of the last step."""
-        return BM.stats_words(self.lib, self.mc._plan, self.mf._plan if self.mf is not None else None, self.cfg, self._ws_n, 1, name, self._ws)
+        return BM.stats_words(self.render_call, name, self._ws)
 
     def backward_sample_counts(self):
         """{"coarse": (kept, total), "fine": (kept, total)}: the sample points the last step's COMPACTED backward of each net kept

@@ -16,6 +16,7 @@ import ctypes as C
 import torch
 
 from . import _lib as L
+from .render_call import RenderCall
 
 
 def _aabb(aabb):
@@ -210,26 +211,22 @@ def render_fwd_occ(rays, model_c, model_f, cfg_tuple, rand, grid):
     cfg = L.RenderCfg(nc, nf, int(bool(perturb)), int(bool(lindisp)), int(bool(white)), float(noise_std), stride)
     plan_c = model_c._inference_plan()
     plan_f = model_f._inference_plan() if nf > 0 else None
-    wsb = lib.render_workspace_bytes(plan_c, plan_f, C.byref(cfg), n, 0)
-    tb = lib.render_occ_tmp_bytes(C.byref(cfg), n)
-    if wsb < 0 or tb < 0:
-        raise L.NerfHipError(lib.last_error().decode())
+    wsb = RenderCall.workspace_bytes(lib, plan_c, plan_f, cfg, n, 0)
+    tb = RenderCall.occ_tmp_bytes(lib, cfg, n)
     ws = torch.empty(wsb // 4 + 1, dtype=torch.float32, device=dev)
     tmp = torch.empty(tb // 4, dtype=torch.int32, device=dev)
     names = ("rgb_coarse", "disp_coarse", "acc_coarse", "depth_coarse", "rgb_fine", "disp_fine", "acc_fine", "depth_fine")
     bufs = {k: torch.empty((n, 3) if k.startswith("rgb") else (n,), dtype=torch.float32, device=dev) for k in names}
-    out = L.RenderOut(*[bufs[k].data_ptr() for k in names])
-    rr = L.RenderRand(*[None if r is None else r.data_ptr() for r in rand])
     packed_c = model_c._inference_packed()
     packed_f = model_f._inference_packed() if nf > 0 else None
+    call = RenderCall(lib, plan_c, plan_f, cfg, rays.data_ptr(), n, packed_c.data_ptr(), packed_f.data_ptr() if nf > 0 else None,
+                      linspace01(nc, dev).data_ptr(), linspace01(nf, dev).data_ptr() if nf > 0 else None,
+                      [None if r is None else r.data_ptr() for r in rand], 0, 0, 0, ws.data_ptr(), wsb)
     g = grid._struct()
     if n > 0:
         tmp[:4].zero_()  # (a pass that does not run -- num_fine == 0 -- leaves its pair untouched)
         with L.launch_on(rays, ws, tmp, grid.bits, packed_c, packed_f, *[r for r in rand if r is not None]) as st:
-            lib.render_fwd_occ(plan_c, plan_f, C.byref(cfg), rays.data_ptr(), n, packed_c.data_ptr(),
-                               packed_f.data_ptr() if packed_f is not None else None, linspace01(nc, dev).data_ptr(),
-                               linspace01(nf, dev).data_ptr() if nf > 0 else None, C.byref(rr), 0, 0, C.byref(out), ws.data_ptr(), wsb,
-                               0, L.PART_COARSE | L.PART_FINE, C.byref(g), C.byref(g), tmp.data_ptr(), tb, st)
+            call.forward([bufs[k].data_ptr() for k in names], L.PART_COARSE | L.PART_FINE, st, (g, g, tmp.data_ptr(), tb))
         grid.last_counts = tmp[:4]  # (a view of the chunk's list area: no copy, no sync)
         grid.view_counts += grid.last_counts
     return tuple(bufs[k] for k in names)

@@ -13,6 +13,7 @@ Reference quirk kept on purpose: run_one_iter_of_nerf does not forward `mode` to
 (train_utils.py:171-181), so rendering always reads options.nerf.train.* ; only the ray chunk size and the output
 reshape honour `mode`.
 """
+import contextlib
 import ctypes as C
 
 import torch
@@ -22,6 +23,7 @@ from . import backward_mode as BM
 from .models import FlexibleNeRFModel
 from .nerf_helpers import (EmbeddingFunction, _dist_vector, _intr_vector, get_minibatches, linspace01, ndc_rays,
                            sample_pdf_2 as sample_pdf)
+from .render_call import RenderCall
 from .volume_rendering_utils import volume_render_radiance_field
 
 
@@ -104,29 +106,28 @@ class _FusedRender(torch.autograd.Function):
         plan_f = (model_f._plan if training else model_f._inference_plan()) if nf > 0 else None
         # (training layout 2: this node's backward runs the two nets one after the other on one stream, so they share one
         # set of backward buffers -- several nodes may be alive at once when a batch is rendered in ray chunks)
-        wsb = lib.render_workspace_bytes(plan_c, plan_f, C.byref(cfg), n, 2 if training else 0)
-        if wsb < 0:
-            raise L.NerfHipError(lib.last_error().decode())
+        layout = 2 if training else 0
+        wsb = RenderCall.workspace_bytes(lib, plan_c, plan_f, cfg, n, layout)
         ws = torch.empty(wsb // 4 + 1, dtype=torch.float32, device=dev)
         ctx.set_materialize_grads(False)  # cotangents of outputs the loss never touched arrive as None, not as zeros
         names = ("rgb_coarse", "disp_coarse", "acc_coarse", "depth_coarse", "rgb_fine", "disp_fine", "acc_fine",
                  "depth_fine")
         bufs = {k: torch.empty((n, 3) if k.startswith("rgb") else (n,), dtype=torch.float32, device=dev) for k in names}
-        out = L.RenderOut(*[bufs[k].data_ptr() for k in names])
-        rr = L.RenderRand(*[None if r is None else r.data_ptr() for r in rand])
         packed_c = model_c._packed() if training else model_c._inference_packed()
         packed_f = (model_f._packed() if training else model_f._inference_packed()) if nf > 0 else None
+        ctx.call = call = RenderCall(lib, plan_c, plan_f, cfg, rays.data_ptr(), n, packed_c.data_ptr(), _ptr(packed_f),
+                                     linspace01(nc, dev).data_ptr(), linspace01(nf, dev).data_ptr() if nf > 0 else None,
+                                     [_ptr(r) for r in rand], 0, 0, layout, ws.data_ptr(), wsb)
         with L.launch_on(rays, ws, packed_c, packed_f, *[r for r in rand if r is not None]) as st:
-            lib.render_fwd(plan_c, plan_f, C.byref(cfg), rays.data_ptr(), n, packed_c.data_ptr(),
-                           packed_f.data_ptr() if packed_f is not None else None, linspace01(nc, dev).data_ptr(),
-                           linspace01(nf, dev).data_ptr() if nf > 0 else None, C.byref(rr), 0, 0, C.byref(out),
-                           ws.data_ptr(), wsb, 2 if training else 0, st)  # (2: this node's backward shares one set of backward buffers)
+            call.forward([bufs[k].data_ptr() for k in names], None, st)
         # (the ray gradient multiplies by the weights of THIS forward: keep copies only if it will be asked for)
         # (... of the nets as they ran: theta_eff under an encoding window)
         flats = (model_c._theta_eff(copy=True), model_f._theta_eff(copy=True) if nf > 0 else None) if (training and rays_grad) else None
         # (the window is schedule state of the model: the node's backward windows its gradients as its forward was windowed)
         ctx.windows = (model_c._window_w, model_f._window_w if nf > 0 else None)
-        ctx.keep = (rays, model_c, model_f, cfg, rand, ws, wsb, packed_c, packed_f, training, flats)
+        ctx.keep = (rays, model_c, model_f, ws, flats)
+        # (ctx.call holds addresses and plan handles: what else stands behind them, kept alive for the node's backward)
+        ctx.alive = (rand, packed_c, packed_f, (model_c._plan_owner, model_f._plan_owner if nf > 0 else None) if training else None)
         # (the backward data flow is an option of the PLAN, and what this forward left in the workspace -- the general stash, nothing, the
         # register-image stash -- depends on it: the node's backward runs in the mode its forward ran in, whatever
         # set_backward_compaction was called with in between)
@@ -143,36 +144,19 @@ class _FusedRender(torch.autograd.Function):
             raise ValueError("spread=True on frozen nets (set_frozen) makes no sense: the spread loss regularises the nets")
         sp = [torch.empty(n, dtype=torch.float32, device=dev) for _ in range(2 if nf > 0 else 1)]
         with L.launch_on(rays, ws, *sp) as st:
-            for fine, out_sp in enumerate(sp):
-                _FusedRender._spread(lib, ctx.keep, fine, None, out_sp, None, st)
+            for fine, out_sp in enumerate(sp):   # (the losses alone, over the raw rows and depths the forward left in its workspace)
+                call.spread(fine, 1.0, None, out_sp.data_ptr(), None, st)
         return tuple(bufs[k] for k in names) + (sp[0], sp[1] if nf > 0 else None)
 
     @staticmethod
-    def _spread(lib, keep, fine, g_loss, loss, g_weights, st):
-        """nerfhip_spread_loss of one pass over the raw rows and depths the node's forward left in its workspace."""
-        rays, model_c, model_f, cfg, rand, ws, wsb, _, _, training, _ = keep
-        n = rays.shape[0]
-        plan_c = model_c._plan if training else model_c._inference_plan()
-        plan_f = (model_f._plan if training else model_f._inference_plan()) if cfg.num_fine > 0 else None
-        offs = []
-        for name in (b"raw_fine", b"z_fine") if fine else (b"raw_coarse", b"z_coarse"):
-            off, nb = C.c_int64(), C.c_int64()
-            lib.render_workspace_region(plan_c, plan_f, C.byref(cfg), n, 2 if training else 0, name, C.byref(off), C.byref(nb))
-            offs.append(ws.data_ptr() + off.value)
-        noise = rand[3 if fine else 1]
-        lib.spread_loss(offs[0], offs[1], rays.data_ptr(), rays.shape[1], n, cfg.num_coarse + (cfg.num_fine if fine else 0), cfg.noise_std,
-                        None if noise is None else noise.data_ptr(), 0, 3 if fine else 1, 0, 1.0,
-                        None if g_loss is None else g_loss.data_ptr(), None if loss is None else loss.data_ptr(),
-                        None if g_weights is None else g_weights.data_ptr(), st)
-
-    @staticmethod
     def backward(ctx, g_rgb_c, g_disp_c, g_acc_c, g_depth_c, g_rgb_f, g_disp_f, g_acc_f, g_depth_f, *g_spread):
-        lib = L.get_lib()
-        rays, model_c, model_f, cfg, rand, ws, wsb, packed_c, packed_f, training, flats = ctx.keep
-        if not training:
+        call, lib = ctx.call, ctx.call.lib
+        rays, model_c, model_f, ws, flats = ctx.keep
+        if call.layout == 0:
             raise RuntimeError("fused render was run without gradient bookkeeping")
         n = rays.shape[0]
         dev = rays.device
+        cfg = call.cfg
         nf = cfg.num_fine
         keep = [None if g is None else g.contiguous().float()
                 for g in (g_rgb_c, g_acc_c, g_depth_c, g_rgb_f, g_acc_f, g_depth_f)]
@@ -188,21 +172,17 @@ class _FusedRender(torch.autograd.Function):
         gpf = torch.zeros(model_f.num_flat_params, dtype=torch.float32, device=dev) if nf > 0 else None
         g_rays = torch.zeros_like(rays) if flats is not None else None
         if parts:
-            cot = L.RenderCotangents(*[None if k is None else k.data_ptr() for k in keep])
-            bwd_rays = lib.render_bwd_rays
             gw = [None, None]
-            if ctx.spread and (g_sp[0] is not None or g_sp[1] is not None):   # (the weight cotangents of the passes whose spread a loss touched)
+            if ctx.spread:   # (the weight cotangents of the passes whose spread a loss touched)
                 for fine in (0, 1):
                     if g_sp[fine] is not None:
                         gw[fine] = torch.empty((n, cfg.num_coarse + (nf if fine else 0)), dtype=torch.float32, device=dev)
-                cot = L.RenderCotangentsW(*[None if k is None else k.data_ptr() for k in keep], *[None if g is None else g.data_ptr() for g in gw])
-                bwd_rays = lib.render_bwd_rays_w
-            rr = L.RenderRand(*[None if r is None else r.data_ptr() for r in rand])
-            plan_f = model_f._plan if nf > 0 else None
-            tmp, tmpb = None, 0
+            g_weights = [_ptr(g) for g in gw] if (gw[0] is not None or gw[1] is not None) else None
+            tmp = rays_args = None
             if g_rays is not None:
-                tmpb = lib.render_bwd_rays_tmp_bytes(model_c._plan, plan_f, C.byref(cfg), n)
-                tmp = torch.empty(tmpb // 4 + 1, dtype=torch.float32, device=dev)
+                tmpb = RenderCall.tmp_bytes(lib, call.plan_c, call.plan_f, cfg, n)[0]
+                tmp = torch.empty(tmpb // 4 + 4, dtype=torch.float32, device=dev)
+                rays_args = (flats[0].data_ptr(), _ptr(flats[1]), tmp.data_ptr(), tmpb, g_rays.data_ptr())
             # "auto" models read the {kept, total} words of their compacted backward; the two nets share one set of backward buffers
             # here (the fine pass runs first), so the passes are issued one by one with the copy in between -- the same launches in
             # the same order as the single call (not with a ray gradient: its second pass accumulates into the first one's)
@@ -210,33 +190,17 @@ class _FusedRender(torch.autograd.Function):
             passes = [parts]
             if auto and g_rays is None and parts == (L.PART_COARSE | L.PART_FINE):
                 passes = [L.PART_FINE, L.PART_COARSE]
-            pins = [(p, was, lib.plan_bwd_compaction(p)) for p, was in zip((model_c._plan, plan_f), ctx.bwd_modes) if p is not None]
-            for plan, was, cur in pins:
-                if was != cur:
-                    lib.plan_set_bwd_compaction(plan, was)
-            try:
-                with L.launch_on(rays, ws, gpc, gpf, tmp, *[k for k in keep if k is not None]) as st:
-                    for fine in (0, 1):
-                        if gw[fine] is not None:
-                            _FusedRender._spread(lib, ctx.keep, fine, g_sp[fine], None, gw[fine], st)
-                    for part in passes:
-                        bwd_rays(model_c._plan, plan_f, C.byref(cfg), rays.data_ptr(), n,
-                                 packed_c.data_ptr(), packed_f.data_ptr() if nf > 0 else None, C.byref(rr), 0, 0,
-                                 C.byref(cot), ws.data_ptr(), wsb, gpc.data_ptr(),
-                                 gpf.data_ptr() if gpf is not None else None, part | L.PART_SHARED_BWD,
-                                 flats[0].data_ptr() if flats is not None else None,
-                                 flats[1].data_ptr() if (flats is not None and flats[1] is not None) else None,
-                                 tmp.data_ptr() if tmp is not None else None, tmpb,
-                                 g_rays.data_ptr() if g_rays is not None else None, st)
-                        # (the words in the shared buffers: the coarse net's behind a pass that ran it -- it runs last --, the fine net's
-                        # only between the two passes)
-                        model, net, mode = (model_c, "coarse", ctx.bwd_modes[0]) if part & L.PART_COARSE else (model_f, "fine", ctx.bwd_modes[1])
-                        if (part & L.PART_COARSE or len(passes) == 2) and model in auto and mode in BM.BUILDS_LIST:
-                            model._stats.request([("net", BM.stats_words(lib, model_c._plan, plan_f, cfg, n, 2, net, ws))], torch.cuda.current_stream(dev))
-            finally:
-                for plan, was, cur in pins:
-                    if was != cur:
-                        lib.plan_set_bwd_compaction(plan, cur)
+            with _forward_modes(ctx), L.launch_on(rays, ws, gpc, gpf, tmp, *[k for k in keep if k is not None]) as st:
+                for fine in (0, 1):
+                    if gw[fine] is not None:
+                        call.spread(fine, 1.0, g_sp[fine].data_ptr(), None, gw[fine].data_ptr(), st)
+                for part in passes:
+                    call.backward([_ptr(k) for k in keep], (gpc.data_ptr(), _ptr(gpf)), part, st, g_weights, rays_args)
+                    # (the words in the shared buffers: the coarse net's behind a pass that ran it -- it runs last --, the fine net's
+                    # only between the two passes)
+                    model, net, mode = (model_c, "coarse", ctx.bwd_modes[0]) if part & L.PART_COARSE else (model_f, "fine", ctx.bwd_modes[1])
+                    if (part & L.PART_COARSE or len(passes) == 2) and model in auto and mode in BM.BUILDS_LIST:
+                        model._stats.request([("net", BM.stats_words(call, net, ws))], torch.cuda.current_stream(dev))
         model_c._window_grads(gpc, ctx.windows[0])
         if nf > 0:
             model_f._window_grads(gpf, ctx.windows[1])
@@ -246,34 +210,37 @@ class _FusedRender(torch.autograd.Function):
     @staticmethod
     def _frozen_backward(ctx, keep, parts):
         """d(loss)/d(rays) of a node whose nets were frozen at its forward: no parameter gradient exists anywhere."""
-        lib = L.get_lib()
-        rays, model_c, model_f, cfg, rand, ws, wsb, packed_c, packed_f, training, flats = ctx.keep
-        n, nf = rays.shape[0], cfg.num_fine
+        call = ctx.call
+        rays, _, _, ws, flats = ctx.keep
         g_rays = torch.zeros_like(rays)
         if not parts:
             return g_rays
-        cot = L.RenderCotangents(*[None if k is None else k.data_ptr() for k in keep])
-        rr = L.RenderRand(*[None if r is None else r.data_ptr() for r in rand])
-        plan_f = model_f._plan if nf > 0 else None
-        tmpb = lib.render_grad_rays_tmp_bytes(model_c._plan, plan_f, C.byref(cfg), n)
-        if tmpb < 0:
-            raise L.NerfHipError(lib.last_error().decode())
+        tmpb = RenderCall.tmp_bytes(call.lib, call.plan_c, call.plan_f, call.cfg, call.n)[1]
         tmp = torch.empty(tmpb // 4 + 4, dtype=torch.float32, device=rays.device)
-        pins = [(p, was, lib.plan_bwd_compaction(p)) for p, was in zip((model_c._plan, plan_f), ctx.bwd_modes) if p is not None]
+        with _forward_modes(ctx), L.launch_on(rays, ws, tmp, *[k for k in keep if k is not None]) as st:
+            call.backward([_ptr(k) for k in keep], None, parts, st, None,
+                          (flats[0].data_ptr(), _ptr(flats[1]), tmp.data_ptr(), tmpb, g_rays.data_ptr()), frozen=True)
+        return g_rays
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+@contextlib.contextmanager
+def _forward_modes(ctx):
+    """The plans of a _FusedRender node in the backward modes its forward ran in (ctx.bwd_modes), for the duration of its backward."""
+    lib = ctx.call.lib
+    pins = [(p, was, lib.plan_bwd_compaction(p)) for p, was in zip((ctx.call.plan_c, ctx.call.plan_f), ctx.bwd_modes) if p is not None]
+    for plan, was, cur in pins:
+        if was != cur:
+            lib.plan_set_bwd_compaction(plan, was)
+    try:
+        yield
+    finally:
         for plan, was, cur in pins:
             if was != cur:
-                lib.plan_set_bwd_compaction(plan, was)
-        try:
-            with L.launch_on(rays, ws, tmp, *[k for k in keep if k is not None]) as st:
-                lib.render_grad_rays(model_c._plan, plan_f, C.byref(cfg), rays.data_ptr(), n, packed_c.data_ptr(),
-                                     packed_f.data_ptr() if nf > 0 else None, C.byref(rr), 0, 0, C.byref(cot), ws.data_ptr(), wsb,
-                                     parts | L.PART_SHARED_BWD, flats[0].data_ptr(), flats[1].data_ptr() if flats[1] is not None else None,
-                                     tmp.data_ptr(), tmpb, g_rays.data_ptr(), st)
-        finally:
-            for plan, was, cur in pins:
-                if was != cur:
-                    lib.plan_set_bwd_compaction(plan, cur)
-        return g_rays
+                lib.plan_set_bwd_compaction(plan, cur)
 
 
 def _predict_fused(ray_batch, model_coarse, model_fine, opts, occupancy=None, spread=False):

@@ -88,14 +88,12 @@ def run(precisions, rounds):
                 out[name] = dict(ms_per_step=round(m, 4), rounds_ms=[round(v, 4) for v in ms[name]], steps_per_window=size[name],
                                  same_arm_spread_pct=round(100.0 * (max(ms[name]) - min(ms[name])) / m, 2))
             out["spread_over_plain_pct"] = round(100.0 * (out["spread"]["ms_per_step"] / out["plain"]["ms_per_step"] - 1.0), 2)
-            # one nerfhip_spread_loss launch per pass, over the workspace the last step left, in windows of its own
-            e = arms["spread"]
-            lib, st = e.lib, torch.cuda.current_stream(dev).cuda_stream
-            rays = batches[0][0]
+            # one nerfhip_spread_loss launch per pass, over the workspace the last step left (the engine's last RenderCall), into
+            # buffers of its own, in windows of its own
+            render, st = arms["spread"].render_call, torch.cuda.current_stream(dev).cuda_stream
             for fine, tag in ((0, "coarse"), (1, "fine")):
-                gw, sl, raw_off, z_off, S = e._spread_bufs[fine]
-                call = lambda: lib.spread_loss(e._ws.data_ptr() + raw_off, e._ws.data_ptr() + z_off, rays.data_ptr(), e.stride, RAYS, S, 0.0,  # noqa: E731
-                                               None, 0, 1 + 2 * fine, 0, LAMBDA / RAYS, None, sl.data_ptr(), gw.data_ptr(), st)
+                gw, sl = torch.empty(RAYS, 64 + 64 * fine, device=dev), torch.empty(RAYS, device=dev)
+                call = lambda: render.spread(fine, LAMBDA / RAYS, None, sl.data_ptr(), gw.data_ptr(), st)  # noqa: E731
                 for _ in range(10):
                     call()
                 torch.cuda.synchronize()

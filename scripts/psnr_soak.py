@@ -26,7 +26,6 @@ arms), and records
     python scripts/psnr_soak.py SEED ITERS OUT.json [--arms engine,engine_f16tr] [--lr 1e-3] [--check 2000] [--diag 1000]
 """
 import argparse
-import ctypes as C
 import json
 import math
 import os
@@ -99,9 +98,8 @@ def diagnose(eng, mf, rays, tgt, student, f16):
     out = dict(grad_finite=bool(torch.isfinite(eng.grad).all()), loss_finite=bool(torch.isfinite(eng.loss).all()),
                grad_absmax=float(eng.grad.abs().max()))
     n = rays.shape[0]
-    off, nbytes = C.c_int64(), C.c_int64()
-    lib.render_workspace_region(eng.mc._plan, eng.mf._plan, C.byref(eng.cfg), n, 1, b"z_fine", C.byref(off), C.byref(nbytes))
-    z = eng._ws.view(torch.uint8)[off.value:off.value + nbytes.value].view(torch.float32).reshape(n, NC + NF)[:DIAG_RAYS].clone()
+    off, nbytes = eng.render_call.region("z_fine")
+    z = eng._ws.view(torch.uint8)[off:off + nbytes].view(torch.float32).reshape(n, NC + NF)[:DIAG_RAYS].clone()
     r = rays[:DIAG_RAYS]
     pts = (r[:, None, :3] + r[:, None, 3:6] * z[..., None]).reshape(-1, 3)
     emb = O.positional_encoding(pts, student["num_encoding_fn_xyz"], True, True)

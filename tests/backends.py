@@ -18,6 +18,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 
 import nerf_pytorch_amd._lib as L  # noqa: E402
+from nerf_pytorch_amd.render_call import RenderCall  # noqa: E402
 
 EMU_SO = os.path.join(ROOT, "tests", "emu", "libnerfhip_emu.so")
 CSRC = os.path.join(ROOT, "nerf-pytorch_amd", "csrc")
@@ -316,77 +317,28 @@ class Backend:
                g_rgb=None, want_regions=(), ray_grad_params=None):
         """opt: dict(num_coarse, num_fine, perturb, lindisp, white_background, noise_std).  Returns dict of outputs
         (+ flat grads 'g_params_coarse/fine' when g_rgb = (g_c, g_f), or a callable that makes them from the outputs, is given)."""
-        rand = rand or {}
-        n, stride = rays.shape
-        nc, nf = opt["num_coarse"], opt["num_fine"]
-        cfg = L.RenderCfg(nc, nf, int(bool(opt.get("perturb", True))), int(bool(opt.get("lindisp", False))),
-                          int(bool(opt.get("white_background", False))), float(opt.get("noise_std", 0.0)), stride)
-        dr = self.dev(np.ascontiguousarray(rays, np.float32))
-        dt = self.dev(self._linspace01(nc))
-        dud = self.dev(self._linspace01(nf)) if nf > 0 else None
-        keep = [self.devopt(rand.get(k)) for k in ("t_rand", "noise_coarse", "u", "noise_fine")]
-        rr = L.RenderRand(*[self.p(k) for k in keep])
-        names = ("rgb_coarse", "disp_coarse", "acc_coarse", "depth_coarse", "rgb_fine", "disp_fine", "acc_fine", "depth_fine")
-        bufs = {k: self.empty((n, 3) if k.startswith("rgb") else (n,)) for k in names}
-        ro = L.RenderOut(*[self.ptr(bufs[k]) for k in names])
-        wsb = self.lib.render_workspace_bytes(plan_c, plan_f, C.byref(cfg), n, int(training))
-        assert wsb >= 0, self.lib.last_error()
-        ws = self.empty((wsb // 4 + 1,))
-        self.lib.render_fwd(plan_c, plan_f, C.byref(cfg), self.ptr(dr), n, self.ptr(packed_c), self.p(packed_f),
-                            self.ptr(dt), self.p(dud), C.byref(rr), seed, ray_offset, C.byref(ro), self.ptr(ws), wsb,
-                            int(training), self.stream())
-        out = {k: self.host(v) for k, v in bufs.items()}
+        s = RenderSession(self, plan_c, plan_f, packed_c, packed_f, rays, opt, rand, int(training), seed, ray_offset)
+        s.forward()
+        out = s.maps()
         for name in want_regions:  # per-sample intermediates the forward left in the workspace
-            off, nb = C.c_int64(), C.c_int64()
-            self.lib.render_workspace_region(plan_c, plan_f, C.byref(cfg), n, int(training), name.encode(), C.byref(off),
-                                             C.byref(nb))
-            flat = self.host(ws[off.value // 4:(off.value + nb.value) // 4])
-            out[name] = flat.reshape(n, -1, 4) if name.startswith("raw") else flat.reshape(n, -1)
-        if nf == 0:
-            for k in names[4:]:
+            out[name] = s.region(name)
+        if s.nf == 0:
+            for k in MAPS[4:]:
                 out[k] = None
         if callable(g_rgb):  # g_rgb(outputs) -> (g_coarse, g_fine): the loss between this forward and its backward
             g_rgb = g_rgb(out)
         if g_rgb is not None:
-            gc, gf = self.dev(np.ascontiguousarray(g_rgb[0], np.float32)), self.devopt(g_rgb[1])
-            gpc = self.empty((self.lib.plan_num_params(plan_c),))
-            gpf = self.empty((self.lib.plan_num_params(plan_f),)) if nf > 0 else None
             compacted = bool(self.lib.plan_bwd_compaction(plan_c)) or bool(plan_f and self.lib.plan_bwd_compaction(plan_f))
-            if ray_grad_params is None and compacted and int(training) == 1:
-                # (one set of backward buffers per net -- the layout the workspace was sized for --, so that each net's kept / total
-                # counts survive the other net's backward: nerfhip_render_bwd shares ONE scratch between the two)
-                cot = L.RenderCotangents(self.ptr(gc), None, None, self.p(gf), None, None)
-                self.lib.render_bwd_parts(plan_c, plan_f, C.byref(cfg), self.ptr(dr), n, self.ptr(packed_c), self.p(packed_f),
-                                          C.byref(rr), seed, ray_offset, C.byref(cot), self.ptr(ws), wsb, self.ptr(gpc), self.p(gpf),
-                                          L.PART_COARSE | (L.PART_FINE if nf > 0 else 0), self.stream())
-            elif ray_grad_params is None:
-                self.lib.render_bwd(plan_c, plan_f, C.byref(cfg), self.ptr(dr), n, self.ptr(packed_c), self.p(packed_f),
-                                    C.byref(rr), seed, ray_offset, self.ptr(gc), self.p(gf), self.ptr(ws), wsb, self.ptr(gpc),
-                                    self.p(gpf), self.stream())
-            else:  # ... and d(loss)/d(rays): ray_grad_params = the two flat parameter vectors
-                fc, ff = self.dev(ray_grad_params[0]), self.devopt(ray_grad_params[1])
-                tb = self.lib.render_bwd_rays_tmp_bytes(plan_c, plan_f, C.byref(cfg), n)
-                tmp, g_rays = self.empty((tb // 4 + 1,)), self.empty((n, stride))
-                cot = L.RenderCotangents(self.ptr(gc), None, None, self.p(gf), None, None)
-                self.lib.render_bwd_rays(plan_c, plan_f, C.byref(cfg), self.ptr(dr), n, self.ptr(packed_c), self.p(packed_f),
-                                         C.byref(rr), seed, ray_offset, C.byref(cot), self.ptr(ws), wsb, self.ptr(gpc),
-                                         self.p(gpf), L.PART_COARSE | (L.PART_FINE if nf > 0 else 0), self.ptr(fc), self.p(ff),
-                                         self.ptr(tmp), tb, self.ptr(g_rays), self.stream())
-                out["g_rays"] = self.host(g_rays)
-            out["g_params_coarse"] = self.host(gpc)
-            out["g_params_fine"] = self.host(gpf) if gpf is not None else None
+            # (compacted: one set of backward buffers per net -- the layout the workspace was sized for --, so that each net's kept /
+            # total counts survive the other net's backward: nerfhip_render_bwd shares ONE scratch between the two, and it is called
+            # here on purpose where nothing is counted; ray_grad_params = the two flat parameter vectors: d(loss)/d(rays) as well)
+            listed = ray_grad_params is None and compacted and int(training) == 1
+            entry = "rays" if ray_grad_params is not None else ("parts" if listed else "rgb")
+            out.update(s.backward(g_rgb, entry=entry, params=ray_grad_params))
             # (kept, total) sample points of each net's backward, where its plan runs compacted (nerfhip_plan_set_bwd_compaction)
-            for name, plan, samples in (("coarse", plan_c, nc), ("fine", plan_f, nc + nf)):
-                if plan is None or samples == 0 or not self.lib.plan_bwd_compaction(plan):
-                    continue
-                off, nb = C.c_int64(), C.c_int64()
-                if not (ray_grad_params is None and int(training) == 1):
-                    continue  # (shared backward buffers: the second net's backward has overwritten the first one's counts)
-                self.lib.render_workspace_region(plan_c, plan_f, C.byref(cfg), n, 1, ("bwd_scratch_" + name).encode(), C.byref(off),
-                                                 C.byref(nb))
-                so = self.lib.plan_bwd_stats_offset(plan, n * samples)
-                w = self.host(ws[(off.value + so) // 4:(off.value + so) // 4 + 2])
-                out["bwd_kept_" + name] = tuple(int(v) for v in np.ascontiguousarray(w).view(np.int32))
+            for name, plan in (("coarse", plan_c), ("fine", plan_f)):
+                if listed and plan is not None and self.lib.plan_bwd_compaction(plan):
+                    out["bwd_kept_" + name] = s.kept(name)
         return out
 
     def mse_loss(self, rgb_c, rgb_f, target, grad_scale=1.0):
@@ -453,3 +405,159 @@ class GpuBackend(Backend):
 
     def stream(self):
         return self.torch.cuda.current_stream().cuda_stream
+
+
+# -- one fused render on a backend ------------------------------------------------------------------------------------------
+MAPS = ("rgb_coarse", "disp_coarse", "acc_coarse", "depth_coarse", "rgb_fine", "disp_fine", "acc_fine", "depth_fine")
+BOTH = L.PART_COARSE | L.PART_FINE
+SAME = object()   # forward_occ(grid_f=SAME): the fine pass through the coarse pass's grid
+
+
+class RenderSession:
+    """One fused render of two plans on a backend, numpy in and numpy out, through nerf_pytorch_amd.render_call.RenderCall: ONE
+    workspace and ONE set of maps (both NaN-filled until written), which stay, so that any number of forwards, spread launches and
+    backwards can run over them and their regions can be read and overwritten in between.
+    opt: dict(num_coarse, num_fine[, perturb (default True), lindisp, white_background, noise_std]); rand: the four draws by name;
+    layout: 0 inference, 1 training (one set of backward buffers per net), 2 training (shared); ws: a workspace to run in."""
+
+    def __init__(self, b, pc, pf, packed_c, packed_f, rays, opt, rand=None, layout=1, seed=0, ray_offset=0, ws=None):
+        rand = rand or {}
+        self.b, self.pc, self.pf, self.layout = b, pc, pf, layout
+        self.n, self.stride = rays.shape
+        self.nc, self.nf = opt["num_coarse"], opt["num_fine"]
+        self.cfg = L.RenderCfg(self.nc, self.nf, int(bool(opt.get("perturb", True))), int(bool(opt.get("lindisp", False))),
+                               int(bool(opt.get("white_background", False))), float(opt.get("noise_std", 0.0)), self.stride)
+        self.wsb = RenderCall.workspace_bytes(b.lib, pc, pf, self.cfg, self.n, layout)
+        self.ws = b.empty((self.wsb // 4 + 1,)) if ws is None else ws
+        self.bufs = {k: b.empty((self.n, 3) if k.startswith("rgb") else (self.n,)) for k in MAPS}
+        self.tmp = None   # (the list area of the last forward_occ)
+        # (the device arrays behind the call's addresses)
+        self._keep = [b.dev(np.ascontiguousarray(rays, np.float32)), b.dev(b._linspace01(self.nc)),
+                      b.dev(b._linspace01(self.nf)) if self.nf > 0 else None, packed_c, packed_f]
+        self._draws = [b.devopt(rand.get(k)) for k in ("t_rand", "noise_coarse", "u", "noise_fine")]
+        self.call = RenderCall(b.lib, pc, pf, self.cfg, b.ptr(self._keep[0]), self.n, b.ptr(packed_c), b.p(packed_f), b.ptr(self._keep[1]),
+                               b.p(self._keep[2]), [b.p(d) for d in self._draws], seed, ray_offset, layout, b.ptr(self.ws), self.wsb)
+
+    # -- forwards --
+    def forward(self, parts=None):
+        """nerfhip_render_fwd_parts (parts=None: nerfhip_render_fwd)."""
+        self.call.forward([self.b.ptr(self.bufs[k]) for k in MAPS], parts, self.b.stream())
+
+    def _occ(self, grid_c, grid_f, tmp_words):
+        tb = RenderCall.occ_tmp_bytes(self.b.lib, self.cfg, self.n)
+        assert tb % 4 == 0
+        words = tb // 4 if tmp_words is None else tmp_words
+        self.tmp = self.b.dev(np.full(max(words, 1), -7, np.int32))
+        gf = grid_c if grid_f is SAME else grid_f   # (None: a NULL pointer)
+        return (None if grid_c is None else grid_c.c, None if gf is None else gf.c, self.b.ptr(self.tmp), words * 4)
+
+    def forward_occ(self, grid_c, grid_f=SAME, parts=BOTH, tmp_words=None):
+        """The culled forward of the layout (nerfhip_render_fwd_occ / nerfhip_render_fwd_occ_train) into a fresh list area of -7s;
+        grids: objects with the OccGrid struct as `.c`."""
+        return self.call.forward([self.b.ptr(self.bufs[k]) for k in MAPS], parts, self.b.stream(), self._occ(grid_c, grid_f, tmp_words))
+
+    def refused_forward_occ(self, entry, grid_c, grid_f=SAME, parts=BOTH, training=None, tmp_words=None):
+        """The return code of a RAW call of `entry` ("render_fwd_occ" / "render_fwd_occ_train") that is expected to be refused: every
+        argument written out, `training` whatever the case asks for (None: the layout)."""
+        b, c = self.b, self.call
+        gc, gf, tmp, tb = self._occ(grid_c, grid_f, tmp_words)
+        rr, ro = L.RenderRand(*c.rand), L.RenderOut(*[b.ptr(self.bufs[k]) for k in MAPS])
+        return getattr(b.lib._dll, "nerfhip_" + entry)(
+            self.pc, self.pf, C.byref(self.cfg), c.rays, self.n, b.ptr(self._keep[3]), b.p(self._keep[4]), c.t_vals, c.u_det, C.byref(rr),
+            c.seed, c.ray_offset, C.byref(ro), b.ptr(self.ws), self.wsb, self.layout if training is None else training, parts,
+            None if gc is None else C.byref(gc), None if gf is None else C.byref(gf), tmp, tb, b.stream())
+
+    def counts(self):
+        """{kept, total} of the coarse, then of the fine pass of the last forward_occ."""
+        return tuple(int(v) for v in np.ascontiguousarray(self.b.host(self.tmp)).view(np.int32)[:4])
+
+    # -- maps and workspace regions --
+    def maps(self):
+        return {k: np.array(self.b.host(v), copy=True) for k, v in self.bufs.items()}
+
+    def set_map(self, name, value):
+        self.bufs[name][...] = self.b.dev(np.ascontiguousarray(value, np.float32))
+
+    def _words(self, name):
+        off, nb = self.call.region(name)
+        assert nb > 0 and off % 4 == 0 and off + nb <= self.wsb, (name, off, nb)
+        return off // 4, (off + nb) // 4
+
+    def region(self, name):
+        """A region of the workspace ("z_coarse", "raw_fine", "bwd_g_raw_coarse", ...) -> host [n, S] (raw rows: [n, S, 4])."""
+        lo, hi = self._words(name)
+        flat = np.array(self.b.host(self.ws[lo:hi]), copy=True)
+        return flat.reshape(self.n, -1, 4) if "raw" in name else flat.reshape(self.n, -1)
+
+    def set_region(self, name, value):
+        lo, hi = self._words(name)
+        self.ws[lo:hi] = self.b.dev(np.ascontiguousarray(value, np.float32).reshape(-1))
+
+    # -- spread, backwards --
+    def spread(self, fine, scale=1.0, g_loss=None, want_g=True):
+        """nerfhip_spread_loss on the pass's regions of the workspace -> (loss host [n], g_weights device [n, S] or None)."""
+        b = self.b
+        lo, gw, dg = b.empty((self.n,)), (b.empty((self.n, self.nc + (self.nf if fine else 0))) if want_g else None), b.devopt(g_loss)
+        self.call.spread(fine, float(scale), b.p(dg), b.ptr(lo), b.p(gw), b.stream())
+        return b.host(lo), gw
+
+    def _cot(self, g):
+        """g: (g_rgb_coarse, g_rgb_fine) or six (..., g_acc_coarse, g_acc_fine, g_depth_coarse, g_depth_fine), host arrays or None ->
+        the device arrays in RenderCotangents' order."""
+        g = tuple(g) + (None,) * (6 - len(g))
+        d = [self.b.devopt(v) for v in g]
+        return [d[0], d[2], d[4], d[1], d[3], d[5]]
+
+    def _rays_args(self, params, tmp_bytes):
+        b = self.b
+        keep = [b.dev(params[0]), b.devopt(params[1]), b.empty((tmp_bytes // 4 + 4,)), b.empty((self.n, self.stride))]
+        return keep, (b.ptr(keep[0]), b.p(keep[1]), b.ptr(keep[2]), tmp_bytes, b.ptr(keep[3]))
+
+    def backward(self, g, gw=None, entry="parts", parts=BOTH, params=None):
+        """One backward entry point over the forward in the workspace.  g: the cotangents (see _cot); gw: None or (coarse, fine) DEVICE
+        weight cotangents; entry: "parts", "parts_w", "rays", "rays_w" (the last two with params = the two flat vectors: also g_rays) or
+        "rgb" (nerfhip_render_bwd).  -> dict(g_params_coarse, g_params_fine[, g_rays])."""
+        b = self.b
+        cot = self._cot(g)
+        gpc = b.empty((b.lib.plan_num_params(self.pc),))
+        gpf = b.empty((b.lib.plan_num_params(self.pf),)) if self.nf > 0 else None
+        g_params, out = (b.ptr(gpc), b.p(gpf)), {}
+        if self.nf == 0:
+            parts &= ~L.PART_FINE
+        if entry == "rgb":
+            self.call.backward_rgb(b.p(cot[0]), b.p(cot[3]), g_params, b.stream())
+        else:
+            assert entry.endswith("_w") or gw is None
+            g_weights = [b.p(w) for w in (gw or (None, None))] if entry.endswith("_w") else None
+            keep, rays = self._rays_args(params, RenderCall.tmp_bytes(b.lib, self.pc, self.pf, self.cfg, self.n)[0]) if entry.startswith("rays") else (None, None)
+            self.call.backward([b.p(c) for c in cot], g_params, parts, b.stream(), g_weights, rays)
+            if rays is not None:
+                out["g_rays"] = b.host(keep[3])
+        out.update(g_params_coarse=np.array(b.host(gpc), copy=True), g_params_fine=None if gpf is None else np.array(b.host(gpf), copy=True))
+        return out
+
+    def grad_rays(self, g, params, parts=BOTH):
+        """nerfhip_render_grad_rays -> g_rays (host)."""
+        b = self.b
+        cot = self._cot(g)
+        keep, rays = self._rays_args(params, RenderCall.tmp_bytes(b.lib, self.pc, self.pf, self.cfg, self.n)[1])
+        self.call.backward([b.p(c) for c in cot], None, parts, b.stream(), None, rays, frozen=True)
+        return b.host(keep[3])
+
+    def kept(self, net):
+        """(kept, total) sample points of the last backward of net "coarse" / "fine" that ran over a list (layout 1)."""
+        assert self.layout == 1
+        so = self.call.stats_offset(net) // 4
+        return tuple(int(v) for v in np.ascontiguousarray(self.b.host(self.ws[so:so + 2])).view(np.int32))
+
+
+class Rendered(RenderSession):
+    """A RenderSession whose whole forward has run: `out` holds the maps of the last forward()."""
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.forward()
+
+    def forward(self, parts=None):
+        super().forward(parts)
+        self.out = self.maps()

@@ -32,6 +32,7 @@ import ctypes as C
 import numpy as np
 import torch
 
+import backends as BK
 import nerf_oracle as O
 import nerf_pytorch_amd._lib as L
 import parity_cases as PC
@@ -42,31 +43,10 @@ BOTH = L.PART_COARSE | L.PART_FINE
 
 
 # ---- the launches -----------------------------------------------------------------------------------------------------------------
-class Rendered:
-    """A training forward of two plans whose workspace stays, so that any number of backwards can run over it.
+class Rendered(BK.Rendered):
+    """A training forward of two plans whose workspace stays, so that any number of backwards can run over it (backends.RenderSession:
+    grad_rays, backward, region, kept), and the cotangents of this file's losses.
     layout: 1 (one set of backward buffers per net) or 2 (shared: calls carry NERFHIP_PART_SHARED_BWD)."""
-
-    def __init__(self, b, pc, pf, packed_c, packed_f, rays, opt, rand=None, layout=1, seed=0, ray_offset=0):
-        rand = rand or {}
-        self.b, self.pc, self.pf, self.packed_c, self.packed_f = b, pc, pf, packed_c, packed_f
-        self.n, self.stride = rays.shape
-        n, nc, nf = self.n, opt["num_coarse"], opt["num_fine"]
-        self.nc, self.nf, self.layout, self.seed, self.ray_offset = nc, nf, layout, seed, ray_offset
-        self.cfg = L.RenderCfg(nc, nf, int(bool(opt.get("perturb", True))), int(bool(opt.get("lindisp", False))),
-                               int(bool(opt.get("white_background", False))), float(opt.get("noise_std", 0.0)), self.stride)
-        self.rays = b.dev(np.ascontiguousarray(rays, np.float32))
-        t_vals, u_det = b.dev(b._linspace01(nc)), b.dev(b._linspace01(nf))
-        self._keep = [b.devopt(rand.get(k)) for k in ("t_rand", "noise_coarse", "u", "noise_fine")]
-        self.rr = L.RenderRand(*[b.p(k) for k in self._keep])
-        names = ("rgb_coarse", "disp_coarse", "acc_coarse", "depth_coarse", "rgb_fine", "disp_fine", "acc_fine", "depth_fine")
-        bufs = {k: b.empty((n, 3) if k.startswith("rgb") else (n,)) for k in names}
-        ro = L.RenderOut(*[b.ptr(bufs[k]) for k in names])
-        self.wsb = b.lib.render_workspace_bytes(pc, pf, C.byref(self.cfg), n, layout)
-        assert self.wsb >= 0, b.lib.last_error()
-        self.ws = b.empty((self.wsb // 4 + 1,))
-        b.lib.render_fwd(pc, pf, C.byref(self.cfg), b.ptr(self.rays), n, b.ptr(packed_c), b.ptr(packed_f), b.ptr(t_vals), b.ptr(u_det),
-                         C.byref(self.rr), seed, ray_offset, C.byref(ro), b.ptr(self.ws), self.wsb, layout, b.stream())
-        self.out = {k: b.host(v) for k, v in bufs.items()}
 
     def mse_cotangents(self, target):
         _, gc, gf = self.b.mse_loss(self.out["rgb_coarse"], self.out["rgb_fine"], np.ascontiguousarray(target, np.float32))
@@ -80,61 +60,9 @@ class Rendered:
         return (gc, gf, np.float32(2.0 * ALL_COT["acc_coarse"]) * self.out["acc_coarse"] / n, np.float32(2.0 * ALL_COT["acc_fine"]) * self.out["acc_fine"] / n,
                 np.float32(ALL_COT["depth_coarse"]) * one / n, np.float32(ALL_COT["depth_fine"]) * one / n)
 
-    def region(self, name):
-        """A per-sample intermediate the forward left in the workspace ("z_coarse", "z_fine", ...: nerfhip_render_workspace_region) -> host [n, -1]."""
-        b = self.b
-        off, nb = C.c_int64(), C.c_int64()
-        b.lib.render_workspace_region(self.pc, self.pf, C.byref(self.cfg), self.n, self.layout, name.encode(), C.byref(off), C.byref(nb))
-        assert nb.value > 0 and off.value % 4 == 0 and off.value + nb.value <= self.wsb, (name, off.value, nb.value)
-        return np.array(b.host(self.ws[off.value // 4:(off.value + nb.value) // 4]), copy=True).reshape(self.n, -1)
-
-    def _cot(self, g):
-        """g: (g_rgb_coarse, g_rgb_fine) or the six of all_cotangents -> (RenderCotangents, the device buffers it points into)."""
-        b = self.b
-        g = tuple(g) + (None,) * (6 - len(g))
-        d = [b.devopt(None if v is None else np.ascontiguousarray(v, np.float32)) for v in g]
-        return L.RenderCotangents(b.p(d[0]), b.p(d[2]), b.p(d[4]), b.p(d[1]), b.p(d[3]), b.p(d[5])), d
-
-    def _head(self):
-        b = self.b
-        return (self.pc, self.pf, C.byref(self.cfg), b.ptr(self.rays), self.n, b.ptr(self.packed_c), b.ptr(self.packed_f), C.byref(self.rr),
-                self.seed, self.ray_offset)
-
-    def grad_rays(self, g, params, parts=BOTH):
-        """nerfhip_render_grad_rays -> g_rays (host).  g: two colour cotangents, or the six of all_cotangents."""
-        b = self.b
-        fc, ff = b.dev(params[0]), b.dev(params[1])
-        cot, _keep = self._cot(g)
-        tb = b.lib.render_grad_rays_tmp_bytes(self.pc, self.pf, C.byref(self.cfg), self.n)
-        assert tb >= 0
-        tmp, g_rays = b.empty((tb // 4 + 4,)), b.empty((self.n, self.stride))
-        b.lib.render_grad_rays(*self._head(), C.byref(cot), b.ptr(self.ws), self.wsb, parts | (L.PART_SHARED_BWD if self.layout == 2 else 0),
-                               b.ptr(fc), b.ptr(ff), b.ptr(tmp), tb, b.ptr(g_rays), b.stream())
-        return b.host(g_rays)
-
     def bwd_rays(self, g, params):
         """nerfhip_render_bwd_rays (the trainable path: parameter gradients too) -> g_rays (host).  g: as grad_rays."""
-        b = self.b
-        fc, ff = b.dev(params[0]), b.dev(params[1])
-        cot, _keep = self._cot(g)
-        gpc, gpf = b.empty((b.lib.plan_num_params(self.pc),)), b.empty((b.lib.plan_num_params(self.pf),))
-        tb = b.lib.render_bwd_rays_tmp_bytes(self.pc, self.pf, C.byref(self.cfg), self.n)
-        tmp, g_rays = b.empty((tb // 4 + 1,)), b.empty((self.n, self.stride))
-        b.lib.render_bwd_rays(*self._head(), C.byref(cot), b.ptr(self.ws), self.wsb, b.ptr(gpc), b.ptr(gpf),
-                              BOTH | (L.PART_SHARED_BWD if self.layout == 2 else 0), b.ptr(fc), b.ptr(ff), b.ptr(tmp), tb, b.ptr(g_rays), b.stream())
-        return b.host(g_rays)
-
-    def kept(self, fine=True):
-        """(kept, total) sample points of the last compacted backward of one net (layout 1)."""
-        b = self.b
-        assert self.layout == 1
-        plan, samples = (self.pf, self.nc + self.nf) if fine else (self.pc, self.nc)
-        off, nb = C.c_int64(), C.c_int64()
-        b.lib.render_workspace_region(self.pc, self.pf, C.byref(self.cfg), self.n, 1, b"bwd_scratch_fine" if fine else b"bwd_scratch_coarse",
-                                      C.byref(off), C.byref(nb))
-        so = b.lib.plan_bwd_stats_offset(plan, self.n * samples)
-        w = b.host(self.ws[(off.value + so) // 4:(off.value + so) // 4 + 2])
-        return tuple(int(v) for v in np.ascontiguousarray(w).view(np.int32))
+        return self.backward(g, entry="rays", params=params)["g_rays"]
 
 
 # ---- the problems -------------------------------------------------------------------------------------------------------------------
@@ -386,7 +314,7 @@ def case_modes_give_the_same_bits(b, name="default4x128", n=13, nc=8, nf=8, mode
             again = r.grad_rays(g, (fc, ff))                      # (two calls over one forward)
             assert np.array_equal(WC.bits(again), WC.bits(got[mode])), (which, mode)
             if b.lib.plan_bwd_compaction(pf) in (1, 2):
-                kept, total = r.kept()
+                kept, total = r.kept("fine")
                 frac = 1.0 - kept / float(total)
                 PC.note("grad_rays_modes_%s_%s" % (name, b.name), **{"zero_fraction_" + which: frac})
                 assert total == n * (nc + nf) and lo <= frac <= hi, (which, kept, total)
@@ -439,10 +367,10 @@ def case_refusals(b, name="default4x128", n=5, nc=8, nf=8):
     tb = b.lib.render_grad_rays_tmp_bytes(pc, pf, C.byref(r.cfg), n)
     assert tb > 0 and b.lib.render_grad_rays_tmp_bytes(pc, pf, C.byref(r.cfg), 0) >= 0 and b.lib.render_grad_rays_tmp_bytes(pc, pf, C.byref(r.cfg), -1) == -1
     tmp, g_rays = b.empty((tb // 4 + 4,)), b.empty((n, r.stride))
-    cot = L.RenderCotangents(b.ptr(gc), None, None, b.ptr(gf), None, None)
+    cot, rr = L.RenderCotangents(b.ptr(gc), None, None, b.ptr(gf), None, None), L.RenderRand(*r.call.rand)
 
     def call(parts=BOTH, params=(b.ptr(dfc), b.ptr(dff)), tmp_p=b.ptr(tmp), tmp_b=tb, out=b.ptr(g_rays), plans_=(pc, pf), packs=(kc, kf), rays_n=n):
-        head = (plans_[0], plans_[1], C.byref(r.cfg), b.ptr(r.rays), rays_n, b.ptr(packs[0]), b.ptr(packs[1]), C.byref(r.rr), 0, 0)
+        head = (plans_[0], plans_[1], C.byref(r.cfg), r.call.rays, rays_n, b.ptr(packs[0]), b.ptr(packs[1]), C.byref(rr), 0, 0)
         return raw(*head, C.byref(cot), b.ptr(r.ws), r.wsb, parts, params[0], params[1], tmp_p, tmp_b, out, b.stream())
 
     assert call() == 0

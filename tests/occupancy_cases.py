@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import torch
 
+import backends as BK
 import nerf_oracle as O
 import nerf_pytorch_amd._lib as L
 import parity_cases as P
@@ -112,54 +113,29 @@ def occ_mark(b, grid, rays, z):
     return b.host(flags).reshape(n, S)
 
 
-SAME = object()
+SAME = BK.SAME
 
 
 def render_occ(b, plan_c, plan_f, packed_c, packed_f, rays, opt, grid_c, grid_f=SAME, rand=None, parts=3, ws=None,
                raise_on_error=True, training=0, tmp_words=None):
-    """nerfhip_render_fwd_occ as Backend.render drives nerfhip_render_fwd.  Returns the eight maps, the four count words, the regions
-    the passes left in the workspace and the last pass's list."""
-    rand = rand or {}
-    n, stride = rays.shape
-    nc, nf = opt["num_coarse"], opt["num_fine"]
-    cfg = L.RenderCfg(nc, nf, int(bool(opt.get("perturb", False))), int(bool(opt.get("lindisp", False))),
-                      int(bool(opt.get("white_background", False))), float(opt.get("noise_std", 0.0)), stride)
-    dr = b.dev(np.ascontiguousarray(rays, f32))
-    dt = b.dev(b._linspace01(nc))
-    dud = b.dev(b._linspace01(nf)) if nf > 0 else None
-    keep = [b.devopt(rand.get(k)) for k in ("t_rand", "noise_coarse", "u", "noise_fine")]
-    rr = L.RenderRand(*[b.p(k) for k in keep])
-    names = ("rgb_coarse", "disp_coarse", "acc_coarse", "depth_coarse", "rgb_fine", "disp_fine", "acc_fine", "depth_fine")
-    bufs = {k: b.empty((n, 3) if k.startswith("rgb") else (n,)) for k in names}
-    ro = L.RenderOut(*[b.ptr(bufs[k]) for k in names])
-    wsb = b.lib.render_workspace_bytes(plan_c, plan_f, C.byref(cfg), n, 0)
-    assert wsb >= 0, b.lib.last_error()
-    ws = b.empty((wsb // 4 + 1,)) if ws is None else ws
-    tb = b.lib.render_occ_tmp_bytes(C.byref(cfg), n)
-    assert tb >= 0 and tb % 4 == 0
-    words = tb // 4 if tmp_words is None else tmp_words
-    tmp = b.dev(np.full(max(words, 1), -7, np.int32))
-    gf = grid_c if grid_f is SAME else grid_f  # (None: a NULL pointer)
-    args = (plan_c, plan_f, C.byref(cfg), b.ptr(dr), n, b.ptr(packed_c), b.p(packed_f), b.ptr(dt), b.p(dud), C.byref(rr), 0, 0,
-            C.byref(ro), b.ptr(ws), wsb, int(training), parts, C.byref(grid_c.c) if grid_c is not None else None,
-            C.byref(gf.c) if gf is not None else None, b.ptr(tmp), words * 4, b.stream())
-    if not raise_on_error:  # (a refusal: the return code, and what the call left in its outputs)
-        rc = b.lib._dll.nerfhip_render_fwd_occ(*args)
-        return rc, {k: b.host(v) for k, v in bufs.items()}, b.host(tmp)
-    b.lib.render_fwd_occ(*args)
-    out = {k: b.host(v) for k, v in bufs.items()}
-    t = np.ascontiguousarray(b.host(tmp)).view(np.int32)
-    out["counts"] = tuple(int(v) for v in t[:4])
+    """nerfhip_render_fwd_occ as Backend.render drives nerfhip_render_fwd (backends.RenderSession in the inference layout).  Returns the
+    eight maps, the four count words, the regions the passes left in the workspace and the last pass's list."""
+    s = BK.RenderSession(b, plan_c, plan_f, packed_c, packed_f, rays, opt, rand, 0, ws=ws)
+    n, nc, nf = s.n, s.nc, s.nf
+    if not raise_on_error:  # (a refusal: the return code of a raw call, and what the call left in its outputs)
+        rc = s.refused_forward_occ("render_fwd_occ", grid_c, grid_f, parts, training, tmp_words)
+        return rc, s.maps(), b.host(s.tmp)
+    s.forward_occ(grid_c, grid_f, parts, tmp_words)
+    out = s.maps()
+    t = np.ascontiguousarray(b.host(s.tmp)).view(np.int32)
+    out["counts"] = s.counts()
     m_max = n * (nc + nf)
     c_words = 16 * (-(-(-(-m_max // 2048)) // 16))
     last_kept = out["counts"][2] if (nf > 0 and parts & 2) else out["counts"][0]
     out["list"] = t[16 + c_words:16 + c_words + last_kept].copy()
     out["list_padding"] = t[16 + c_words + last_kept:16 + c_words + ((last_kept + 127) & ~127)].copy()
     for name in ("z_coarse", "raw_coarse", "weights_coarse") + (("z_fine", "raw_fine") if nf > 0 else ()):
-        off, nb = C.c_int64(), C.c_int64()
-        b.lib.render_workspace_region(plan_c, plan_f, C.byref(cfg), n, 0, name.encode(), C.byref(off), C.byref(nb))
-        flat = b.host(ws[off.value // 4:(off.value + nb.value) // 4])
-        out[name] = flat.reshape(n, -1, 4) if name.startswith("raw") else flat.reshape(n, -1)
+        out[name] = s.region(name)
     return out
 
 
@@ -290,7 +266,7 @@ def case_render_all_ones(b, net, arith, n=19, nc=8, nf=5):
         for k in MAPS + ("raw_coarse", "raw_fine", "z_fine"):
             same(got[k], dense[k], "all-ones %s white=%s" % (k, white))
         # the two parts one after the other, on one workspace
-        ws = b.empty((b.lib.render_workspace_bytes(pc, pf, C.byref(L.RenderCfg(nc, nf, 1, 0, int(white), 0.4, rays.shape[1])), n, 0) // 4 + 1,))
+        ws = b.empty((BK.RenderCall.workspace_bytes(b.lib, pc, pf, L.RenderCfg(nc, nf, 1, 0, int(white), 0.4, rays.shape[1]), n, 0) // 4 + 1,))
         first = render_occ(b, pc, pf, packed_c, packed_f, rays.numpy(), opt, grid, rand=rnp, parts=1, ws=ws)
         second = render_occ(b, pc, pf, packed_c, packed_f, rays.numpy(), opt, grid, rand=rnp, parts=2, ws=ws)
         for k in MAPS[:4]:

@@ -6,6 +6,7 @@ import ctypes as C
 
 import numpy as np
 
+import backends as BK
 import nerf_pytorch_amd._lib as L
 import occupancy_cases as OC
 import parity_cases as P
@@ -31,91 +32,25 @@ def has_mode(b, plan, mode):
     return ok
 
 
-class Step:
+class Step(BK.RenderSession):
     """One training step's buffers on a backend, layout 1 (one set of backward buffers per net): the forward entry points write into
-    ONE workspace and ONE set of maps, whose regions can be read and overwritten between the calls."""
-
-    def __init__(self, b, pc, pf, packed_c, packed_f, rays, opt, rand=None, layout=1):
-        self.b, self.pc, self.pf, self.packed_c, self.packed_f, self.layout = b, pc, pf, packed_c, packed_f, layout
-        rand = rand or {}
-        self.n, stride = rays.shape
-        self.nc, self.nf = opt["num_coarse"], opt["num_fine"]
-        self.opt, self.rand, self.rays = opt, rand, np.ascontiguousarray(rays, f32)
-        self.cfg = L.RenderCfg(self.nc, self.nf, int(bool(opt.get("perturb", False))), int(bool(opt.get("lindisp", False))),
-                               int(bool(opt.get("white_background", False))), float(opt.get("noise_std", 0.0)), stride)
-        self.dr = b.dev(self.rays)
-        self.dt = b.dev(b._linspace01(self.nc))
-        self.dud = b.dev(b._linspace01(self.nf)) if self.nf > 0 else None
-        self.keep = [b.devopt(rand.get(k)) for k in ("t_rand", "noise_coarse", "u", "noise_fine")]
-        self.rr = L.RenderRand(*[b.p(k) for k in self.keep])
-        self.bufs = {k: b.empty((self.n, 3) if k.startswith("rgb") else (self.n,)) for k in MAPS}
-        self.ro = L.RenderOut(*[b.ptr(self.bufs[k]) for k in MAPS])
-        self.wsb = b.lib.render_workspace_bytes(pc, pf, C.byref(self.cfg), self.n, layout)
-        assert self.wsb >= 0, b.lib.last_error()
-        self.ws = b.empty((self.wsb // 4 + 1,))
-        self.tb = b.lib.render_occ_tmp_bytes(C.byref(self.cfg), self.n)
-        self.tmp = None
-
-    def _head(self):
-        b = self.b
-        return (self.pc, self.pf, C.byref(self.cfg), b.ptr(self.dr), self.n, b.ptr(self.packed_c), b.p(self.packed_f), b.ptr(self.dt),
-                b.p(self.dud), C.byref(self.rr), 0, 0, C.byref(self.ro), b.ptr(self.ws), self.wsb)
-
-    def fwd(self, parts=3):
-        self.b.lib.render_fwd_parts(*self._head(), self.layout, parts, self.b.stream())
+    ONE workspace and ONE set of maps, whose regions can be read and overwritten between the calls (backends.RenderSession)."""
+    fwd = BK.RenderSession.forward
 
     def fwd_occ(self, grid_c, grid_f=OC.SAME, parts=3, training=None, tmp_words=None, check=True):
-        """nerfhip_render_fwd_occ_train; returns the code (check=False: a refusal is the caller's to look at)."""
-        b = self.b
-        words = self.tb // 4 if tmp_words is None else tmp_words
-        self.tmp = b.dev(np.full(max(words, 1), -7, np.int32))
-        gf = grid_c if grid_f is OC.SAME else grid_f
-        args = self._head() + (self.layout if training is None else training, parts, C.byref(grid_c.c) if grid_c is not None else None,
-                               C.byref(gf.c) if gf is not None else None, b.ptr(self.tmp), words * 4, b.stream())
+        """nerfhip_render_fwd_occ_train; returns the code (check=False: a refusal is the caller's to look at, from a raw call)."""
         if check:
-            return b.lib.render_fwd_occ_train(*args)
-        return b.lib._dll.nerfhip_render_fwd_occ_train(*args)
+            return self.forward_occ(grid_c, grid_f, parts, tmp_words)
+        return self.refused_forward_occ("render_fwd_occ_train", grid_c, grid_f, parts, training, tmp_words)
 
-    def counts(self):
-        return tuple(int(v) for v in np.ascontiguousarray(self.b.host(self.tmp)).view(np.int32)[:4])
-
-    def maps(self):
-        return {k: np.array(self.b.host(v), copy=True) for k, v in self.bufs.items()}
-
-    def _region(self, name):
-        off, nb = C.c_int64(), C.c_int64()
-        self.b.lib.render_workspace_region(self.pc, self.pf, C.byref(self.cfg), self.n, self.layout, name.encode(), C.byref(off), C.byref(nb))
-        return off.value // 4, (off.value + nb.value) // 4
-
-    def region(self, name):
-        lo, hi = self._region(name)
-        flat = np.array(self.b.host(self.ws[lo:hi]), copy=True)
-        return flat.reshape(self.n, -1, 4) if name.startswith("raw") else flat.reshape(self.n, -1)
-
-    def set_region(self, name, value):
-        lo, hi = self._region(name)
-        self.ws[lo:hi] = self.b.dev(np.ascontiguousarray(value, f32).reshape(-1))
-
-    def set_map(self, name, value):
-        self.bufs[name][...] = self.b.dev(np.ascontiguousarray(value, f32))
-
-    def bwd(self, g_c, g_f):
-        """nerfhip_render_bwd_parts of both nets on the step's workspace: the two flat gradients and each net's {kept, total}."""
-        b = self.b
-        gc, gf = b.dev(np.ascontiguousarray(g_c, f32)), b.devopt(g_f)
-        gpc = b.empty((b.lib.plan_num_params(self.pc),))
-        gpf = b.empty((b.lib.plan_num_params(self.pf),)) if self.nf > 0 else None
-        cot = L.RenderCotangents(b.ptr(gc), None, None, b.p(gf), None, None)
-        b.lib.render_bwd_parts(self.pc, self.pf, C.byref(self.cfg), b.ptr(self.dr), self.n, b.ptr(self.packed_c), b.p(self.packed_f),
-                               C.byref(self.rr), 0, 0, C.byref(cot), b.ptr(self.ws), self.wsb, b.ptr(gpc), b.p(gpf),
-                               L.PART_COARSE | (L.PART_FINE if self.nf > 0 else 0), b.stream())
-        out = dict(g_coarse=np.array(b.host(gpc), copy=True), g_fine=np.array(b.host(gpf), copy=True) if gpf is not None else None)
-        for name, plan, samples in (("coarse", self.pc, self.nc), ("fine", self.pf, self.nc + self.nf)):
-            if plan is None or not b.lib.plan_bwd_compaction(plan) in (1, 2, 4):
-                continue
-            lo, _ = self._region("bwd_scratch_" + name)
-            so = lo + b.lib.plan_bwd_stats_offset(plan, self.n * samples) // 4
-            out["kept_" + name] = tuple(int(v) for v in np.ascontiguousarray(b.host(self.ws[so:so + 2])).view(np.int32))
+    def bwd(self, g_c, g_f, gw=None):
+        """nerfhip_render_bwd_parts (gw, the two device weight cotangents: _parts_w) of both nets on the step's workspace: the two flat
+        gradients and each net's {kept, total}."""
+        r = self.backward((g_c, g_f), gw, entry="parts" if gw is None else "parts_w")
+        out = dict(g_coarse=r["g_params_coarse"], g_fine=r["g_params_fine"])
+        for name, plan in (("coarse", self.pc), ("fine", self.pf)):
+            if plan is not None and self.b.lib.plan_bwd_compaction(plan) in (1, 2, 4):
+                out["kept_" + name] = self.kept(name)
         return out
 
 

@@ -19,11 +19,10 @@ Bounds of this file, and where they come from:
                     the formula: up to 4.24 and 6.26 x 2^-24), and the most the kernel exceeds 2 x the formula's error of its own case
                     by -- what the floor has to cover -- is 0.46 x 2^-24 (`loss`, n = 5, S = 129).
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
+import backends as BK
 import nerf_oracle as O
 import nerf_pytorch_amd._lib as L
 import occupancy_cases as OC
@@ -252,92 +251,9 @@ RENDER_SHAPES = ((48, 8, 8), (150, 13, 5))
 LAMBDA = (0.02, 0.01)   # (coarse, fine) weights of the spread term in the render cases: mip-NeRF 360's 0.01 and twice that
 
 
-class RenderW:
-    """One training forward of two nets on a backend and the backward entry points over it, with the spread kernel reading the forward's
-    own raw rows and depths in the workspace.  layout: 1 (one set of backward buffers per net) or 2 (shared)."""
-
-    def __init__(self, b, pc, pf, packed_c, packed_f, rays, opt, rand, layout=1):
-        self.b, self.pc, self.pf, self.packed_c, self.packed_f, self.layout = b, pc, pf, packed_c, packed_f, layout
-        self.n, self.stride = rays.shape
-        self.nc, self.nf = opt["num_coarse"], opt["num_fine"]
-        self.noise_std = float(opt.get("noise_std", 0.0))
-        self.cfg = L.RenderCfg(self.nc, self.nf, int(bool(opt.get("perturb", True))), 0, int(bool(opt.get("white_background", False))),
-                               self.noise_std, self.stride)
-        self.rays = b.dev(np.ascontiguousarray(rays, f32))
-        self.t_vals, self.u_det = b.dev(b._linspace01(self.nc)), b.dev(b._linspace01(self.nf))
-        self._keep = [b.devopt(rand.get(k)) for k in ("t_rand", "noise_coarse", "u", "noise_fine")]
-        self.rr = L.RenderRand(*[b.p(k) for k in self._keep])
-        self.wsb = b.lib.render_workspace_bytes(pc, pf, C.byref(self.cfg), self.n, layout)
-        assert self.wsb >= 0, b.lib.last_error()
-        self.ws = b.empty((self.wsb // 4 + 1,))
-        self.forward()
-
-    def forward(self):
-        b = self.b
-        names = ("rgb_coarse", "disp_coarse", "acc_coarse", "depth_coarse", "rgb_fine", "disp_fine", "acc_fine", "depth_fine")
-        bufs = {k: b.empty((self.n, 3) if k.startswith("rgb") else (self.n,)) for k in names}
-        ro = L.RenderOut(*[b.ptr(bufs[k]) for k in names])
-        b.lib.render_fwd(self.pc, self.pf, C.byref(self.cfg), b.ptr(self.rays), self.n, b.ptr(self.packed_c), b.ptr(self.packed_f),
-                         b.ptr(self.t_vals), b.ptr(self.u_det), C.byref(self.rr), 0, 0, C.byref(ro), b.ptr(self.ws), self.wsb, self.layout,
-                         b.stream())
-        self.out = {k: b.host(v) for k, v in bufs.items()}
-
-    def _region(self, name):
-        off, nb = C.c_int64(), C.c_int64()
-        self.b.lib.render_workspace_region(self.pc, self.pf, C.byref(self.cfg), self.n, self.layout, name.encode(), C.byref(off), C.byref(nb))
-        assert nb.value > 0 and off.value % 4 == 0 and off.value + nb.value <= self.wsb, (name, off.value, nb.value)
-        return off.value, nb.value
-
-    def region(self, name):
-        off, nb = self._region(name)
-        flat = np.array(self.b.host(self.ws[off // 4:(off + nb) // 4]), copy=True)
-        return flat.reshape(self.n, -1, 4) if "raw" in name else flat.reshape(self.n, -1)
-
-    def spread(self, fine, scale=1.0, g_loss=None, want_g=True):
-        """nerfhip_spread_loss on the pass's regions of the workspace -> (loss host [n], g_weights device [n, S] or None)."""
-        b = self.b
-        tag, S = ("fine", self.nc + self.nf) if fine else ("coarse", self.nc)
-        raw, z = self._region("raw_" + tag)[0], self._region("z_" + tag)[0]
-        lo, gw, dg = b.empty((self.n,)), (b.empty((self.n, S)) if want_g else None), b.devopt(g_loss)
-        b.lib.spread_loss(b.ptr(self.ws) + raw, b.ptr(self.ws) + z, b.ptr(self.rays), self.stride, self.n, S, self.noise_std,
-                          b.p(self._keep[3 if fine else 1]), 0, 3 if fine else 1, 0, float(scale), b.p(dg), b.ptr(lo), b.p(gw), b.stream())
-        return b.host(lo), gw
-
-    def backward(self, g_rgb, gw=None, entry="parts_w", parts=BOTH, params=None):
-        """One backward entry point over the forward in the workspace.  g_rgb: (coarse, fine) host cotangents (either may be None);
-        gw: None or (coarse, fine) DEVICE weight cotangents; entry: "parts", "parts_w", "rays", "rays_w" (the last two with
-        params = the two flat vectors: also g_rays).  -> dict(g_params_coarse, g_params_fine[, g_rays])."""
-        b = self.b
-        d = [b.devopt(g) for g in g_rgb]
-        six = (b.p(d[0]), None, None, b.p(d[1]), None, None)
-        if entry.endswith("_w"):
-            gw = gw or (None, None)
-            cot = L.RenderCotangentsW(*six, b.p(gw[0]), b.p(gw[1]))
-        else:
-            assert gw is None
-            cot = L.RenderCotangents(*six)
-        gpc, gpf = b.empty((b.lib.plan_num_params(self.pc),)), b.empty((b.lib.plan_num_params(self.pf),))
-        head = (self.pc, self.pf, C.byref(self.cfg), b.ptr(self.rays), self.n, b.ptr(self.packed_c), b.ptr(self.packed_f), C.byref(self.rr), 0, 0,
-                C.byref(cot), b.ptr(self.ws), self.wsb, b.ptr(gpc), b.ptr(gpf), parts | (L.PART_SHARED_BWD if self.layout == 2 else 0))
-        out = {}
-        if entry.startswith("parts"):
-            getattr(b.lib, "render_bwd_" + entry)(*head, b.stream())
-        else:
-            fc, ff = b.dev(params[0]), b.dev(params[1])
-            tb = b.lib.render_bwd_rays_tmp_bytes(self.pc, self.pf, C.byref(self.cfg), self.n)
-            tmp, g_rays = b.empty((tb // 4 + 1,)), b.empty((self.n, self.stride))
-            getattr(b.lib, "render_bwd_" + entry)(*head, b.ptr(fc), b.ptr(ff), b.ptr(tmp), tb, b.ptr(g_rays), b.stream())
-            out["g_rays"] = b.host(g_rays)
-        out.update(g_params_coarse=b.host(gpc), g_params_fine=b.host(gpf))
-        return out
-
-    def kept(self, fine):
-        """(kept, total) sample points of the last compacted backward of one net (layout 1)."""
-        assert self.layout == 1
-        plan, samples, tag = (self.pf, self.nc + self.nf, "fine") if fine else (self.pc, self.nc, "coarse")
-        off = self._region("bwd_scratch_" + tag)[0] + self.b.lib.plan_bwd_stats_offset(plan, self.n * samples)
-        w = self.b.host(self.ws[off // 4:off // 4 + 2])
-        return tuple(int(v) for v in np.ascontiguousarray(w).view(np.int32))
+# One training forward of two nets on a backend and the backward entry points over it, with the spread kernel reading the forward's own
+# raw rows and depths in the workspace.  layout: 1 (one set of backward buffers per net) or 2 (shared).
+RenderW = BK.Rendered
 
 
 def setup(b, net, arith, seed):
@@ -484,7 +400,7 @@ def case_compacted(b, net, arith, modes, n=48, nc=8, nf=8, noise=0.6):
             out["g_params_" + tag] = got["g_params_" + tag]
             nonzero = int(r.region("bwd_g_raw_" + tag).reshape(-1, 4).any(axis=1).sum())
             if mode in (True, "recompute", "fused_compact"):
-                kept, total = r.kept(fine)
+                kept, total = r.kept(tag)
                 assert total == n * (nc + (nf if fine else 0)) and kept == nonzero and 0 < kept < total, (mode, tag, kept, nonzero, total)
             else:
                 assert 0 < nonzero < n * (nc + (nf if fine else 0))
@@ -540,35 +456,6 @@ def case_rays_w(b, net="w128", n=48, nc=8, nf=8):
 
 
 # ---- the culled step of the occupancy grid with a spread term -------------------------------------------------------------------------
-def _step_spread(s, lam):
-    """nerfhip_spread_loss of both passes over an occupancy_train_cases.Step's workspace -> the two device weight cotangents."""
-    b, out = s.b, []
-    for fine, tag, S in ((0, "coarse", s.nc), (1, "fine", s.nc + s.nf)):
-        raw, z = s._region("raw_" + tag)[0] * 4, s._region("z_" + tag)[0] * 4
-        gw, lo = b.empty((s.n, S)), b.empty((s.n,))
-        b.lib.spread_loss(b.ptr(s.ws) + raw, b.ptr(s.ws) + z, b.ptr(s.dr), s.rays.shape[1], s.n, S, float(s.opt.get("noise_std", 0.0)),
-                          b.p(s.keep[3 if fine else 1]), 0, 3 if fine else 1, 0, lam[fine] / s.n, None, b.ptr(lo), b.ptr(gw), b.stream())
-        assert (b.host(lo) >= 0).all()
-        out.append(gw)
-    return out
-
-
-def _step_bwd_w(s, g_c, g_f, gw):
-    """occupancy_train_cases.Step.bwd through nerfhip_render_bwd_parts_w."""
-    b = s.b
-    gc, gf = b.dev(np.ascontiguousarray(g_c, f32)), b.dev(np.ascontiguousarray(g_f, f32))
-    gpc, gpf = b.empty((b.lib.plan_num_params(s.pc),)), b.empty((b.lib.plan_num_params(s.pf),))
-    cot = L.RenderCotangentsW(b.ptr(gc), None, None, b.ptr(gf), None, None, b.ptr(gw[0]), b.ptr(gw[1]))
-    b.lib.render_bwd_parts_w(s.pc, s.pf, C.byref(s.cfg), b.ptr(s.dr), s.n, b.ptr(s.packed_c), b.ptr(s.packed_f), C.byref(s.rr), 0, 0,
-                             C.byref(cot), b.ptr(s.ws), s.wsb, b.ptr(gpc), b.ptr(gpf), BOTH, b.stream())
-    out = dict(g_coarse=np.array(b.host(gpc), copy=True), g_fine=np.array(b.host(gpf), copy=True))
-    for name, plan, samples in (("coarse", s.pc, s.nc), ("fine", s.pf, s.nc + s.nf)):
-        lo, _ = s._region("bwd_scratch_" + name)
-        so = lo + b.lib.plan_bwd_stats_offset(plan, s.n * samples) // 4
-        out["kept_" + name] = tuple(int(v) for v in np.ascontiguousarray(b.host(s.ws[so:so + 2])).view(np.int32))
-    return out
-
-
 def case_culled_step(b, net, arith, outside, n=21, nc=9, nf=6, noise_std=0.3, lam=(0.05, 0.05)):
     """occupancy_train_cases.case_half_empty with a spread term: arm A by hand in mode 1 (training forward, the library's own flags, the
     culled rows overwritten with the empty row, compositing again), arm B nerfhip_render_fwd_occ_train in mode 2 and (where the plan
@@ -599,9 +486,10 @@ def case_culled_step(b, net, arith, outside, n=21, nc=9, nf=6, noise_std=0.3, la
         if not fine:
             a.set_region("weights_coarse", out[3])
     want = a.maps()
-    gw_a = _step_spread(a, lam)
+    gw_a, losses = spread_cotangents(a, lam)
+    assert all((lo >= 0).all() for lo in losses)
     plain = a.bwd(want["rgb_coarse"] - tgt, want["rgb_fine"] - tgt)
-    want.update(_step_bwd_w(a, want["rgb_coarse"] - tgt, want["rgb_fine"] - tgt, gw_a))
+    want.update(a.bwd(want["rgb_coarse"] - tgt, want["rgb_fine"] - tgt, gw_a))
     assert not np.array_equal(want["g_coarse"], plain["g_coarse"]) and not np.array_equal(want["g_fine"], plain["g_fine"])
     assert want["kept_coarse"] == plain["kept_coarse"] and want["kept_fine"] == plain["kept_fine"]   # (a weight cotangent wakes no row)
     ctol = TL.bound("unit.compact_vs_dense", arith if arith == "fp32" else "f16x3_train")
@@ -611,10 +499,11 @@ def case_culled_step(b, net, arith, outside, n=21, nc=9, nf=6, noise_std=0.3, la
         s = OT.Step(b, pc, pf, packed_c, packed_f, rays, opt, rnp)
         s.fwd_occ(grid)
         got = s.maps()
-        gw = _step_spread(s, lam)
+        gw, losses = spread_cotangents(s, lam)
+        assert all((lo >= 0).all() for lo in losses)
         for i in (0, 1):
             assert np.array_equal(b.host(gw[i]), b.host(gw_a[i])), (mode, i)
-        got.update(_step_bwd_w(s, got["rgb_coarse"] - tgt, got["rgb_fine"] - tgt, gw))
+        got.update(s.bwd(got["rgb_coarse"] - tgt, got["rgb_fine"] - tgt, gw))
         for tag, plan in (("coarse", pc), ("fine", pf)):
             assert got["kept_" + tag] == want["kept_" + tag], (mode, tag, got["kept_" + tag], want["kept_" + tag])
             g, w = got["g_" + tag], want["g_" + tag]
