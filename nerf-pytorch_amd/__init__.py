@@ -10,6 +10,7 @@ from . import eval_utils, io_utils, models, occupancy  # noqa: F401
 from .cameras import CameraTable, Distortion, Exposure, Intrinsics, se3_poses  # noqa: F401
 from .cfg import AttrDict, make_options  # noqa: F401
 from .engine import TrainEngine  # noqa: F401
+from .launch_profile import LaunchProfile  # noqa: F401
 from .models import FlexibleNeRFModel  # noqa: F401
 from .occupancy import OccupancyGrid  # noqa: F401
 from .nerf_helpers import (cumprod_exclusive, get_embedding_function, get_minibatches, get_ray_bundle,  # noqa: F401

@@ -12,22 +12,13 @@ tests/test_gpu_cameras.py prints (its CAMERAS_CAPABILITY line, pytest -s) are ca
     python scripts/bench_cameras.py [--steps 30] [--warmup 5] [--timeout 240] [--out profiles/r09_cameras.json] [--capability-log LOG]
 """
 import argparse
-import json
 import os
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from bench_common import LINES, ROOT, child_spec, emit, pair_cost, pose_stack, run_specs, scrape_log, timed, write_out
+
 sys.path.insert(0, os.path.join(ROOT, "tests"))   # (the per-view torch exponential is the one the GPU test compares against)
 
-LINES = {
-    "lego_8x256": dict(H=400, W=400, focal=555.5555, nc=64, nf=128, no_ndc=True, noise=0.2, near=2.0, far=6.0, views=100,
-                       model=dict(num_layers=8, hidden_size=256, skip_connect_every=4, num_encoding_fn_xyz=10, num_encoding_fn_dir=4)),
-    "fern_4x64": dict(H=378, W=504, focal=407.5, nc=64, nf=64, no_ndc=False, noise=1.0, near=0.0, far=1.0, views=20,
-                      model=dict(num_layers=4, hidden_size=64, skip_connect_every=3, num_encoding_fn_xyz=6, num_encoding_fn_dir=4)),
-}
 TAG = "BENCH_CAMERAS_RESULT "
 
 
@@ -52,51 +43,11 @@ def _exp_batched(xi):
     return torch.cat([top, bottom], 1)
 
 
-WINDOWS = 5
-
-
-def _timed(step, steps, warmup, count_kernels=True):
-    """ms per step over WINDOWS timed windows of `steps` steps each (median, smallest, largest), and the device kernels of one step."""
-    import torch
-    for _ in range(warmup):
-        step()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(WINDOWS):
-        t0 = time.perf_counter()
-        for _ in range(steps):
-            step()
-        torch.cuda.synchronize()
-        ms.append((time.perf_counter() - t0) * 1e3 / steps)
-    ms.sort()
-    kernels = None
-    if count_kernels:
-        try:
-            from torch.profiler import ProfilerActivity, profile
-            with profile(activities=[ProfilerActivity.CUDA]) as prof:
-                step()
-                torch.cuda.synchronize()
-            kernels = sum(1 for e in prof.events() if str(e.device_type).endswith("CUDA"))
-        except Exception:
-            pass
-    return dict(ms=round(ms[len(ms) // 2], 4), ms_min=round(ms[0], 4), ms_max=round(ms[-1], 4), windows=WINDOWS, steps=steps,
-                kernels=kernels)
-
-
-def pose_stack(V, dev, z):
-    import torch
-    g = torch.Generator().manual_seed(2)
-    p = torch.eye(4).repeat(V, 1, 1)
-    p[:, :3, 3] = torch.randn(V, 3, generator=g) * 0.05
-    p[:, 2, 3] += z
-    return p.to(dev)
-
-
 def one_update(arm, V, steps, warmup):
     import torch
 
     import nerf_pytorch_amd as N
-    from test_gpu_cameras import _se3_exp as exp_one
+    from engine_scenes import se3_exp as exp_one
     dev = torch.device("cuda", 0)
     base = pose_stack(V, dev, 4.0)
     pg = torch.randn(V, 3, 4, generator=torch.Generator().manual_seed(3)).to(dev)
@@ -120,7 +71,7 @@ def one_update(arm, V, steps, warmup):
             torch.autograd.backward(poses[:, :3, :4], pg)
             opt.step()
     # (the profiler's record of the per-view loop at V = 1000, some 1.8e5 kernels, comes back cut short: not counted)
-    return _timed(step, steps, warmup, count_kernels=not (arm == "torch_loop" and V >= 1000))
+    return timed(step, steps, warmup, count_kernels=not (arm == "torch_loop" and V >= 1000))
 
 
 def one_line(name, arm, steps, warmup, rays):
@@ -142,7 +93,7 @@ def one_line(name, arm, steps, warmup, rays):
     else:
         pg = torch.empty(V, 3, 4, device=dev)
         step = lambda: eng.step_on_views(imgs, poses, H, W, w["focal"], opts, rays, pose_grads=pg)  # noqa: E731
-    res = _timed(step, steps, warmup)
+    res = timed(step, steps, warmup)
     res["views"] = V
     return res
 
@@ -152,20 +103,7 @@ def child(spec):
         res = one_update(spec["arm"], spec["V"], spec["steps"], spec["warmup"])
     else:
         res = one_line(spec["line"], spec["arm"], spec["steps"], spec["warmup"], spec["rays"])
-    print(TAG + json.dumps(res))
-
-
-def measure(spec, limit):
-    """Runs one measurement in a fresh process under `limit` seconds; returns its result, or None (and the reason) on failure."""
-    try:
-        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", json.dumps(spec)], timeout=limit, capture_output=True,
-                           text=True)
-    except subprocess.TimeoutExpired:
-        return None, "time limit of %d s" % limit
-    for ln in p.stdout.splitlines():
-        if ln.startswith(TAG):
-            return json.loads(ln[len(TAG):]), None
-    return None, "exit status %d: %s" % (p.returncode, p.stderr.strip().splitlines()[-1:] or "")
+    emit(TAG, res)
 
 
 def main():
@@ -179,7 +117,7 @@ def main():
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:
-        return child(json.loads(a.child))
+        return child(child_spec(a.child))
     out = dict(metric="camera_table_cost", rays=a.rays, steps=a.steps, pose_update={}, lines={})
     specs = []
     for V in (2, 100, 1000):
@@ -191,27 +129,14 @@ def main():
         for arm in ("pose_grads", "cameras", "pose_grads_again", "cameras_again"):
             specs.append((("lines", name, arm), dict(kind="line", line=name, arm=arm.split("_again")[0], steps=a.steps, warmup=a.warmup,
                                                      rays=a.rays)))
-    for (top, mid, arm), spec in specs:
-        res, why = measure(spec, a.timeout)
-        if res is None:
-            out["stopped_at"] = dict(measurement=[top, mid, arm], reason=why)
-            break
-        out[top].setdefault(mid, {})[arm] = res
+    run_specs(__file__, TAG, specs, out, a.timeout)
     for name, r in out["lines"].items():
         if all(k in r for k in ("cameras", "pose_grads", "cameras_again", "pose_grads_again")):
-            cam, pg = [r[k]["ms"] for k in ("cameras", "cameras_again")], [r[k]["ms"] for k in ("pose_grads", "pose_grads_again")]
-            r["cameras_cost_pct"] = round(100.0 * (sum(cam) / sum(pg) - 1.0), 2)
-            # what the same arm differs by between its two rounds: a difference between the arms below this is not resolved
-            r["same_arm_spread_pct"] = round(100.0 * max(abs(cam[0] - cam[1]) / min(cam), abs(pg[0] - pg[1]) / min(pg)), 2)
+            cost = pair_cost([r[k]["ms"] for k in ("cameras", "cameras_again")], [r[k]["ms"] for k in ("pose_grads", "pose_grads_again")])
+            r["cameras_cost_pct"], r["same_arm_spread_pct"] = cost["cost_pct"], cost["same_arm_spread_pct"]
     if a.capability_log:
-        with open(a.capability_log) as f:
-            for ln in f:
-                if "CAMERAS_CAPABILITY " in ln:
-                    out["capability"] = json.loads(ln[ln.index("CAMERAS_CAPABILITY ") + len("CAMERAS_CAPABILITY "):])
-    with open(a.out, "w") as f:
-        json.dump(out, f, indent=1, sort_keys=True)
-        f.write("\n")
-    print(json.dumps(out))
+        scrape_log(out, a.capability_log, "CAMERAS_CAPABILITY ")
+    write_out(out, a.out)
 
 
 if __name__ == "__main__":

@@ -15,19 +15,10 @@ curves) and the worst measured error over the bound of the forward rows.
                                        [--out profiles/r14_distortion.json]
 """
 import argparse
-import ctypes
-import json
 import os
-import re
-import subprocess
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "scripts"))
-
-from bench_cameras import LINES, _timed, pose_stack  # noqa: E402
-from bench_intrinsics import parent_bench  # noqa: E402
+from bench_common import (LINES, ROOT, child_spec, emit, launch_costs, pair_cost, parent_bench, pose_stack, run_specs, scrape_log, timed,
+                          write_out)
 
 TAG = "BENCH_DISTORTION_RESULT "
 KERNELS = ("k_select_rays", "k_dist_vjp_part", "k_dist_vjp_sum", "k_intr_vjp_part", "k_intr_vjp_sum", "k_pose_views_part", "k_pose_vjp_sum")
@@ -56,57 +47,23 @@ def _setup(name, arm, rays):
 
 def one_line(name, arm, steps, warmup, rays):
     step, V = _setup(name, arm, rays)
-    res = _timed(step, steps, warmup)
+    res = timed(step, steps, warmup)
     res["views"] = V
     return res
 
 
 def launches(name, arm, steps, warmup, rays):
     """Device us per launch of the selection and of the VJP's kernels over `steps` steps of the arm."""
-    import torch
-
-    import nerf_pytorch_amd as N
-    lib = N._lib.get_lib()
     step, _ = _setup(name, arm, rays)
-    for _ in range(warmup):
-        step()
-    torch.cuda.synchronize()
-    lib.profile_reserve(128 * steps)
-    lib.profile_enable(1)
-    for _ in range(steps):
-        step()
-    torch.cuda.synchronize()
-    lib.profile_enable(0)
-    buf = ctypes.create_string_buffer(1 << 16)
-    lib.profile_report(buf, len(buf))
-    out = {}
-    for ln in buf.value.decode().splitlines():
-        parts = ln.rsplit(None, 2)
-        if len(parts) == 3 and parts[0] in KERNELS:
-            out[parts[0]] = dict(launches_per_step=round(int(parts[1]) / steps, 2), us_per_launch=round(1e3 * float(parts[2]) / int(parts[1]), 2))
-    return out
+    return launch_costs(step, steps, warmup, KERNELS)
 
 
 def child(spec):
-    if spec.get("root"):   # (the package of another checkout: the parent commit's build)
-        sys.path.insert(0, spec["root"])
     if spec["kind"] == "launches":
         res = launches(spec["line"], spec["arm"], spec["steps"], spec["warmup"], spec["rays"])
     else:
         res = one_line(spec["line"], spec["arm"], spec["steps"], spec["warmup"], spec["rays"])
-    print(TAG + json.dumps(res))
-
-
-def measure(spec, limit):
-    try:
-        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", json.dumps(spec)], timeout=limit, capture_output=True,
-                           text=True)
-    except subprocess.TimeoutExpired:
-        return None, "time limit of %d s" % limit
-    for ln in p.stdout.splitlines():
-        if ln.startswith(TAG):
-            return json.loads(ln[len(TAG):]), None
-    return None, "exit status %d: %s" % (p.returncode, p.stderr.strip().splitlines()[-1:] or "")
+    emit(TAG, res)
 
 
 def main():
@@ -121,7 +78,7 @@ def main():
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:
-        return child(json.loads(a.child))
+        return child(child_spec(a.child))
     out = dict(metric="lens_distortion_cost", rays=a.rays, steps=a.steps, lines={}, launches={})
     parent_root = os.path.abspath(a.parent_root) if a.parent_root else None
     if parent_root:
@@ -132,44 +89,25 @@ def main():
             specs.append((("lines", name, arm), dict(kind="line", line=name, arm=arm.split("_again")[0], steps=a.steps, warmup=a.warmup,
                                                      rays=a.rays)))
             if parent_root and arm.startswith("distortion"):
-                specs.append((("parent_build", name, "intrinsics" + arm[len("distortion"):]),
+                specs.append((("parent_build", "intrinsics_arm", name, "intrinsics" + arm[len("distortion"):]),
                               dict(kind="line", line=name, arm="intrinsics", steps=a.steps, warmup=a.warmup, rays=a.rays, root=parent_root)))
     for arm in ("intrinsics", "distortion"):
         specs.append((("launches", "lego_8x256", arm), dict(kind="launches", line="lego_8x256", arm=arm, steps=a.steps, warmup=a.warmup,
                                                             rays=a.rays)))
-    for (top, mid, arm), spec in specs:
-        res, why = measure(spec, a.timeout)
-        if res is None:
-            out["stopped_at"] = dict(measurement=[top, mid, arm], reason=why)
-            break
-        if top == "parent_build":
-            out[top]["intrinsics_arm"].setdefault(mid, {})[arm] = res
-        else:
-            out[top].setdefault(mid, {})[arm] = res
+    run_specs(__file__, TAG, specs, out, a.timeout)
     for name, r in out["lines"].items():
         if all(k in r for k in ARMS):
-            dist, intr = [r[k]["ms"] for k in ("distortion", "distortion_again")], [r[k]["ms"] for k in ("intrinsics", "intrinsics_again")]
-            r["distortion_cost_pct"] = round(100.0 * (sum(dist) / sum(intr) - 1.0), 2)
-            r["distortion_cost_us"] = round(1e3 * (sum(dist) - sum(intr)) / 2, 1)
-            # what the same arm differs by between its two rounds: a difference between the arms below this is not resolved
-            r["same_arm_spread_pct"] = round(100.0 * max(abs(dist[0] - dist[1]) / min(dist), abs(intr[0] - intr[1]) / min(intr)), 2)
+            cost = pair_cost([r[k]["ms"] for k in ("distortion", "distortion_again")], [r[k]["ms"] for k in ("intrinsics", "intrinsics_again")])
+            r["distortion_cost_pct"], r["distortion_cost_us"], r["same_arm_spread_pct"] = cost["cost_pct"], cost["cost_us"], cost["same_arm_spread_pct"]
     if parent_root and "stopped_at" not in out:
         parent_bench(out, parent_root, a.timeout)
     if a.test_log:
-        ratios = []
-        with open(a.test_log) as f:
-            for ln in f:
-                if "DISTORTION_CAPABILITY " in ln:
-                    out["capability"] = json.loads(ln[ln.index("DISTORTION_CAPABILITY ") + len("DISTORTION_CAPABILITY "):])
-                m = re.search(r"distortion rows vs fp64 \((.*)\): worst error / bound = ([0-9.]+)", ln)
-                if m:
-                    ratios.append(dict(case=m.group(1), error_over_bound=float(m.group(2))))
+        rows = scrape_log(out, a.test_log, "DISTORTION_CAPABILITY ",
+                          dict(rows=r"distortion rows vs fp64 \((.*)\): worst error / bound = ([0-9.]+)"))["rows"]
+        ratios = [dict(case=case, error_over_bound=float(ratio)) for case, ratio in rows]
         if ratios:
             out["forward_rows_vs_fp64"] = dict(cases=ratios, worst_error_over_bound=max(r["error_over_bound"] for r in ratios))
-    with open(a.out, "w") as f:
-        json.dump(out, f, indent=1, sort_keys=True)
-        f.write("\n")
-    print(json.dumps(out))
+    write_out(out, a.out)
 
 
 if __name__ == "__main__":

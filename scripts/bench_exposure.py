@@ -17,19 +17,10 @@ and g_expo in the kernel cases.
                                      [--out profiles/r15_exposure.json]
 """
 import argparse
-import ctypes
-import json
 import os
-import re
-import subprocess
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "scripts"))
-
-from bench_cameras import LINES, _timed, pose_stack  # noqa: E402
-from bench_intrinsics import parent_bench  # noqa: E402
+from bench_common import (LINES, ROOT, child_spec, emit, launch_costs, pair_cost, parent_bench, pose_stack, run_specs, scrape_log, timed,
+                          write_out)
 
 TAG = "BENCH_EXPOSURE_RESULT "
 KERNELS = ("k_mse_loss", "k_mse_loss_views", "k_pose_views_group", "k_expo_part", "k_expo_sum", "k_adam")
@@ -63,35 +54,15 @@ def _setup(name, arm, rays):
 
 def one_line(name, arm, steps, warmup, rays):
     step, V = _setup(name, arm, rays)
-    res = _timed(step, steps, warmup)
+    res = timed(step, steps, warmup)
     res["views"] = V
     return res
 
 
 def launches(name, arm, steps, warmup, rays):
     """Device us per launch of the loss and of the table gradient's kernels over `steps` steps of the arm."""
-    import torch
-
-    import nerf_pytorch_amd as N
-    lib = N._lib.get_lib()
     step, _ = _setup(name, arm, rays)
-    for _ in range(warmup):
-        step()
-    torch.cuda.synchronize()
-    lib.profile_reserve(128 * steps)
-    lib.profile_enable(1)
-    for _ in range(steps):
-        step()
-    torch.cuda.synchronize()
-    lib.profile_enable(0)
-    buf = ctypes.create_string_buffer(1 << 16)
-    lib.profile_report(buf, len(buf))
-    out = {}
-    for ln in buf.value.decode().splitlines():
-        parts = ln.rsplit(None, 2)
-        if len(parts) == 3 and parts[0] in KERNELS:
-            out[parts[0]] = dict(launches_per_step=round(int(parts[1]) / steps, 2), us_per_launch=round(1e3 * float(parts[2]) / int(parts[1]), 2))
-    return out
+    return launch_costs(step, steps, warmup, KERNELS)
 
 
 def child(spec):
@@ -99,19 +70,7 @@ def child(spec):
         res = launches(spec["line"], spec["arm"], spec["steps"], spec["warmup"], spec["rays"])
     else:
         res = one_line(spec["line"], spec["arm"], spec["steps"], spec["warmup"], spec["rays"])
-    print(TAG + json.dumps(res))
-
-
-def measure(spec, limit):
-    try:
-        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", json.dumps(spec)], timeout=limit, capture_output=True,
-                           text=True)
-    except subprocess.TimeoutExpired:
-        return None, "time limit of %d s" % limit
-    for ln in p.stdout.splitlines():
-        if ln.startswith(TAG):
-            return json.loads(ln[len(TAG):]), None
-    return None, "exit status %d: %s" % (p.returncode, p.stderr.strip().splitlines()[-1:] or "")
+    emit(TAG, res)
 
 
 def main():
@@ -126,7 +85,7 @@ def main():
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:
-        return child(json.loads(a.child))
+        return child(child_spec(a.child))
     out = dict(metric="per_view_exposure_cost", rays=a.rays, steps=a.steps, lines={}, launches={})
     parent_root = os.path.abspath(a.parent_root) if a.parent_root else None
     if parent_root:
@@ -140,43 +99,29 @@ def main():
     for name in LINES:
         for arm in ("plain", "exposure", "cameras_exposure"):
             specs.append((("launches", name, arm), dict(kind="launches", line=name, arm=arm, steps=a.steps, warmup=a.warmup, rays=a.rays)))
-    for (top, mid, arm), spec in specs:
-        res, why = measure(spec, a.timeout)
-        if res is None:
-            out["stopped_at"] = dict(measurement=[top, mid, arm], reason=why)
-            break
-        out[top].setdefault(mid, {})[arm] = res
+    run_specs(__file__, TAG, specs, out, a.timeout)
     for name, r in out["lines"].items():
         for base, with_x in PAIRS:
             if all(k + rnd in r for k in (base, with_x) for rnd in ("", "_again")):
-                x, b = [r[with_x + rnd]["ms"] for rnd in ("", "_again")], [r[base + rnd]["ms"] for rnd in ("", "_again")]
-                r[with_x + "_cost_pct"] = round(100.0 * (sum(x) / sum(b) - 1.0), 2)
-                r[with_x + "_cost_us"] = round(1e3 * (sum(x) - sum(b)) / 2, 1)
-                # what the same arm differs by between its two rounds: a difference between the arms below this is not resolved
-                r[with_x + "_same_arm_spread_pct"] = round(100.0 * max(abs(x[0] - x[1]) / min(x), abs(b[0] - b[1]) / min(b)), 2)
+                cost = pair_cost([r[with_x + rnd]["ms"] for rnd in ("", "_again")], [r[base + rnd]["ms"] for rnd in ("", "_again")])
+                r.update({with_x + "_" + k: v for k, v in cost.items()})
     if parent_root and "stopped_at" not in out:
         parent_bench(out, parent_root, a.timeout)
         b = out["parent_build"].get("bench", {})
         if all(k in b for k in ("this", "parent", "this_again", "parent_again")):
             t, p = [b[k]["ms_per_step"] for k in ("this", "this_again")], [b[k]["ms_per_step"] for k in ("parent", "parent_again")]
             if all(v is not None for v in t + p):
-                out["parent_build"]["bench_this_over_parent_pct"] = round(100.0 * (sum(t) / sum(p) - 1.0), 2)
-                out["parent_build"]["bench_same_arm_spread_pct"] = round(100.0 * max(abs(t[0] - t[1]) / min(t), abs(p[0] - p[1]) / min(p)), 2)
+                cost = pair_cost(t, p)
+                out["parent_build"]["bench_this_over_parent_pct"] = cost["cost_pct"]
+                out["parent_build"]["bench_same_arm_spread_pct"] = cost["same_arm_spread_pct"]
     if a.test_log:
         worst = {}
-        with open(a.test_log) as f:
-            for ln in f:
-                if "EXPOSURE_CAPABILITY " in ln:
-                    out["capability"] = json.loads(ln[ln.index("EXPOSURE_CAPABILITY ") + len("EXPOSURE_CAPABILITY "):])
-                m = re.search(r"(g_rgb|g_expo) worst error / bound ([0-9.eE+-]+)", ln)
-                if m:
-                    worst[m.group(1)] = max(worst.get(m.group(1), 0.0), float(m.group(2)))
+        for what, ratio in scrape_log(out, a.test_log, "EXPOSURE_CAPABILITY ",
+                                      dict(worst=r"(g_rgb|g_expo) worst error / bound ([0-9.eE+-]+)"))["worst"]:
+            worst[what] = max(worst.get(what, 0.0), float(ratio))
         if worst:
             out["kernel_cases_worst_error_over_bound"] = worst
-    with open(a.out, "w") as f:
-        json.dump(out, f, indent=1, sort_keys=True)
-        f.write("\n")
-    print(json.dumps(out))
+    write_out(out, a.out)
 
 
 if __name__ == "__main__":

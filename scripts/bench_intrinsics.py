@@ -14,20 +14,10 @@ that fails ends the run.  Nothing here asserts a speed.  Writes profiles/r13_int
                                        [--out profiles/r13_intrinsics.json]
 """
 import argparse
-import ctypes
-import glob
-import json
 import os
-import shutil
-import subprocess
-import sys
-import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "scripts"))
-
-from bench_cameras import LINES, _timed, pose_stack  # noqa: E402
+from bench_common import (LINES, ROOT, child_spec, emit, launch_costs, pair_cost, parent_bench, pose_stack, run_specs, scrape_log, timed,
+                          write_out)
 
 TAG = "BENCH_INTRINSICS_RESULT "
 NEW_KERNELS = ("k_intr_vjp_part", "k_intr_vjp_sum", "k_intrinsics_fwd", "k_intrinsics_bwd")
@@ -53,7 +43,7 @@ def _setup(name, arm, rays):
 
 def one_line(name, arm, steps, warmup, rays):
     step, V = _setup(name, arm, rays)
-    res = _timed(step, steps, warmup)
+    res = timed(step, steps, warmup)
     res["views"] = V
     return res
 
@@ -64,7 +54,6 @@ def launches(name, steps, warmup, rays):
     import torch
 
     import nerf_pytorch_amd as N
-    lib = N._lib.get_lib()
     if name == "object":
         I = N.Intrinsics(400, 400, 555.5555, learn="all", lr=1e-5, device=torch.device("cuda", 0))
         I.g_intr.fill_(1e-3)
@@ -75,84 +64,15 @@ def launches(name, steps, warmup, rays):
             I.step()
     else:
         step, _ = _setup(name, "intrinsics", rays)
-    for _ in range(warmup):
-        step()
-    torch.cuda.synchronize()
-    lib.profile_reserve(128 * steps)
-    lib.profile_enable(1)
-    for _ in range(steps):
-        step()
-    torch.cuda.synchronize()
-    lib.profile_enable(0)
-    buf = ctypes.create_string_buffer(1 << 16)
-    lib.profile_report(buf, len(buf))
-    out = {}
-    for ln in buf.value.decode().splitlines():
-        parts = ln.rsplit(None, 2)
-        if len(parts) == 3 and parts[0] in NEW_KERNELS + (("k_adam",) if name == "object" else ()):
-            out[parts[0]] = dict(launches_per_step=round(int(parts[1]) / steps, 2), us_per_launch=round(1e3 * float(parts[2]) / int(parts[1]), 2))
-    return out
+    return launch_costs(step, steps, warmup, NEW_KERNELS + (("k_adam",) if name == "object" else ()))
 
 
 def child(spec):
-    if spec.get("root"):   # (the package of another checkout: the parent commit's build)
-        sys.path.insert(0, spec["root"])
     if spec["kind"] == "launches":
         res = launches(spec["line"], spec["steps"], spec["warmup"], spec["rays"])
     else:
         res = one_line(spec["line"], spec["arm"], spec["steps"], spec["warmup"], spec["rays"])
-    print(TAG + json.dumps(res))
-
-
-def bench_run(root, dump_dir, limit):
-    """`bench.py --dump-outputs dump_dir` of the checkout `root` in a process of its own: (its result line, None) or (None, reason)."""
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "3", "--no-labelled-lines",
-           "--no-cpu-baseline", "--dump-outputs", dump_dir]
-    try:
-        p = subprocess.run(cmd, cwd=root, timeout=limit, capture_output=True, text=True)
-    except subprocess.TimeoutExpired:
-        return None, "time limit of %d s" % limit
-    for ln in p.stdout.splitlines():
-        if ln.startswith("{"):
-            r = json.loads(ln)
-            return {k: r.get(k) for k in ("metric", "value", "unit", "ms_per_step", "final_loss")}, None
-    return None, "exit status %d: %s" % (p.returncode, p.stderr.strip().splitlines()[-1:] or "")
-
-
-def parent_bench(out, parent_root, limit):
-    """bench.py of this tree and of the parent checkout, alternating over two rounds; the first round's dumps compared on the bits."""
-    import numpy as np
-    pb = out["parent_build"]
-    pb["bench"] = {}
-    tmp = tempfile.mkdtemp(prefix="bench_intrinsics_")
-    try:
-        for rnd in ("", "_again"):
-            for arm, root in (("this", ROOT), ("parent", parent_root)):
-                d = os.path.join(tmp, arm + rnd)
-                res, why = bench_run(root, d, limit)
-                if res is None:
-                    out["stopped_at"] = dict(measurement=["parent_build", "bench", arm + rnd], reason=why)
-                    return
-                pb["bench"][arm + rnd] = res
-        this, parent = os.path.join(tmp, "this"), os.path.join(tmp, "parent")
-        names = sorted(os.path.basename(f) for f in glob.glob(os.path.join(this, "*.npy")))
-        same = {n: bool(os.path.exists(os.path.join(parent, n)) and np.array_equal(np.load(os.path.join(this, n)).view(np.uint32),
-                                                                                  np.load(os.path.join(parent, n)).view(np.uint32))) for n in names}
-        pb["bench_dump_outputs_vs_parent"] = dict(arrays=len(names), identical_bytes=same, all_identical=bool(names) and all(same.values()))
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
-
-
-def measure(spec, limit):
-    try:
-        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", json.dumps(spec)], timeout=limit, capture_output=True,
-                           text=True)
-    except subprocess.TimeoutExpired:
-        return None, "time limit of %d s" % limit
-    for ln in p.stdout.splitlines():
-        if ln.startswith(TAG):
-            return json.loads(ln[len(TAG):]), None
-    return None, "exit status %d: %s" % (p.returncode, p.stderr.strip().splitlines()[-1:] or "")
+    emit(TAG, res)
 
 
 def main():
@@ -167,7 +87,7 @@ def main():
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:
-        return child(json.loads(a.child))
+        return child(child_spec(a.child))
     out = dict(metric="learned_intrinsics_cost", rays=a.rays, steps=a.steps, lines={}, launches={})
     parent_root = os.path.abspath(a.parent_root) if a.parent_root else None
     if parent_root:
@@ -178,39 +98,20 @@ def main():
             specs.append((("lines", name, arm), dict(kind="line", line=name, arm=arm.split("_again")[0], steps=a.steps, warmup=a.warmup,
                                                      rays=a.rays)))
             if parent_root and arm.startswith("intrinsics"):
-                specs.append((("parent_build", name, "cameras" + arm[len("intrinsics"):]),
+                specs.append((("parent_build", "cameras_arm", name, "cameras" + arm[len("intrinsics"):]),
                               dict(kind="line", line=name, arm="cameras", steps=a.steps, warmup=a.warmup, rays=a.rays, root=parent_root)))
-    specs.append((("launches", "lego_8x256", None), dict(kind="launches", line="lego_8x256", steps=a.steps, warmup=a.warmup, rays=a.rays)))
-    specs.append((("launches", "object", None), dict(kind="launches", line="object", steps=a.steps * 10, warmup=a.warmup, rays=a.rays)))
-    for (top, mid, arm), spec in specs:
-        res, why = measure(spec, a.timeout)
-        if res is None:
-            out["stopped_at"] = dict(measurement=[top, mid, arm], reason=why)
-            break
-        if arm is None:
-            out[top][mid] = res
-        elif top == "parent_build":
-            out[top]["cameras_arm"].setdefault(mid, {})[arm] = res
-        else:
-            out[top].setdefault(mid, {})[arm] = res
+    specs.append((("launches", "lego_8x256"), dict(kind="launches", line="lego_8x256", steps=a.steps, warmup=a.warmup, rays=a.rays)))
+    specs.append((("launches", "object"), dict(kind="launches", line="object", steps=a.steps * 10, warmup=a.warmup, rays=a.rays)))
+    run_specs(__file__, TAG, specs, out, a.timeout)
     for name, r in out["lines"].items():
         if all(k in r for k in ("cameras", "intrinsics", "cameras_again", "intrinsics_again")):
-            intr, cam = [r[k]["ms"] for k in ("intrinsics", "intrinsics_again")], [r[k]["ms"] for k in ("cameras", "cameras_again")]
-            r["intrinsics_cost_pct"] = round(100.0 * (sum(intr) / sum(cam) - 1.0), 2)
-            r["intrinsics_cost_us"] = round(1e3 * (sum(intr) - sum(cam)) / 2, 1)
-            # what the same arm differs by between its two rounds: a difference between the arms below this is not resolved
-            r["same_arm_spread_pct"] = round(100.0 * max(abs(intr[0] - intr[1]) / min(intr), abs(cam[0] - cam[1]) / min(cam)), 2)
+            cost = pair_cost([r[k]["ms"] for k in ("intrinsics", "intrinsics_again")], [r[k]["ms"] for k in ("cameras", "cameras_again")])
+            r["intrinsics_cost_pct"], r["intrinsics_cost_us"], r["same_arm_spread_pct"] = cost["cost_pct"], cost["cost_us"], cost["same_arm_spread_pct"]
     if parent_root and "stopped_at" not in out:
         parent_bench(out, parent_root, a.timeout)
     if a.capability_log:
-        with open(a.capability_log) as f:
-            for ln in f:
-                if "INTRINSICS_CAPABILITY " in ln:
-                    out["capability"] = json.loads(ln[ln.index("INTRINSICS_CAPABILITY ") + len("INTRINSICS_CAPABILITY "):])
-    with open(a.out, "w") as f:
-        json.dump(out, f, indent=1, sort_keys=True)
-        f.write("\n")
-    print(json.dumps(out))
+        scrape_log(out, a.capability_log, "INTRINSICS_CAPABILITY ")
+    write_out(out, a.out)
 
 
 if __name__ == "__main__":

@@ -20,16 +20,13 @@ Writes profiles/rNN_localize.json under the next free round number (and prints i
                                        [--dump-outputs-dirs THIS PARENT] [--out FILE]
 """
 import argparse
-import ctypes
 import glob
 import json
 import os
 import re
-import subprocess
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from bench_common import ROOT, child_spec, emit, measure, profiled
 
 LINES = {
     "lego_8x256": dict(H=400, W=400, focal=555.5555, nc=64, nf=128, no_ndc=True, noise=0.2, near=2.0, far=6.0,
@@ -44,17 +41,6 @@ STAGE = {"localize": ("k_point_grad_pack", "k_point_grad", "k_ray_grad_sum", "k_
 TAG = "BENCH_LOCALIZE_RESULT "
 WINDOWS, ROUNDS, VIEWS = 5, 2, 2
 HBM_TBPS = 6.3
-
-
-def kernel_ms(lib, names):
-    buf = ctypes.create_string_buffer(1 << 16)
-    lib.profile_report(buf, len(buf))
-    out = {}
-    for ln in buf.value.decode().splitlines():
-        parts = ln.split()
-        if len(parts) == 3 and parts[0] in names:
-            out[parts[0]] = dict(launches=int(parts[1]), total_ms=float(parts[2]))
-    return out
 
 
 def stage_bytes(model, rays, nc, nf):
@@ -99,16 +85,8 @@ def one_line(name, arm, steps, warmup, rays):
         torch.cuda.synchronize()
         ms.append((time.perf_counter() - t0) * 1e3 / steps)
     ms.sort()
-    lib = N._lib.get_lib()
-    lib.profile_reserve(400 * steps)
-    torch.cuda.synchronize()
-    lib.profile_enable(1)
-    for _ in range(steps):
-        step()
-    torch.cuda.synchronize()
-    lib.profile_enable(0)
-    k = kernel_ms(lib, STAGE[arm])
-    stage_us = {kk: round(v["total_ms"] * 1e3 / steps, 2) for kk, v in k.items()}
+    rows = profiled(step, steps, 0, reserve_per_step=400).rows
+    stage_us = {kk: round(rows[kk][1] * 1e3 / steps, 2) for kk in rows if kk in STAGE[arm]}
     res = dict(ms=round(ms[len(ms) // 2], 4), ms_min=round(ms[0], 4), ms_max=round(ms[-1], 4), windows=WINDOWS, steps=steps,
                stage_us_per_step=stage_us, stage_total_us=round(sum(stage_us.values()), 2), pose_grads_finite=bool(torch.isfinite(pg).all()),
                modes=(mc.backward_compaction, mf.backward_compaction),
@@ -120,20 +98,6 @@ def one_line(name, arm, steps, warmup, rays):
         if mfma_us > 0:
             res["stage_hbm_fraction_of_%.1f_TBps" % HBM_TBPS] = round(b / (mfma_us * 1e-6) / (HBM_TBPS * 1e12), 4)
     return res
-
-
-def measure(spec, limit, root):
-    """Runs one figure in a fresh process (package imported from `root`) under `limit` seconds; (result, None) or (None, reason)."""
-    env = dict(os.environ, PYTHONPATH=root + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    try:
-        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", json.dumps(spec)], timeout=limit, capture_output=True,
-                           text=True, env=env)
-    except subprocess.TimeoutExpired:
-        return None, "time limit of %d s" % limit
-    for ln in p.stdout.splitlines():
-        if ln.startswith(TAG):
-            return json.loads(ln[len(TAG):]), None
-    return None, "exit status %d: %s" % (p.returncode, p.stderr.strip().splitlines()[-1:] or "")
 
 
 def next_round_file():
@@ -156,9 +120,8 @@ def main():
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:
-        spec = json.loads(a.child)
-        print(TAG + json.dumps(one_line(spec["line"], spec["arm"], spec["steps"], spec["warmup"], spec["rays"])))
-        return
+        spec = child_spec(a.child)
+        return emit(TAG, one_line(spec["line"], spec["arm"], spec["steps"], spec["warmup"], spec["rays"]))
     base_root = os.path.abspath(a.parent_root) if a.parent_root else ROOT
     out = dict(metric="localize_step_cost", rays=a.rays, steps=a.steps, views=VIEWS, lines={},
                step_lr0_arm="parent build" if a.parent_root else "this build (its unchanged trainable path)")
@@ -176,8 +139,8 @@ def main():
     for name in a.lines.split(","):
         for rnd in range(ROUNDS):
             for arm in ("step_lr0", "localize"):
-                res, why = measure(dict(line=name, arm=arm, steps=a.steps, warmup=a.warmup, rays=a.rays), a.timeout,
-                                   base_root if arm == "step_lr0" else ROOT)
+                res, why = measure(__file__, TAG, dict(line=name, arm=arm, steps=a.steps, warmup=a.warmup, rays=a.rays), a.timeout,
+                                   root=base_root if arm == "step_lr0" else ROOT)
                 if res is None:   # (nothing more is started on the device after a failure)
                     out["stopped_at"] = dict(measurement=[name, arm, rnd], reason=why)
                     break

@@ -41,7 +41,6 @@ def render_arms(sizes, rounds, repeats):
     import torch
 
     import nerf_pytorch_amd as N
-    from nerf_pytorch_amd import _lib as L
     if not torch.cuda.is_available():
         raise SystemExit("bench_occupancy needs the GPU: a CPU run measures nothing")
     dev = torch.device("cuda", 0)
@@ -54,7 +53,6 @@ def render_arms(sizes, rounds, repeats):
     pose = torch.from_numpy(r["pose"]).to(dev)
     ex, ed = N.get_embedding_function(10, True, True), N.get_embedding_function(4, True, True)
     opts = N.make_options(64, 64, perturb=False, white_background=True, radiance_field_noise_std=0.0)
-    lib = L.get_lib()
     rec = {}
     for arith in ("fp32", "f16x3"):
         mc.set_inference_precision(arith), mf.set_inference_precision(arith)
@@ -99,14 +97,9 @@ def render_arms(sizes, rounds, repeats):
             # per-launch kernel times: a pass of its own under the launch profile
             kernels = {}
             for name, occ in (("dense", None), ("grid", grid)):
-                lib.profile_enable(1)
-                render(occ)
-                buf = __import__("ctypes").create_string_buffer(1 << 16)
-                lib.profile_report(buf, len(buf))
-                lib.profile_enable(0)
-                kernels[name] = {" ".join(l.split()[:-2]):
-                                 dict(launches=int(l.split()[-2]), ms_per_launch=round(float(l.split()[-1]) / int(l.split()[-2]), 4))
-                                 for l in buf.value.decode().splitlines() if l.strip()}
+                with N.LaunchProfile() as prof:
+                    render(occ)
+                kernels[name] = {k: dict(launches=launches, ms_per_launch=round(ms / launches, 4)) for k, (launches, ms) in prof.rows.items()}
             spread = max((max(v) - min(v)) / median(v) for v in rates.values()) * 100.0
             a["%dx%d" % (side, side)] = dict(
                 rays_per_s_dense=round(median(rates["dense"])), rays_per_s_grid=round(median(rates["grid"])),

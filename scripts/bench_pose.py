@@ -5,7 +5,6 @@ default; a step with pose_grad runs it as mode 2).  Prints one JSON line.
     python scripts/bench_pose.py [--steps 30] [--warmup 5]
 """
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -28,17 +27,6 @@ LINES = {
 }
 
 
-def kernel_ms(lib, names):
-    buf = ctypes.create_string_buffer(1 << 16)
-    lib.profile_report(buf, len(buf))
-    out = {}
-    for ln in buf.value.decode().splitlines():
-        parts = ln.split()
-        if len(parts) == 3 and parts[0] in names:
-            out[parts[0]] = dict(launches=int(parts[1]), total_ms=float(parts[2]))
-    return out
-
-
 def run_line(name, w, steps, warmup, rays):
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
@@ -49,7 +37,6 @@ def run_line(name, w, steps, warmup, rays):
     pose = torch.eye(4, device=dev)
     pose[2, 3] = 4.0 if w["no_ndc"] else 0.0
     res = dict(modes=(mc.backward_compaction, mf.backward_compaction))
-    lib = N._lib.get_lib()
     for arm in ("plain", "pose_grad"):
         eng = N.TrainEngine(mc, mf, w["nc"], w["nf"], noise_std=w["noise"], lr=1e-6, world_size=1, rank=0)
         pg = torch.empty(3, 4, device=dev) if arm == "pose_grad" else None
@@ -62,15 +49,11 @@ def run_line(name, w, steps, warmup, rays):
         torch.cuda.synchronize()
         res[arm + "_ms"] = round((time.perf_counter() - t0) * 1e3 / steps, 4)
         if pg is not None:  # the two new launches by themselves, timed per launch
-            lib.profile_reserve(200 * steps)
-            torch.cuda.synchronize()
-            lib.profile_enable(1)
-            for _ in range(steps):
-                eng.step_on_image(img, pose, H, W, w["focal"], opts, rays, pose_grad=pg)
-            torch.cuda.synchronize()
-            lib.profile_enable(0)
-            k = kernel_ms(lib, ("k_pose_vjp_part", "k_pose_vjp_sum", "k_ray_grad"))
-            res["kernels_us_per_step"] = {kk: round(v["total_ms"] * 1e3 / steps, 2) for kk, v in k.items()}
+            with N.LaunchProfile(200 * steps) as prof:
+                for _ in range(steps):
+                    eng.step_on_image(img, pose, H, W, w["focal"], opts, rays, pose_grad=pg)
+            res["kernels_us_per_step"] = {k: round(ms * 1e3 / steps, 2) for k, (_, ms) in prof.rows.items()
+                                          if k in ("k_pose_vjp_part", "k_pose_vjp_sum", "k_ray_grad")}
             res["pose_grad_finite"] = bool(torch.isfinite(pg).all())
     res["pose_grad_cost_pct"] = round(100.0 * (res["pose_grad_ms"] / res["plain_ms"] - 1.0), 2)
     return res

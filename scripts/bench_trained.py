@@ -21,7 +21,6 @@ recorded 75-87 % on this scene).  This script
 """
 import argparse
 import copy
-import ctypes as C
 import json
 import os
 import sys
@@ -64,25 +63,16 @@ def make_engine(state_c, state_f, precision, compact, lr, seed):
 
 
 def timed(eng, stream, opts, steps, warmup, lr):
-    lib = L.get_lib()
     batches = [next(stream) for _ in range(warmup + steps)]
     for ro, rd, tgt in batches[:warmup]:
         eng.step(N.pack_rays(ro, rd, opts), tgt, lr=lr)
-    lib.profile_reserve(96 * steps)
-    torch.cuda.synchronize()
-    lib.profile_enable(1)
-    t0 = time.perf_counter()
-    for ro, rd, tgt in batches[warmup:]:
-        eng.step(N.pack_rays(ro, rd, opts), tgt, lr=lr)
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    lib.profile_enable(0)
-    buf = C.create_string_buffer(1 << 16)
-    lib.profile_report(buf, len(buf))
-    kern = {}
-    for line in buf.value.decode().splitlines():
-        name, cnt, ms = line.rsplit(" ", 2)
-        kern[name.strip("()")] = round(float(ms) / steps, 4)
+    with N.LaunchProfile(96 * steps) as prof:
+        t0 = time.perf_counter()
+        for ro, rd, tgt in batches[warmup:]:
+            eng.step(N.pack_rays(ro, rd, opts), tgt, lr=lr)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+    kern = {name.strip("()"): round(ms / steps, 4) for name, (_, ms) in prof.rows.items()}
     return dt / steps, dict(sorted(kern.items(), key=lambda kv: -kv[1])[:12])
 
 

@@ -7,7 +7,6 @@ with --capability-log, the error curves that tests/test_gpu_views.py prints (its
     python scripts/bench_views.py [--steps 30] [--warmup 5] [--reps 50] [--out profiles/r08_views.json] [--capability-log LOG]
 """
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -32,15 +31,8 @@ VJP1 = ("k_pose_vjp_part", "k_pose_vjp_sum")                                    
 VJPV = ("k_pose_views_group", "k_pose_views_part", "k_pose_vjp_sum")             # the views VJP's three (the sum kernel is shared)
 
 
-def kernel_us(lib, names):
-    buf = ctypes.create_string_buffer(1 << 16)
-    lib.profile_report(buf, len(buf))
-    out = {}
-    for ln in buf.value.decode().splitlines():
-        parts = ln.split()
-        if len(parts) == 3 and parts[0] in names:
-            out[parts[0]] = round(float(parts[2]) * 1e3 / int(parts[1]), 2)   # us per launch
-    return out
+def kernel_us(prof, names):
+    return {k: round(ms * 1e3 / launches, 2) for k, (launches, ms) in prof.rows.items() if k in names}   # us per launch
 
 
 def pose_stack(V, dev, z):
@@ -51,21 +43,17 @@ def pose_stack(V, dev, z):
     return p.to(dev)
 
 
-def profiled(lib, reps, fn):
+def profiled(reps, fn):
     for _ in range(3):
         fn()
-    torch.cuda.synchronize()
-    lib.profile_reserve(8 * reps)
-    lib.profile_enable(1)
-    for _ in range(reps):
-        fn()
-    torch.cuda.synchronize()
-    lib.profile_enable(0)
+    with N.LaunchProfile(8 * reps) as prof:
+        for _ in range(reps):
+            fn()
+    return prof
 
 
 def launches(n, V, reps):
     dev = torch.device("cuda", 0)
-    lib = N._lib.get_lib()
     H = W = 400
     opts = N.make_options(64, 128)
     imgs = torch.rand(V, H, W, 3, device=dev)
@@ -76,14 +64,14 @@ def launches(n, V, reps):
     _, _, used = T.select_training_rays_views(H, W, 555.5555, poses, imgs, n, opts, seed=1, step=0)
     _, _, used1 = T.select_training_rays(H, W, 555.5555, poses[0], imgs[0], n, opts, seed=1, step=0)
     out, out1 = torch.empty(V, 3, 4, device=dev), torch.empty(3, 4, device=dev)
-    profiled(lib, reps, lambda: T.select_training_rays_views(H, W, 555.5555, poses, imgs, n, opts, seed=1, step=0))
-    res["select_views_us"] = kernel_us(lib, SEL)[SEL[0]]
-    profiled(lib, reps, lambda: T.select_training_rays(H, W, 555.5555, poses[0], imgs[0], n, opts, seed=1, step=0))
-    res["select_single_us"] = kernel_us(lib, SEL)[SEL[0]]
-    profiled(lib, reps, lambda: T.select_training_rays_views_bwd(H, W, 555.5555, poses, used, g, opts, g2, out=out))
-    res["views_vjp_kernels_us"] = kernel_us(lib, VJPV)
-    profiled(lib, reps, lambda: T.select_training_rays_bwd(H, W, 555.5555, poses[0], used1, g, opts, g2, out=out1))
-    res["single_vjp_kernels_us"] = kernel_us(lib, VJP1)
+    prof = profiled(reps, lambda: T.select_training_rays_views(H, W, 555.5555, poses, imgs, n, opts, seed=1, step=0))
+    res["select_views_us"] = kernel_us(prof, SEL)[SEL[0]]
+    prof = profiled(reps, lambda: T.select_training_rays(H, W, 555.5555, poses[0], imgs[0], n, opts, seed=1, step=0))
+    res["select_single_us"] = kernel_us(prof, SEL)[SEL[0]]
+    prof = profiled(reps, lambda: T.select_training_rays_views_bwd(H, W, 555.5555, poses, used, g, opts, g2, out=out))
+    res["views_vjp_kernels_us"] = kernel_us(prof, VJPV)
+    prof = profiled(reps, lambda: T.select_training_rays_bwd(H, W, 555.5555, poses[0], used1, g, opts, g2, out=out1))
+    res["single_vjp_kernels_us"] = kernel_us(prof, VJP1)
     res["views_vjp_us"] = round(sum(res["views_vjp_kernels_us"].values()), 2)
     res["single_vjp_us"] = round(sum(res["single_vjp_kernels_us"].values()), 2)
     res["views_without_a_ray"] = int((torch.bincount(used // (H * W), minlength=V) == 0).sum())

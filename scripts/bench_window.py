@@ -21,11 +21,10 @@ import glob
 import json
 import os
 import re
-import subprocess
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from bench_common import ROOT, child_spec, emit, measure
 
 LINES = {
     "fern_4x64": dict(nc=64, nf=64, noise=1.0,
@@ -142,21 +141,7 @@ def child(spec):
         res = one_line(spec["line"], spec["arm"], spec["steps"], spec["warmup"], spec["rays"])
     else:
         res = capability(spec["schedule"], spec["steps"], spec["rays"], spec["deg"], spec["shift"], spec["views"])
-    print(TAG + json.dumps(res))
-
-
-def measure(spec, limit, root):
-    """Runs one measurement in a fresh process (package imported from `root`) under `limit` seconds; (result, None) or (None, reason)."""
-    env = dict(os.environ, PYTHONPATH=root + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    try:
-        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", json.dumps(spec)], timeout=limit, capture_output=True,
-                           text=True, env=env)
-    except subprocess.TimeoutExpired:
-        return None, "time limit of %d s" % limit
-    for ln in p.stdout.splitlines():
-        if ln.startswith(TAG):
-            return json.loads(ln[len(TAG):]), None
-    return None, "exit status %d: %s" % (p.returncode, p.stderr.strip().splitlines()[-1:] or "")
+    emit(TAG, res)
 
 
 def next_round_file():
@@ -182,7 +167,7 @@ def main():
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:
-        return child(json.loads(a.child))
+        return child(child_spec(a.child))
     base_root = os.path.abspath(a.parent_root) if a.parent_root else ROOT
     out = dict(metric="encoding_window", rays=a.rays, steps=a.steps, no_window_arm="parent build" if a.parent_root else "this build", lines={},
                capability={})
@@ -199,7 +184,7 @@ def main():
                           dict(kind="capability", schedule=schedule, steps=a.capability_steps, rays=a.capability_rays, deg=a.deg,
                                shift=a.shift, views=a.views), 2 * a.timeout))
     for (top, mid, arm), root, spec, limit in specs:
-        res, why = measure(spec, limit, root)
+        res, why = measure(__file__, TAG, spec, limit, root=root)
         if res is None:
             out["stopped_at"] = dict(measurement=[top, mid, arm], reason=why)
             break

@@ -7,9 +7,9 @@ import pytest
 import torch
 
 import cameras_cases as CC
+import engine_scenes as ES
 import parity_cases as PC
 import pose_vjp as P
-import test_gpu_views as TV
 
 pytestmark = pytest.mark.gpu
 
@@ -52,14 +52,14 @@ def test_dropin_twist_gradient_is_the_kernel_on_the_views_node_gradient():
     grad) returns the bits of the autograd path's forward."""
     import nerf_pytorch_amd as N
     import nerf_pytorch_amd._lib as L
-    dev = TV._dev()
-    r = TV.gold("lego_lowres_render.npz")
+    dev = ES.dev()
+    r = ES.gold("lego_lowres_render.npz")
     H, W, focal, pose0 = int(r["H"]), int(r["W"]), float(np.float32(r["focal"])), r["pose"].astype(np.float32)
     opts = N.make_options(64, 64)
     V, n = 3, 768
     g = torch.Generator().manual_seed(8)
     imgs = torch.rand(V, H, W, 3, generator=g).to(dev)
-    base = TV._views(pose0, dev, V)
+    base = ES.views(pose0, dev, V)
     xi = (torch.randn(V, 6, generator=g) * 0.05).to(dev).requires_grad_(True)
     gr = torch.randn(n, 11, generator=g).to(dev)
     poses = N.se3_poses(xi, base)
@@ -85,14 +85,14 @@ def test_dropin_twist_gradient_is_the_kernel_on_the_views_node_gradient():
 # ---- CameraTable ----------------------------------------------------------------------------------------------------------------------
 def _table(dev, V, **kw):
     import nerf_pytorch_amd as N
-    pose0 = TV.gold("lego_lowres_render.npz")["pose"].astype(np.float32)
-    return N.CameraTable(TV._views(pose0, dev, V), **kw)
+    pose0 = ES.gold("lego_lowres_render.npz")["pose"].astype(np.float32)
+    return N.CameraTable(ES.views(pose0, dev, V), **kw)
 
 
 def test_table_adam_matches_torch_adam():
     """CameraTable.step over three recorded gradients against torch.optim.Adam on a CPU copy, to the bound parity_cases.case_loss_adam
     holds the same kernel to: close(..., 1e-7, 1e-6)."""
-    dev = TV._dev()
+    dev = ES.dev()
     V = 5
     T = _table(dev, V, lr=5e-3)
     p = torch.zeros(V, 6, requires_grad=True)
@@ -109,7 +109,7 @@ def test_table_adam_matches_torch_adam():
 
 
 def test_table_state_round_trip_gives_the_same_next_step():
-    dev = TV._dev()
+    dev = ES.dev()
     V = 4
     T = _table(dev, V, lr=2e-3)
     g = torch.Generator().manual_seed(5)
@@ -140,16 +140,16 @@ def test_step_on_views_with_cameras_equals_its_parts(overlap):
     step_on_views(images, poses, pose_grads=pg), T.backward(pg), T.step() -- loss, both nets' parameters and the table's twists and
     moments on the bits after every step; view 1 is inactive: its twist stays exactly 0 and its pose its base."""
     import nerf_pytorch_amd as N
-    dev = TV._dev()
+    dev = ES.dev()
     V, n = 3, 256
     opts = N.make_options(64, 64)
     res = {}
     for arm in ("cameras", "parts"):
-        mc, mf, H, W, focal, pose0 = TV._lego(dev)
+        mc, mf, H, W, focal, pose0 = ES.lego(dev)
         eng = N.TrainEngine(mc, mf, 64, 64, perturb=True, white_background=True, noise_std=0.2, seed=3, lr=5e-4, world_size=1, rank=0,
                             overlap=overlap)
         imgs = torch.rand(V, H, W, 3, generator=torch.Generator().manual_seed(1)).to(dev)
-        base = TV._views(pose0, dev, V)
+        base = ES.views(pose0, dev, V)
         T = N.CameraTable(base, lr=2e-3, active=[True, False, True])
         seen = []
         for _ in range(3):
@@ -173,10 +173,10 @@ def test_step_on_views_with_cameras_equals_its_parts(overlap):
 
 def test_step_on_views_with_cameras_refuses_what_it_cannot_do():
     import nerf_pytorch_amd as N
-    dev = TV._dev()
-    mc, mf, H, W, focal, pose0 = TV._lego(dev)
+    dev = ES.dev()
+    mc, mf, H, W, focal, pose0 = ES.lego(dev)
     V = 2
-    T = N.CameraTable(TV._views(pose0, dev, V))
+    T = N.CameraTable(ES.views(pose0, dev, V))
     imgs = torch.zeros(V, H, W, 3, device=dev)
     opts = N.make_options(32, 32)
     eng = N.TrainEngine(mc, mf, 32, 32, world_size=1, rank=0)
@@ -194,26 +194,6 @@ def test_step_on_views_with_cameras_refuses_what_it_cannot_do():
 STEPS, LR = 300, 3e-3
 
 
-def _se3_exp(xi):
-    """4 x 4 SE(3) exponential of a twist [w, v] in torch (fp32 here): the kernel's exponential restated per view -- series in th^2
-    below 1e-2 (three terms: the first one left out is below 1e-10 of the sum), closed forms above."""
-    w, v = xi[:3], xi[3:]
-    x = (w * w).sum()
-    small = x < 1e-2
-    xs = torch.where(small, torch.ones_like(x), x)    # (no 0 / 0 in the branch torch.where does not select)
-    th = torch.sqrt(xs)
-    a = torch.where(small, 1 - x / 6 + x * x / 120, torch.sin(th) / th)
-    b = torch.where(small, 0.5 - x / 24 + x * x / 720, (1 - torch.cos(th)) / xs)
-    c = torch.where(small, 1 / 6 - x / 120 + x * x / 5040, (th - torch.sin(th)) / (xs * th))
-    z = torch.zeros_like(x)
-    K = torch.stack([torch.stack([z, -w[2], w[1]]), torch.stack([w[2], z, -w[0]]), torch.stack([-w[1], w[0], z])])
-    eye = torch.eye(3, dtype=xi.dtype, device=xi.device)
-    K2 = K @ K
-    R, t = eye + a * K + b * K2, (eye + b * K + c * K2) @ v
-    top = torch.cat([R, t[:, None]], 1)
-    return torch.cat([top, torch.tensor([[0.0, 0.0, 0.0, 1.0]], dtype=xi.dtype, device=xi.device)], 0)
-
-
 def test_two_perturbed_poses_are_recovered_by_the_engine_alone():
     """The joint two-camera recovery of tests/test_gpu_views.py (frozen lego-lowres nets, each pose 2 degrees / 0.05 units off, STEPS
     steps of 1024 rays across both views), driven by step_on_views(cameras=...) alone: no torch autograd, no torch optimiser.
@@ -221,11 +201,11 @@ def test_two_perturbed_poses_are_recovered_by_the_engine_alone():
     fed by step_on_views(pose_grads=...).  Every final error is below its start and at most 3x the comparison arm's: the two Adam
     trajectories share a gradient but not a rounding sequence, the bar section 3.7's capability test holds two such runs to."""
     import nerf_pytorch_amd as N
-    dev = TV._dev()
-    mc, mf, H, W, focal, pose0 = TV._lego(dev)
+    dev = ES.dev()
+    mc, mf, H, W, focal, pose0 = ES.lego(dev)
     for p in list(mc.parameters()) + list(mf.parameters()):
         p.requires_grad_(False)
-    ex, ed = TV._ex_ed()
+    ex, ed = ES.ex_ed()
     opts = N.make_options(64, 64, perturb=False, white_background=True, radiance_field_noise_std=0.0)
     gt0 = torch.from_numpy(pose0).to(dev)
     turn = torch.eye(4, device=dev)
@@ -242,7 +222,7 @@ def test_two_perturbed_poses_are_recovered_by_the_engine_alone():
     for axis, shift in (([0.3, -0.8, 0.5], [0.03, -0.03, 0.0277]), ([-0.6, 0.2, 0.7], [-0.0277, 0.03, 0.03])):
         axis = torch.tensor(axis)
         deltas.append(torch.cat([axis / axis.norm() * np.deg2rad(2.0), torch.tensor(shift)]).float().to(dev))
-    starts = torch.stack([(gts[v] @ TV._se3(deltas[v])).detach() for v in range(2)])
+    starts = torch.stack([(gts[v] @ ES.se3(deltas[v])).detach() for v in range(2)])
     gts64 = gts.cpu().numpy().astype(np.float64)
 
     def errors(est, v):
@@ -262,7 +242,7 @@ def test_two_perturbed_poses_are_recovered_by_the_engine_alone():
             xi = torch.zeros(2, 6, device=dev, requires_grad=True)
             opt = torch.optim.Adam([xi], lr=LR)
             pg = torch.empty(2, 3, 4, device=dev)
-            poses_of = lambda: torch.stack([starts[v] @ _se3_exp(xi[v]) for v in range(2)])  # noqa: E731
+            poses_of = lambda: torch.stack([starts[v] @ ES.se3_exp(xi[v]) for v in range(2)])  # noqa: E731
             now = lambda: poses_of().detach()  # noqa: E731
         for it in range(STEPS):
             if cameras:

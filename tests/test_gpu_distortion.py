@@ -16,10 +16,8 @@ import torch
 
 import conftest  # noqa: F401 (first: run as a script, --record, this is what puts the package and the oracle on sys.path)
 import distortion_cases as DC
+import engine_scenes as ES
 import pose_vjp as P
-import test_gpu_localize as TL
-import test_gpu_step_forms as SF
-import test_gpu_views as TV
 
 pytestmark = pytest.mark.gpu
 
@@ -93,14 +91,14 @@ def test_dropin_distortion_gradient_is_the_kernel_and_none_is_the_existing_path(
     bits of the _bwd call from ONE node; the forward is the plain launch; distortion=None is the existing node and function; zero
     coefficients give the rows of the call without them; the bundle forms and render_pose_rows take the distortion forward only."""
     import nerf_pytorch_amd as N
-    dev = TV._dev()
-    mc, mf, H, W, focal, pose0 = TV._lego(dev)
+    dev = ES.dev()
+    mc, mf, H, W, focal, pose0 = ES.lego(dev)
     V, n = 3, 700
     g = torch.Generator().manual_seed(8)
     imgs = torch.rand(V, H, W, 3, generator=g).to(dev)
     gr = torch.randn(n, 11, generator=g).to(dev)
     opts = N.make_options(64, 64)
-    poses = TV._views(pose0, dev, V)
+    poses = ES.views(pose0, dev, V)
     intr = torch.tensor([focal * 1.03, focal * 0.98, W * 0.5 + 1.25, H * 0.5 - 0.75], dtype=torch.float32, device=dev)
     kap = _kappa(dev)
     plain = N.select_training_rays_views(H, W, focal, poses, imgs, n, opts, seed=4, step=1, intrinsics=intr, distortion=kap)
@@ -176,7 +174,7 @@ def test_dropin_distortion_gradient_is_the_kernel_and_none_is_the_existing_path(
         assert torch.equal(b, full[1].reshape(-1, 3)[pix]) and not torch.equal(full[1], N.get_ray_bundle(H, W, focal, poses[0], intrinsics=k)[1])
     with pytest.raises(RuntimeError, match="forward only"):
         N.get_ray_bundle(H, W, focal, poses[0].clone().requires_grad_(True), distortion=kap)
-    ex, ed = TV._ex_ed()
+    ex, ed = ES.ex_ed()
     eval_opts = N.make_options(8, 8, perturb=False, radiance_field_noise_std=0.0)
     rows0 = N.render_pose_rows(H, W, focal, poses[0], mc, mf, eval_opts, ex, ed, rank=1, world_size=8)
     rows1 = N.render_pose_rows(H, W, focal, poses[0], mc, mf, eval_opts, ex, ed, rank=1, world_size=8, distortion=zero)
@@ -193,7 +191,7 @@ def test_dropin_distortion_gradient_is_the_kernel_and_none_is_the_existing_path(
 # ---- cameras.Distortion and the engine ------------------------------------------------------------------------------------------------
 def test_distortion_object_values_masks_and_state():
     import nerf_pytorch_amd as N
-    dev = TV._dev()
+    dev = ES.dev()
     D = N.Distortion(learn="radial", lr=1e-2, device=dev)
     assert torch.equal(D.values(), torch.zeros(4, device=dev)) and D.mask.tolist() == [1, 1, 0, 0]
     D.g_dist.copy_(torch.tensor([0.5, -0.25, 0.0, 0.0], device=dev))   # (what the masked VJP leaves: exact zeros in p1, p2)
@@ -247,15 +245,15 @@ def test_step_on_views_with_distortion_equals_its_parts():
     """Five steps of step_on_views(cameras=T, intrinsics=I, distortion=D) against the same calls made by hand: loss, nets, twists, q
     and the coefficients on the bits."""
     import nerf_pytorch_amd as N
-    dev = TV._dev()
+    dev = ES.dev()
     V, n = 3, 256
     opts = N.make_options(32, 32)
     res = {}
     for arm in ("engine", "parts"):
-        mc, mf, H, W, focal, pose0 = TV._lego(dev)
+        mc, mf, H, W, focal, pose0 = ES.lego(dev)
         eng = N.TrainEngine(mc, mf, 32, 32, perturb=True, white_background=True, noise_std=0.2, seed=3, lr=5e-4, world_size=1, rank=0)
         imgs = torch.rand(V, H, W, 3, generator=torch.Generator().manual_seed(1)).to(dev)
-        T = N.CameraTable(TV._views(pose0, dev, V), lr=2e-3)
+        T = N.CameraTable(ES.views(pose0, dev, V), lr=2e-3)
         I = N.Intrinsics(H, W, focal * 1.02, learn="all", lr=1e-3, device=dev)
         D = N.Distortion((-0.05, 0.01, 1e-3, -1e-3), learn="all", lr=1e-3, device=dev)
         seen = []
@@ -280,15 +278,15 @@ def test_a_distortion_that_learns_nothing_leaves_the_step_what_it_was():
     gradient, are those of step_on_views(cameras=T, intrinsics=I) without distortion, on the bits; the same with the distortion
     alone against step_on_views with pose_grads."""
     import nerf_pytorch_amd as N
-    dev = TV._dev()
+    dev = ES.dev()
     V, n = 3, 256
     opts = N.make_options(32, 32)
     res = {}
     for arm in ("with", "without", "alone", "plain"):
-        mc, mf, H, W, focal, pose0 = TV._lego(dev)
+        mc, mf, H, W, focal, pose0 = ES.lego(dev)
         eng = N.TrainEngine(mc, mf, 32, 32, perturb=True, white_background=True, noise_std=0.2, seed=3, lr=5e-4, world_size=1, rank=0)
         imgs = torch.rand(V, H, W, 3, generator=torch.Generator().manual_seed(1)).to(dev)
-        base = TV._views(pose0, dev, V)
+        base = ES.views(pose0, dev, V)
         T = N.CameraTable(base, lr=2e-3)
         I = N.Intrinsics(H, W, focal * 1.02, learn="all", lr=1e-3, device=dev)
         D = N.Distortion(learn=(), device=dev) if arm in ("with", "alone") else None
@@ -313,15 +311,15 @@ def test_a_distortion_that_learns_nothing_leaves_the_step_what_it_was():
 
 def test_localize_with_distortion_leaves_the_nets_alone_and_refusals():
     import nerf_pytorch_amd as N
-    dev = TV._dev()
-    mc, mf, H, W, focal, pose0 = TL._small(dev)
+    dev = ES.dev()
+    mc, mf, H, W, focal, pose0 = ES.small(dev)
     V, n = 3, 256
     opts = N.make_options(8, 8)
     imgs = torch.rand(V, H, W, 3, generator=torch.Generator().manual_seed(1)).to(dev)
-    base = TV._views(pose0, dev, V)
+    base = ES.views(pose0, dev, V)
     eng = N.TrainEngine(mc, mf, 8, 8, perturb=True, white_background=True, noise_std=0.2, seed=3, lr=5e-4, world_size=1, rank=0)
     eng.grad.normal_(), eng.exp_avg.normal_(), eng.exp_avg_sq.uniform_()
-    before = TL._state(eng)
+    before = ES.state(eng)
     D = N.Distortion(learn="radial", lr=1e-3, device=dev)
     I = N.Intrinsics(H, W, focal * 1.05, learn="focal", lr=1e-3, device=dev)
     T = N.CameraTable(base, lr=2e-3)
@@ -332,7 +330,7 @@ def test_localize_with_distortion_leaves_the_nets_alone_and_refusals():
     eng.localize_on_image(imgs[0], base[0], H, W, focal, opts, n, pose_grad=pg, distortion=D)
     eng.localize_on_image(imgs[0], base[0], H, W, focal, opts, n, distortion=D)
     torch.cuda.synchronize()
-    for name, a, b in zip(("coarse", "fine", "exp_avg", "exp_avg_sq", "grad", "packed_c", "packed_f"), before, TL._state(eng)):
+    for name, a, b in zip(("coarse", "fine", "exp_avg", "exp_avg_sq", "grad", "packed_c", "packed_f"), before, ES.state(eng)):
         assert torch.equal(a, b), name
     assert eng.step_count == 0 and eng.localize_count == 5 and D.step_count == 5 and I.step_count == 1 and T.step_count == 1
     assert torch.all(D.dist[:2] != 0) and torch.all(D.dist[2:] == 0) and torch.all(D.g_dist[2:] == 0)
@@ -354,7 +352,7 @@ def _forms(s):
     """{form: (engine, cameras, intrinsics, distortion) -> one step of that form}."""
     img, vw, no_poses = s.image_args(), s.views_args(), s.views_args(poses=False)
     g34 = lambda: torch.empty(3, 4, device=s.dev)  # noqa: E731
-    gv34 = lambda: torch.empty(SF.V, 3, 4, device=s.dev)  # noqa: E731
+    gv34 = lambda: torch.empty(ES.V, 3, 4, device=s.dev)  # noqa: E731
     return {
         "step_on_image distortion": lambda e, T, I, D: e.step_on_image(*img, distortion=D),
         "step_on_image pose_grad intrinsics distortion": lambda e, T, I, D: e.step_on_image(*img, pose_grad=g34(), intrinsics=I, distortion=D),
@@ -372,31 +370,8 @@ def _forms(s):
 
 def _launches():
     """{form: {kernel name: launches}} of the second step of every form (the first one warms up), fresh objects for each."""
-    import ctypes
-    s = SF._Scene()
-    lib = s.N._lib.get_lib()
-    out = {}
-    for form, step in _forms(s).items():
-        eng, T, I = s.engine(world_size=1), s.table(), s.intrinsics()
-        D = s.N.Distortion((-0.05, 0.01, 0.0, 0.0), learn="radial", lr=1e-3, device=s.dev)
-        step(eng, T, I, D)
-        torch.cuda.synchronize()
-        lib.profile_reserve(256)
-        lib.profile_enable(1)
-        try:
-            step(eng, T, I, D)
-            torch.cuda.synchronize()
-        finally:
-            lib.profile_enable(0)
-        buf = ctypes.create_string_buffer(1 << 16)
-        lib.profile_report(buf, len(buf))
-        counts = {}
-        for ln in buf.value.decode().splitlines():   # "kernel_name launches total_ms"
-            parts = ln.rsplit(None, 2)
-            if len(parts) == 3:
-                counts[parts[0]] = counts.get(parts[0], 0) + int(parts[1])
-        out[form] = counts
-    return out
+    s = ES.Scene()
+    return ES.form_launches(s, _forms(s), lambda: (s.engine(world_size=1), s.table(), s.intrinsics(), s.distortion()))
 
 
 def test_every_distortion_step_form_launches_what_the_fixture_recorded():
@@ -437,10 +412,10 @@ def _undistort_torch(xd, yd, kappa):
 
 def _capability_scene(dev, k1_true):
     import nerf_pytorch_amd as N
-    mc, mf, H, W, focal, pose0 = TV._lego(dev)
+    mc, mf, H, W, focal, pose0 = ES.lego(dev)
     for p in list(mc.parameters()) + list(mf.parameters()):
         p.requires_grad_(False)
-    ex, ed = TV._ex_ed()
+    ex, ed = ES.ex_ed()
     opts = N.make_options(64, 64, perturb=False, white_background=True, radiance_field_noise_std=0.0)
     gt0 = torch.from_numpy(pose0).to(dev)
     turn = torch.eye(4, device=dev)
@@ -496,7 +471,7 @@ def test_a_radial_coefficient_is_recovered_on_frozen_nets():
     localize_on_views(distortion=D) steps of RAYS rays, D = Distortion(learn="radial") from zero.  Reference arm: _reference_arm.  The
     bar: the engine arm's final |k1 - k1_true| is at most 3 x the reference arm's (the margin of the three existing capability
     tests); the reference arm alone must end below one fifth of its start, which is what fixed CHOSEN."""
-    dev = TV._dev()
+    dev = ES.dev()
     k1_true, lr, steps = CHOSEN
     scene = _capability_scene(dev, k1_true)
     N, mc, mf, H, W, focal, ex, ed, opts, gts, targets = scene

@@ -14,11 +14,9 @@ import pytest
 import torch
 
 import conftest  # noqa: F401 (first: run as a script, --record, this is what puts the package and the oracle on sys.path)
+import engine_scenes as ES
 import exposure_cases as EC
 import pose_vjp as P
-import test_gpu_localize as TL
-import test_gpu_step_forms as SF
-import test_gpu_views as TV
 
 pytestmark = pytest.mark.gpu
 
@@ -82,7 +80,7 @@ def test_dropin_exposure_loss_is_the_kernels_from_one_node(gpu):
     in rgb.grad and table.grad from ONE node; a table that does not require grad gets none; rgb_fine=None is the coarse-only net;
     other cotangents scale."""
     import nerf_pytorch_amd as N
-    dev = TV._dev()
+    dev = ES.dev()
     c, rc, rf, tgt, inds, table = _case_on(dev)
     lo, gc, gf = EC.loss_views(gpu, c["rc"], c["rf"], c["tgt"], c["inds"], EC.HW, c["table"])
     ge = EC.expo_bwd(gpu, c["rc"], c["rf"], c["tgt"], c["inds"], EC.HW, c["table"])
@@ -131,32 +129,16 @@ def test_dropin_exposure_loss_is_the_kernels_from_one_node(gpu):
 
 def _launches_of(fn):
     """{kernel name: launches} of the library's kernels while fn() runs."""
-    import ctypes
-
     import nerf_pytorch_amd as N
-    lib = N._lib.get_lib()
-    torch.cuda.synchronize()
-    lib.profile_reserve(256)
-    lib.profile_enable(1)
-    try:
+    with N.LaunchProfile() as prof:
         fn()
-        torch.cuda.synchronize()
-    finally:
-        lib.profile_enable(0)
-    buf = ctypes.create_string_buffer(1 << 16)
-    lib.profile_report(buf, len(buf))
-    counts = {}
-    for ln in buf.value.decode().splitlines():   # "kernel_name launches total_ms"
-        parts = ln.rsplit(None, 2)
-        if len(parts) == 3:
-            counts[parts[0]] = counts.get(parts[0], 0) + int(parts[1])
-    return counts
+    return prof.counts()
 
 
 # ---- cameras.Exposure ------------------------------------------------------------------------------------------------------------------
 def test_exposure_object_masks_backward_steps_and_state(gpu):
     import nerf_pytorch_amd as N
-    dev = TV._dev()
+    dev = ES.dev()
     c, rc, rf, tgt, inds, table = _case_on(dev)
     X = N.Exposure(3, learn="affine", lr=1e-2, device=dev)
     assert torch.equal(X.values(), torch.zeros(3, 6, device=dev)) and X.values().data_ptr() == X.expo.data_ptr()
@@ -217,18 +199,18 @@ def test_exposure_object_masks_backward_steps_and_state(gpu):
 
 # ---- the engine ------------------------------------------------------------------------------------------------------------------------
 def _lego_engine(N, dev, overlap=None, **kw):
-    mc, mf, H, W, focal, pose0 = TV._lego(dev)
+    mc, mf, H, W, focal, pose0 = ES.lego(dev)
     eng = N.TrainEngine(mc, mf, 32, 32, perturb=True, white_background=True, noise_std=0.2, seed=3, lr=5e-4, world_size=1, rank=0,
                         overlap=overlap, **kw)
     imgs = torch.rand(3, H, W, 3, generator=torch.Generator().manual_seed(1)).to(dev)
-    return eng, mc, mf, H, W, focal, imgs, TV._views(pose0, dev, 3)
+    return eng, mc, mf, H, W, focal, imgs, ES.views(pose0, dev, 3)
 
 
 def test_a_zero_table_that_learns_nothing_leaves_the_step_what_it_was():
     """Exposure(learn=()) at zero: three steps of step_on_views(exposure=X) give the loss, grad, flat_params and Adam moments of
     step_on_views without it, by torch.equal (fp32 plans, the lego-lowres geometry, 256 rays)."""
     import nerf_pytorch_amd as N
-    dev = TV._dev()
+    dev = ES.dev()
     opts = N.make_options(32, 32)
     res = {}
     for arm in ("with", "without"):
@@ -252,7 +234,7 @@ def test_two_streams_and_one_stream_give_the_same_bits_under_a_table():
     nerfhip_exposure_bwd on the engine's own rgb buffers under X.mask."""
     import nerf_pytorch_amd as N
     from nerf_pytorch_amd.cameras import exposure_grad
-    dev = TV._dev()
+    dev = ES.dev()
     opts = N.make_options(32, 32)
     table = torch.from_numpy(EC.batch(700, 3, True, 4)["table"]).to(dev)
     res = {}
@@ -277,22 +259,22 @@ def test_two_streams_and_one_stream_give_the_same_bits_under_a_table():
 
 def test_the_test_time_fit_alone_leaves_the_nets_alone_and_the_refusals():
     import nerf_pytorch_amd as N
-    dev = TV._dev()
-    mc, mf, H, W, focal, pose0 = TL._small(dev)
+    dev = ES.dev()
+    mc, mf, H, W, focal, pose0 = ES.small(dev)
     V, n = 3, 256
     opts = N.make_options(8, 8)
     imgs = torch.rand(V, H, W, 3, generator=torch.Generator().manual_seed(1)).to(dev)
-    base = TV._views(pose0, dev, V)
+    base = ES.views(pose0, dev, V)
     eng = N.TrainEngine(mc, mf, 8, 8, perturb=True, white_background=True, noise_std=0.2, seed=3, lr=5e-4, world_size=1, rank=0)
     eng.grad.normal_(), eng.exp_avg.normal_(), eng.exp_avg_sq.uniform_()
-    before = TL._state(eng)
+    before = ES.state(eng)
     X = N.Exposure(V, learn="affine", lr=1e-2, device=dev)
     T = N.CameraTable(base, lr=2e-3)
     for _ in range(3):
         eng.localize_on_views(imgs, base, H, W, focal, opts, n, exposure=X)      # the test-time fit alone
     eng.localize_on_views(imgs, None, H, W, focal, opts, n, cameras=T, exposure=X)
     torch.cuda.synchronize()
-    for name, a, b in zip(("coarse", "fine", "exp_avg", "exp_avg_sq", "grad", "packed_c", "packed_f"), before, TL._state(eng)):
+    for name, a, b in zip(("coarse", "fine", "exp_avg", "exp_avg_sq", "grad", "packed_c", "packed_f"), before, ES.state(eng)):
         assert torch.equal(a, b), name
     assert eng.step_count == 0 and eng.localize_count == 4 and X.step_count == 4 and T.step_count == 1
     assert torch.all(X.expo[0] == 0) and torch.all(X.expo[1:] != 0) and torch.all(torch.isfinite(X.expo))
@@ -327,7 +309,7 @@ def test_the_test_time_fit_alone_leaves_the_nets_alone_and_the_refusals():
 def _forms(s):
     """{form: (engine, cameras, intrinsics, distortion, exposure) -> one step of that form}."""
     vw, no_poses = s.views_args(), s.views_args(poses=False)
-    gv34 = lambda: torch.empty(SF.V, 3, 4, device=s.dev)  # noqa: E731
+    gv34 = lambda: torch.empty(ES.V, 3, 4, device=s.dev)  # noqa: E731
     return {
         "step_on_views exposure": lambda e, T, I, D, X: e.step_on_views(*vw, exposure=X),
         "step_on_views pose_grads exposure": lambda e, T, I, D, X: e.step_on_views(*vw, pose_grads=gv34(), exposure=X),
@@ -340,32 +322,8 @@ def _forms(s):
 
 def _launches():
     """{form: {kernel name: launches}} of the second step of every form (the first one warms up), fresh objects for each."""
-    import ctypes
-    s = SF._Scene()
-    lib = s.N._lib.get_lib()
-    out = {}
-    for form, step in _forms(s).items():
-        eng, T, I = s.engine(world_size=1), s.table(), s.intrinsics()
-        D = s.N.Distortion((-0.05, 0.01, 0.0, 0.0), learn="radial", lr=1e-3, device=s.dev)
-        X = s.N.Exposure(SF.V, learn="affine", lr=1e-3, device=s.dev)
-        step(eng, T, I, D, X)
-        torch.cuda.synchronize()
-        lib.profile_reserve(256)
-        lib.profile_enable(1)
-        try:
-            step(eng, T, I, D, X)
-            torch.cuda.synchronize()
-        finally:
-            lib.profile_enable(0)
-        buf = ctypes.create_string_buffer(1 << 16)
-        lib.profile_report(buf, len(buf))
-        counts = {}
-        for ln in buf.value.decode().splitlines():   # "kernel_name launches total_ms"
-            parts = ln.rsplit(None, 2)
-            if len(parts) == 3:
-                counts[parts[0]] = counts.get(parts[0], 0) + int(parts[1])
-        out[form] = counts
-    return out
+    s = ES.Scene()
+    return ES.form_launches(s, _forms(s), lambda: (s.engine(world_size=1), s.table(), s.intrinsics(), s.distortion(), s.exposure()))
 
 
 BACKWARD = ("bwd", "dgrad", "wgrad")                                          # what a render backward launches
@@ -377,7 +335,7 @@ def test_every_exposure_step_form_launches_what_the_fixture_recorded():
         want = json.load(f)
     got = _launches()
     assert sorted(got) == sorted(want) and len(got) == 5
-    with open(SF.FIXTURE) as f:
+    with open(ES.STEP_LAUNCHES) as f:
         plain = json.load(f)["step_on_views"]
     for form in want:
         assert got[form] and got[form] == want[form], (form, got[form], want[form])
@@ -408,10 +366,10 @@ TRUE_ROWS = ((0.0, 0.0, 0.0, 0.0, 0.0, 0.0),            # view 0: untouched, the
 
 def _capability_scene(dev):
     import nerf_pytorch_amd as N
-    mc, mf, H, W, focal, pose0 = TV._lego(dev)
+    mc, mf, H, W, focal, pose0 = ES.lego(dev)
     for p in list(mc.parameters()) + list(mf.parameters()):
         p.requires_grad_(False)
-    ex, ed = TV._ex_ed()
+    ex, ed = ES.ex_ed()
     opts = N.make_options(64, 64, perturb=False, white_background=True, radiance_field_noise_std=0.0)
     gt0 = torch.from_numpy(pose0).to(dev)
     gts = [gt0]
@@ -467,12 +425,12 @@ def test_the_exposure_of_re_exposed_views_is_recovered_on_frozen_nets():
     localize_on_views(exposure=X) steps of RAYS rays, X = Exposure(3, learn="affine") from zero.  Reference arm: _reference_arm.  The
     bar: the engine arm's final max |row - true| is at most 3 x the reference arm's (the project's margin for an optimiser trajectory
     compared across two arithmetic paths); the reference arm alone must end below one fifth of its start, which is what fixed CHOSEN."""
-    dev = TV._dev()
+    dev = ES.dev()
     lr, steps = CHOSEN
     scene = _capability_scene(dev)
     N, mc, mf, H, W, focal, ex, ed, opts, gts, targets, true = scene
     eng = N.TrainEngine(mc, mf, 64, 64, perturb=False, white_background=True, noise_std=0.0, lr=0.0, world_size=1, rank=0)
-    before = TL._state(eng)
+    before = ES.state(eng)
     X = N.Exposure(3, learn="affine", lr=lr, device=dev)
     curve_e = [(-1, _error(X.expo, true))]
     for it in range(steps):
@@ -480,7 +438,7 @@ def test_the_exposure_of_re_exposed_views_is_recovered_on_frozen_nets():
         if it % 50 == 0 or it == steps - 1:
             curve_e.append((it, _error(X.expo, true)))
     assert torch.all(X.expo[0] == 0) and torch.all(torch.isfinite(X.expo)) and eng.localize_count == steps and eng.step_count == 0
-    for a, b in zip(before, TL._state(eng)):
+    for a, b in zip(before, ES.state(eng)):
         assert torch.equal(a, b)
     curve_r = _reference_arm(scene, lr, steps, eng.seed)
     print("exposure recovery, engine arm (step, max |row - true|): %s" % curve_e)

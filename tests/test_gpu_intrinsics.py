@@ -7,9 +7,9 @@ import numpy as np
 import pytest
 import torch
 
+import engine_scenes as ES
 import intrinsics_cases as IC
 import pose_vjp as P
-import test_gpu_views as TV
 
 pytestmark = pytest.mark.gpu
 
@@ -78,14 +78,14 @@ def test_dropin_intrinsics_gradient_is_the_kernel_and_none_is_the_existing_path(
     call; the forward is the plain launch; intrinsics=None is today's node and function; the bundle forms take the intrinsics
     forward only."""
     import nerf_pytorch_amd as N
-    dev = TV._dev()
-    _, _, H, W, focal, pose0 = TV._lego(dev)
+    dev = ES.dev()
+    _, _, H, W, focal, pose0 = ES.lego(dev)
     V, n = 3, 700
     g = torch.Generator().manual_seed(8)
     imgs = torch.rand(V, H, W, 3, generator=g).to(dev)
     gr = torch.randn(n, 11, generator=g).to(dev)
     opts = N.make_options(64, 64)
-    poses = TV._views(pose0, dev, V)
+    poses = ES.views(pose0, dev, V)
     intr = torch.tensor([focal * 1.03, focal * 0.98, W * 0.5 + 1.25, H * 0.5 - 0.75], dtype=torch.float32, device=dev)
     plain = N.select_training_rays_views(H, W, focal, poses, imgs, n, opts, seed=4, step=1, intrinsics=intr)
     assert plain[0].grad_fn is None
@@ -150,7 +150,7 @@ def test_dropin_intrinsics_gradient_is_the_kernel_and_none_is_the_existing_path(
 # ---- cameras.Intrinsics and the engine ------------------------------------------------------------------------------------------------
 def test_intrinsics_object_values_masks_and_state():
     import nerf_pytorch_amd as N
-    dev = TV._dev()
+    dev = ES.dev()
     I = N.Intrinsics(378, 504, 407.5, learn="focal", lr=1e-2, device=dev)
     assert torch.equal(I.values(), torch.tensor([407.5, 407.5, 252.0, 189.0], device=dev))
     g = torch.tensor([0.5, -0.25, 3.0, -2.0], device=dev)
@@ -202,15 +202,15 @@ def _by_hand(eng, N, T, I, imgs, H, W, focal, opts, n):
 def test_step_on_views_with_intrinsics_equals_its_parts():
     """Five steps of step_on_views(cameras=T, intrinsics=I) against the same calls made by hand: loss, nets, twists and q on the bits."""
     import nerf_pytorch_amd as N
-    dev = TV._dev()
+    dev = ES.dev()
     V, n = 3, 256
     opts = N.make_options(32, 32)
     res = {}
     for arm in ("engine", "parts"):
-        mc, mf, H, W, focal, pose0 = TV._lego(dev)
+        mc, mf, H, W, focal, pose0 = ES.lego(dev)
         eng = N.TrainEngine(mc, mf, 32, 32, perturb=True, white_background=True, noise_std=0.2, seed=3, lr=5e-4, world_size=1, rank=0)
         imgs = torch.rand(V, H, W, 3, generator=torch.Generator().manual_seed(1)).to(dev)
-        T = N.CameraTable(TV._views(pose0, dev, V), lr=2e-3)
+        T = N.CameraTable(ES.views(pose0, dev, V), lr=2e-3)
         I = N.Intrinsics(H, W, focal * 1.02, learn="all", lr=1e-3, device=dev)
         seen = []
         for _ in range(5):
@@ -232,15 +232,15 @@ def test_intrinsics_that_learn_nothing_leave_the_step_what_it_was():
     """learn=() at the scalar camera's values: after five steps nets, twists and loss are those of step_on_views(cameras=T) without
     intrinsics, on the bits (the same rays, the same pose gradients)."""
     import nerf_pytorch_amd as N
-    dev = TV._dev()
+    dev = ES.dev()
     V, n = 3, 256
     opts = N.make_options(32, 32)
     res = {}
     for arm in ("with", "without"):
-        mc, mf, H, W, focal, pose0 = TV._lego(dev)
+        mc, mf, H, W, focal, pose0 = ES.lego(dev)
         eng = N.TrainEngine(mc, mf, 32, 32, perturb=True, white_background=True, noise_std=0.2, seed=3, lr=5e-4, world_size=1, rank=0)
         imgs = torch.rand(V, H, W, 3, generator=torch.Generator().manual_seed(1)).to(dev)
-        T = N.CameraTable(TV._views(pose0, dev, V), lr=2e-3)
+        T = N.CameraTable(ES.views(pose0, dev, V), lr=2e-3)
         I = N.Intrinsics(H, W, focal, learn=(), device=dev) if arm == "with" else None
         for _ in range(5):
             loss = eng.step_on_views(imgs, None, H, W, focal, opts, n, cameras=T, intrinsics=I)
@@ -254,23 +254,22 @@ def test_intrinsics_that_learn_nothing_leave_the_step_what_it_was():
 
 def test_localize_with_intrinsics_leaves_the_nets_alone_and_refusals():
     import nerf_pytorch_amd as N
-    import test_gpu_localize as TL
-    dev = TV._dev()
-    mc, mf, H, W, focal, pose0 = TL._small(dev)
+    dev = ES.dev()
+    mc, mf, H, W, focal, pose0 = ES.small(dev)
     V, n = 3, 256
     opts = N.make_options(8, 8)
     imgs = torch.rand(V, H, W, 3, generator=torch.Generator().manual_seed(1)).to(dev)
-    base = TV._views(pose0, dev, V)
+    base = ES.views(pose0, dev, V)
     eng = N.TrainEngine(mc, mf, 8, 8, perturb=True, white_background=True, noise_std=0.2, seed=3, lr=5e-4, world_size=1, rank=0)
     eng.grad.normal_(), eng.exp_avg.normal_(), eng.exp_avg_sq.uniform_()
-    before = TL._state(eng)
+    before = ES.state(eng)
     I = N.Intrinsics(H, W, focal * 1.05, learn="focal", lr=1e-3, device=dev)
     for _ in range(3):
         eng.localize_on_views(imgs, base, H, W, focal, opts, n, intrinsics=I)     # the intrinsics alone
     pg = torch.full((3, 4), float("nan"), device=dev)
     eng.localize_on_image(imgs[0], base[0], H, W, focal, opts, n, pose_grad=pg, intrinsics=I)
     torch.cuda.synchronize()
-    for name, a, b in zip(("coarse", "fine", "exp_avg", "exp_avg_sq", "grad", "packed_c", "packed_f"), before, TL._state(eng)):
+    for name, a, b in zip(("coarse", "fine", "exp_avg", "exp_avg_sq", "grad", "packed_c", "packed_f"), before, ES.state(eng)):
         assert torch.equal(a, b), name
     assert eng.step_count == 0 and eng.localize_count == 4 and I.step_count == 4
     assert float(I.q[0]) != 0 and torch.all(I.q[1:] == 0) and torch.all(torch.isfinite(pg)) and float(pg.abs().sum()) > 0
@@ -296,11 +295,11 @@ def test_a_focal_five_per_cent_off_is_recovered_on_frozen_nets():
     tests/test_gpu_cameras.py give two chaotic 300-step runs); the reference arm alone must end below one fifth of its start.
     Measured (MI355X, STEPS = 300, LR = 3e-3): see profiles/r13_intrinsics.json, "capability"."""
     import nerf_pytorch_amd as N
-    dev = TV._dev()
-    mc, mf, H, W, f_true, pose0 = TV._lego(dev)
+    dev = ES.dev()
+    mc, mf, H, W, f_true, pose0 = ES.lego(dev)
     for p in list(mc.parameters()) + list(mf.parameters()):
         p.requires_grad_(False)
-    ex, ed = TV._ex_ed()
+    ex, ed = ES.ex_ed()
     opts = N.make_options(64, 64, perturb=False, white_background=True, radiance_field_noise_std=0.0)
     gt0 = torch.from_numpy(pose0).to(dev)
     turn = torch.eye(4, device=dev)

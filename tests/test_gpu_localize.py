@@ -7,10 +7,10 @@ import numpy as np
 import pytest
 import torch
 
+import engine_scenes as ES
 import localize_cases as LC
 import parity_cases as PC
 import pose_vjp as P
-import test_gpu_views as TV
 
 pytestmark = pytest.mark.gpu
 
@@ -94,39 +94,22 @@ def test_entry_point_rejects_bad_arguments(gpu):
 
 
 # ---- the engine -------------------------------------------------------------------------------------------------------------------------
-CFG64 = dict(num_layers=4, hidden_size=64, skip_connect_every=4, num_encoding_fn_xyz=6, num_encoding_fn_dir=4)
-
-
-def _small(dev, seed=11):
-    import nerf_pytorch_amd as N
-    torch.manual_seed(seed)
-    mc, mf = N.FlexibleNeRFModel(**CFG64).to(dev), N.FlexibleNeRFModel(**CFG64).to(dev)
-    for p in list(mc.parameters()) + list(mf.parameters()):
-        p.requires_grad_(False)
-    _, _, H, W, focal, pose0 = TV._lego(dev)
-    return mc, mf, H, W, focal, pose0
-
-
-def _state(eng):
-    return [t.clone() for t in (eng.mc.flat_params, eng.mf.flat_params, eng.exp_avg, eng.exp_avg_sq, eng.grad, eng.packed_c, eng.packed_f)]
-
-
 def test_localize_leaves_the_nets_and_their_optimizer_alone():
     """Three localize_on_views steps with pose_grads, then three with a camera table: parameters, Adam moments, the gradient buffer
     and both packed images are what they were on the bits, step_count has not moved, localize_count counts, the table's twists move."""
     import nerf_pytorch_amd as N
-    dev = TV._dev()
-    mc, mf, H, W, focal, pose0 = _small(dev)
+    dev = ES.dev()
+    mc, mf, H, W, focal, pose0 = ES.small(dev)
     V, n = 3, 256
     opts = N.make_options(8, 8)
     imgs = torch.rand(V, H, W, 3, generator=torch.Generator().manual_seed(1)).to(dev)
-    base = TV._views(pose0, dev, V)
+    base = ES.views(pose0, dev, V)
     for use_table in (False, True):
         eng = N.TrainEngine(mc, mf, 8, 8, perturb=True, white_background=True, noise_std=0.2, seed=3, lr=5e-4, world_size=1, rank=0)
         eng.grad.normal_()     # (what a training step left there stays there)
         eng.exp_avg.normal_()
         eng.exp_avg_sq.uniform_()
-        before = _state(eng)
+        before = ES.state(eng)
         T = N.CameraTable(base, lr=2e-3) if use_table else None
         grads = []
         for _ in range(3):
@@ -137,7 +120,7 @@ def test_localize_leaves_the_nets_and_their_optimizer_alone():
                 eng.localize_on_views(imgs, base, H, W, focal, opts, n, pose_grads=pg)
                 grads.append(pg)
         torch.cuda.synchronize()
-        for name, a, b in zip(("coarse", "fine", "exp_avg", "exp_avg_sq", "grad", "packed_c", "packed_f"), before, _state(eng)):
+        for name, a, b in zip(("coarse", "fine", "exp_avg", "exp_avg_sq", "grad", "packed_c", "packed_f"), before, ES.state(eng)):
             assert torch.equal(a, b), (use_table, name)
         assert eng.step_count == 0 and eng.localize_count == 3
         if use_table:
@@ -151,16 +134,16 @@ def test_localize_leaves_the_nets_and_their_optimizer_alone():
 def test_localize_on_views_equals_its_parts_and_two_streams_equal_one():
     import nerf_pytorch_amd as N
     from nerf_pytorch_amd.train_utils import select_training_rays_views, select_training_rays_views_bwd
-    dev = TV._dev()
+    dev = ES.dev()
     V, n = 3, 256
     opts = N.make_options(8, 8)
     res = {}
     for arm in ("whole", "parts", "one_stream"):
-        mc, mf, H, W, focal, pose0 = _small(dev)
+        mc, mf, H, W, focal, pose0 = ES.small(dev)
         eng = N.TrainEngine(mc, mf, 8, 8, perturb=True, white_background=True, noise_std=0.2, seed=3, world_size=1, rank=0,
                             overlap=arm != "one_stream")
         imgs = torch.rand(V, H, W, 3, generator=torch.Generator().manual_seed(1)).to(dev)
-        poses = TV._views(pose0, dev, V)
+        poses = ES.views(pose0, dev, V)
         seen = []
         for it in range(3):
             pg = torch.full((V, 3, 4), float("nan"), device=dev)
@@ -189,9 +172,9 @@ def test_dropin_frozen_pose_gradient_equals_the_engine_and_leaves_no_parameter_g
     kernel adds its two buffers row by row); no parameter has a gradient; the node keeps the flag of its forward."""
     import nerf_pytorch_amd as N
     from nerf_pytorch_amd.train_utils import select_training_rays_bwd
-    dev = TV._dev()
-    mc, mf, H, W, focal, pose0 = TV._lego(dev)
-    ex, ed = TV._ex_ed()
+    dev = ES.dev()
+    mc, mf, H, W, focal, pose0 = ES.lego(dev)
+    ex, ed = ES.ex_ed()
     opts = N.make_options(64, 64, perturb=True, white_background=True, radiance_field_noise_std=0.0)
     n = 512
     g = torch.Generator().manual_seed(4)
@@ -209,7 +192,7 @@ def test_dropin_frozen_pose_gradient_equals_the_engine_and_leaves_no_parameter_g
     for switch in (False, True):
         leaf = torch.from_numpy(pose0).to(dev).requires_grad_(True)
         rays, tgt, used = N.select_training_rays(H, W, focal, leaf, img, n, opts, seed=9, step=0)
-        real = TV._queue_draws([draws[0], draws[2]])
+        real = ES.queue_draws([draws[0], draws[2]])
         try:
             out = N.predict_and_render_radiance(rays, mc, mf, opts, encode_position_fn=ex, encode_direction_fn=ed)
         finally:
@@ -234,10 +217,10 @@ def test_dropin_frozen_pose_gradient_equals_the_engine_and_leaves_no_parameter_g
 
 def test_localize_refuses_what_it_cannot_do():
     import nerf_pytorch_amd as N
-    dev = TV._dev()
-    mc, mf, H, W, focal, pose0 = _small(dev)
+    dev = ES.dev()
+    mc, mf, H, W, focal, pose0 = ES.small(dev)
     V = 2
-    T = N.CameraTable(TV._views(pose0, dev, V))
+    T = N.CameraTable(ES.views(pose0, dev, V))
     imgs = torch.zeros(V, H, W, 3, device=dev)
     opts = N.make_options(8, 8)
     eng = N.TrainEngine(mc, mf, 8, 8, world_size=1, rank=0)
@@ -268,11 +251,11 @@ def test_two_perturbed_poses_are_recovered_by_localize_on_views():
     step_on_views(lr=0.0, cameras=T): every final error is below its start and at most 3x the yardstick's (the two runs share
     kernels up to the ray gradient's summation order; x3 is what the sibling tests give two such runs over 300 chaotic steps)."""
     import nerf_pytorch_amd as N
-    dev = TV._dev()
-    mc, mf, H, W, focal, pose0 = TV._lego(dev)
+    dev = ES.dev()
+    mc, mf, H, W, focal, pose0 = ES.lego(dev)
     for p in list(mc.parameters()) + list(mf.parameters()):
         p.requires_grad_(False)
-    ex, ed = TV._ex_ed()
+    ex, ed = ES.ex_ed()
     opts = N.make_options(64, 64, perturb=False, white_background=True, radiance_field_noise_std=0.0)
     gt0 = torch.from_numpy(pose0).to(dev)
     turn = torch.eye(4, device=dev)
@@ -289,7 +272,7 @@ def test_two_perturbed_poses_are_recovered_by_localize_on_views():
     for axis, shift in (([0.3, -0.8, 0.5], [0.03, -0.03, 0.0277]), ([-0.6, 0.2, 0.7], [-0.0277, 0.03, 0.03])):
         axis = torch.tensor(axis)
         deltas.append(torch.cat([axis / axis.norm() * np.deg2rad(2.0), torch.tensor(shift)]).float().to(dev))
-    starts = torch.stack([(gts[v] @ TV._se3(deltas[v])).detach() for v in range(2)])
+    starts = torch.stack([(gts[v] @ ES.se3(deltas[v])).detach() for v in range(2)])
     gts64 = gts.cpu().numpy().astype(np.float64)
 
     def errors(est, v):

@@ -7,10 +7,10 @@ import numpy as np
 import pytest
 import torch
 
+import engine_scenes as ES
 import occupancy_cases as OC
 import occupancy_train_cases as OT
 import parity_cases as P
-from conftest import gold
 
 pytestmark = pytest.mark.gpu
 
@@ -60,36 +60,13 @@ def test_refusals(gpu):
 
 
 # ---- the engine ----------------------------------------------------------------------------------------------------------------
-CFG = dict(num_layers=4, hidden_size=128, skip_connect_every=4, num_encoding_fn_xyz=10, num_encoding_fn_dir=4)
-AABB = ((-1.5, -1.5, -1.5), (1.5, 1.5, 1.5))
+AABB = ES.AABB
 SAMPLING = dict(num_coarse=64, num_fine=64, perturb=False, white_background=True, noise_std=0.0)
-
-
-def make_lego():
-    """The lego-lowres fixture nets, the fixture pose cut to 64 x 64 rays with a random target, and ONE grid from from_models at its
-    defaults."""
-    import nerf_pytorch_amd as N
-    dev = torch.device("cuda", 0)
-    w, r = gold("lego_lowres_weights.npz"), gold("lego_lowres_render.npz")
-    mc, mf = N.FlexibleNeRFModel(**CFG), N.FlexibleNeRFModel(**CFG)
-    mc.load_state_dict({k[2:]: torch.from_numpy(w[k]) for k in w.files if k.startswith("c_")})
-    mf.load_state_dict({k[2:]: torch.from_numpy(w[k]) for k in w.files if k.startswith("f_")})
-    mc, mf = mc.to(dev), mf.to(dev)
-    H = W = 64
-    focal = float(r["focal"]) * 64.0 / float(r["W"])
-    pose = torch.from_numpy(r["pose"]).to(dev)
-    opts = N.make_options(64, 64, perturb=False, white_background=True, radiance_field_noise_std=0.0)
-    pix = torch.arange(H * W, dtype=torch.int64, device=dev)
-    ro, rd = N.get_rays_at_pixels(H, W, focal, pose[:3, :4], pix)
-    rays = N.pack_rays(ro, rd, opts, H, W, focal)
-    target = torch.rand(H * W, 3, generator=torch.Generator().manual_seed(3)).to(dev)
-    grid = N.OccupancyGrid.from_models(mc, mf, AABB)
-    return dict(N=N, dev=dev, mc=mc, mf=mf, H=H, W=W, focal=focal, pose=pose, opts=opts, rays=rays, target=target, grid=grid)
 
 
 @pytest.fixture(scope="module")
 def lego(gpu):
-    return make_lego()
+    return ES.lego64()
 
 
 def _engine(s, **kw):

@@ -5,41 +5,12 @@ import numpy as np
 import pytest
 import torch
 
+import engine_scenes as ES
 import pose_vjp as P
-from conftest import gold
 
 pytestmark = pytest.mark.gpu
 
 CFG = dict(num_layers=4, hidden_size=128, skip_connect_every=4, num_encoding_fn_xyz=10, num_encoding_fn_dir=4)
-
-
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU visible")
-    return torch.device("cuda", 0)
-
-
-def _lego(dev):
-    import nerf_pytorch_amd as N
-    w, r = gold("lego_lowres_weights.npz"), gold("lego_lowres_render.npz")
-    mc, mf = N.FlexibleNeRFModel(**CFG), N.FlexibleNeRFModel(**CFG)
-    mc.load_state_dict({k[2:]: torch.from_numpy(w[k]) for k in w.files if k.startswith("c_")})
-    mf.load_state_dict({k[2:]: torch.from_numpy(w[k]) for k in w.files if k.startswith("f_")})
-    return mc.to(dev), mf.to(dev), int(r["H"]), int(r["W"]), float(np.float32(r["focal"])), r["pose"].astype(np.float32)
-
-
-def _se3(xi):
-    """4 x 4 transform of a twist-like 6-vector (rotation by Rodrigues' formula, translation as given)."""
-    T = torch.zeros(4, 4, dtype=xi.dtype, device=xi.device)
-    T = T + torch.nn.functional.pad(P.rodrigues(xi[:3]), (0, 1, 0, 1))
-    T = T + torch.nn.functional.pad(xi[3:, None], (3, 0, 0, 1))
-    T = T + torch.nn.functional.pad(torch.ones(1, 1, dtype=xi.dtype, device=xi.device), (3, 0, 3, 0))
-    return T
-
-
-def _ex_ed():
-    import nerf_pytorch_amd as N
-    return N.get_embedding_function(10, True, True), N.get_embedding_function(4, True, True)
 
 
 def _close(got, want, mag, n, what):
@@ -50,7 +21,7 @@ def _close(got, want, mag, n, what):
 
 def test_dropin_pose_gradient_exists_matches_oracle_and_keeps_the_forward():
     import nerf_pytorch_amd as N
-    dev = _dev()
+    dev = ES.dev()
     H, W, focal = 21, 34, float(np.float32(30.5))
     g = torch.Generator().manual_seed(0)
     base = torch.eye(4)
@@ -119,18 +90,18 @@ def test_reference_loop_backpropagates_to_the_pose(no_ndc):
     pose = pose0 @ exp(xi): xi.grad is filled, and pose.grad is fp64 oracle autograd of get_ray_bundle applied to the ray
     cotangents captured with retain_grad() (isolating the new layer from the sampler's conditioning)."""
     import nerf_pytorch_amd as N
-    dev = _dev()
-    mc, mf, H, W, focal, pose0 = _lego(dev)
+    dev = ES.dev()
+    mc, mf, H, W, focal, pose0 = ES.lego(dev)
     near_far = dict(near=2.0, far=6.0)
     if not no_ndc:  # (LLFF options; NDC space misses the lego scene, so untrained nets give the render something to differentiate)
         torch.manual_seed(5)
         mc, mf = N.FlexibleNeRFModel(**CFG).to(dev), N.FlexibleNeRFModel(**CFG).to(dev)
         near_far = dict(near=0.0, far=1.0)
-    ex, ed = _ex_ed()
+    ex, ed = ES.ex_ed()
     opts = N.make_options(64, 64, perturb=True, white_background=True, radiance_field_noise_std=0.0, no_ndc=no_ndc, **near_far)
     torch.manual_seed(3)
     xi = (torch.randn(6) * 0.01).to(dev).requires_grad_(True)
-    pose = torch.from_numpy(pose0).to(dev) @ _se3(xi)
+    pose = torch.from_numpy(pose0).to(dev) @ ES.se3(xi)
     pose.retain_grad()
     ro, rd = N.get_ray_bundle(H, W, focal, pose[:3, :4])
     ro.retain_grad(), rd.retain_grad()
@@ -148,14 +119,6 @@ def test_reference_loop_backpropagates_to_the_pose(no_ndc):
            "reference loop no_ndc=%s" % no_ndc)
 
 
-def _queue_draws(draws):
-    queue = list(draws)
-    real = torch.rand, torch.randn
-    torch.rand = lambda *a, **k: queue.pop(0)
-    torch.randn = lambda *a, **k: queue.pop(0)
-    return real
-
-
 @pytest.mark.parametrize("precision", ["fp32", "f16x3_train"])
 @pytest.mark.parametrize("backward", [None, "auto"])
 def test_engine_pose_gradient_equals_dropin(precision, backward):
@@ -165,13 +128,13 @@ def test_engine_pose_gradient_equals_dropin(precision, backward):
     dropped), so the two pose gradients agree to 1e-4 of their norm (fp32 rounding of a sum of ~10^5 terms, with margin)."""
     import nerf_pytorch_amd as N
     from nerf_pytorch_amd.train_utils import select_training_rays_bwd
-    dev = _dev()
-    mc, mf, H, W, focal, pose0 = _lego(dev)
+    dev = ES.dev()
+    mc, mf, H, W, focal, pose0 = ES.lego(dev)
     if precision != "fp32":
         mc.set_training_precision(precision), mf.set_training_precision(precision)
     if backward == "auto":
         mc.set_backward_compaction("auto"), mf.set_backward_compaction("auto")
-    ex, ed = _ex_ed()
+    ex, ed = ES.ex_ed()
     opts = N.make_options(64, 64, perturb=True, white_background=True, radiance_field_noise_std=0.0)
     n = 1024
     g = torch.Generator().manual_seed(4)
@@ -179,7 +142,7 @@ def test_engine_pose_gradient_equals_dropin(precision, backward):
     draws = (torch.rand(n, 64, generator=g).to(dev), None, torch.rand(n, 64, generator=g).to(dev), None)
     leaf = torch.from_numpy(pose0).to(dev).requires_grad_(True)
     rays, tgt, used = N.select_training_rays(H, W, focal, leaf, img, n, opts, seed=9, step=0)
-    real = _queue_draws([draws[0], draws[2]])
+    real = ES.queue_draws([draws[0], draws[2]])
     try:
         out = N.predict_and_render_radiance(rays, mc, mf, opts, encode_position_fn=ex, encode_direction_fn=ed)
     finally:
@@ -202,10 +165,10 @@ def test_engine_pose_gradient_two_stream_equals_one_stream():
     """Extends test_two_stream_step_equals_single_stream_step's invariant to pose_grad: the coarse part of the ray gradient lands
     in its own buffer on the side stream and the pose kernel adds the two parts row by row -- the same bits in both orders."""
     import nerf_pytorch_amd as N
-    dev = _dev()
+    dev = ES.dev()
     outs = []
     for overlap in (True, False):
-        mc, mf, H, W, focal, pose0 = _lego(dev)
+        mc, mf, H, W, focal, pose0 = ES.lego(dev)
         eng = N.TrainEngine(mc, mf, 32, 32, perturb=True, white_background=True, noise_std=0.2, seed=3, world_size=1, rank=0,
                             overlap=overlap)
         img = torch.rand(H, W, 3, generator=torch.Generator().manual_seed(1)).to(dev)
@@ -223,8 +186,8 @@ def test_engine_pose_gradient_two_stream_equals_one_stream():
 
 def test_engine_pose_gradient_refuses_data_parallel_steps():
     import nerf_pytorch_amd as N
-    dev = _dev()
-    mc, mf, H, W, focal, pose0 = _lego(dev)
+    dev = ES.dev()
+    mc, mf, H, W, focal, pose0 = ES.lego(dev)
     eng = N.TrainEngine(mc, mf, 32, 32, world_size=2, rank=0)
     img = torch.rand(H, W, 3, device=dev)
     with pytest.raises(NotImplementedError, match="world size 2"):
@@ -241,10 +204,10 @@ STEPS, LR, RAYS = 300, 3e-3, 1024
 
 def _recover(dev, through_engine):
     import nerf_pytorch_amd as N
-    mc, mf, H, W, focal, pose0 = _lego(dev)
+    mc, mf, H, W, focal, pose0 = ES.lego(dev)
     for p in list(mc.parameters()) + list(mf.parameters()):
         p.requires_grad_(False)
-    ex, ed = _ex_ed()
+    ex, ed = ES.ex_ed()
     opts_val = N.make_options(64, 64, perturb=False, white_background=True, radiance_field_noise_std=0.0)
     gt = torch.from_numpy(pose0).to(dev)
     with torch.no_grad():
@@ -254,7 +217,7 @@ def _recover(dev, through_engine):
     # the start: ~2 degrees about a fixed axis and 0.05 units
     axis = torch.tensor([0.3, -0.8, 0.5], dtype=torch.float32)
     delta = torch.cat([axis / axis.norm() * np.deg2rad(2.0), torch.tensor([0.03, -0.03, 0.0277])]).to(dev)
-    start = (gt @ _se3(delta)).detach()
+    start = (gt @ ES.se3(delta)).detach()
     xi = torch.zeros(6, device=dev, requires_grad=True)
     opt = torch.optim.Adam([xi], lr=LR)
     eng = N.TrainEngine(mc, mf, 64, 64, perturb=False, white_background=True, noise_std=0.0, lr=0.0, world_size=1,
@@ -262,7 +225,7 @@ def _recover(dev, through_engine):
     pg = torch.empty(3, 4, device=dev)
 
     def errors():
-        est = (start @ _se3(xi)).detach().cpu().numpy().astype(np.float64)
+        est = (start @ ES.se3(xi)).detach().cpu().numpy().astype(np.float64)
         g = pose0.astype(np.float64)
         return P.rot_angle_deg(est[:3, :3].T @ g[:3, :3]), float(np.linalg.norm(est[:3, 3] - g[:3, 3]))
 
@@ -270,7 +233,7 @@ def _recover(dev, through_engine):
 
     for it in range(STEPS):
         opt.zero_grad()
-        pose = start @ _se3(xi)
+        pose = start @ ES.se3(xi)
         if through_engine:
             eng.step_on_image(target, pose.detach(), H, W, focal, opts_val, RAYS, lr=0.0, pose_grad=pg)
             torch.autograd.backward(pose[:3, :4], pg)
@@ -292,7 +255,7 @@ def test_perturbed_pose_is_recovered_on_frozen_nets(through_engine):
     with lr=0 for the nets.  Rotation and translation errors each fall at least 4x below their starting values.
     Measured on MI355X (profiles/r07_pose_grad.json): 2.00 deg / 0.0507 -> 0.079 deg / 0.0058 (drop-in) and 0.068 deg / 0.0027
     (engine) after 300 steps, i.e. 25-29x in rotation and 8.7-19x in translation: the 4x asserted leaves a factor >= 2 of margin."""
-    dev = _dev()
+    dev = ES.dev()
     curve = _recover(dev, through_engine)
     print("pose recovery (%s): %s" % ("engine" if through_engine else "drop-in", curve))
     (_, r0, t0), (_, r1, t1) = curve[0], curve[-1]

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import engine_scenes as ES
 import spread_cases as S
 from conftest import gold
 
@@ -209,8 +210,7 @@ LAMBDA_CAP = 0.1
 
 @pytest.fixture(scope="module")
 def lego64(gpu):
-    import test_gpu_occupancy_train as T
-    return T.make_lego()
+    return ES.lego64()
 
 
 def _capability_arm(s, seed, lam, steps=400, n_rays=1024, lr=5e-3, noise_std=1.0):

@@ -5,49 +5,20 @@ tests/step_launches.json, recorded by this module:
 
     python tests/test_gpu_step_forms.py --record tests/step_launches.json
 
-The small nets of test_gpu_localize._small, 8 + 8 samples, 256 rays, V = 3, the dense backward."""
-import ctypes
+The step scene of tests/engine_scenes.py: its small nets, 8 + 8 samples, 256 rays, V = 3, the dense backward."""
 import json
-import os
 import sys
 
 import pytest
 import torch
 
 import conftest  # noqa: F401 (first: run as a script, --record, this is what puts the package and the oracle on sys.path)
-import test_gpu_localize as TL
-import test_gpu_views as TV
+import engine_scenes as ES
 
 pytestmark = pytest.mark.gpu
 
-FIXTURE = os.path.join(conftest.ROOT, "tests", "step_launches.json")
-V, RAYS = 3, 256
-
-
-class _Scene:
-    def __init__(self):
-        import nerf_pytorch_amd as N
-        self.N, self.dev = N, TV._dev()
-        self.mc, self.mf, self.H, self.W, self.focal, pose0 = TL._small(self.dev)
-        self.opts = N.make_options(8, 8)
-        self.imgs = torch.rand(V, self.H, self.W, 3, generator=torch.Generator().manual_seed(1)).to(self.dev)
-        self.base = TV._views(pose0, self.dev, V)
-
-    def engine(self, **kw):
-        return self.N.TrainEngine(self.mc, self.mf, 8, 8, perturb=True, white_background=True, noise_std=0.2, seed=3, lr=5e-4, rank=0,
-                                  backward="dense", **kw)
-
-    def table(self):
-        return self.N.CameraTable(self.base, lr=2e-3)
-
-    def intrinsics(self):
-        return self.N.Intrinsics(self.H, self.W, self.focal * 1.02, learn="all", lr=1e-3, device=self.dev)
-
-    def image_args(self):
-        return (self.imgs[0], self.base[0], self.H, self.W, self.focal, self.opts, RAYS)
-
-    def views_args(self, poses=True):
-        return (self.imgs, self.base if poses else None, self.H, self.W, self.focal, self.opts, RAYS)
+FIXTURE = ES.STEP_LAUNCHES
+V = ES.V
 
 
 # ---- a. refusals ------------------------------------------------------------------------------------------------------------------------
@@ -125,7 +96,7 @@ def _refusals(s):
 
 
 def test_step_forms_refuse_what_they_cannot_do():
-    rows, (one, two, T, I) = _refusals(_Scene())
+    rows, (one, two, T, I) = _refusals(ES.Scene())
     wrong = []
     for label, call, exc, text in rows:
         try:
@@ -170,29 +141,8 @@ def _forms(s):
 def _launches():
     """{form: {kernel name: launches}} of the second step of every form (the first one warms up), a fresh engine, table and
     Intrinsics for each."""
-    s = _Scene()
-    lib = s.N._lib.get_lib()
-    out = {}
-    for form, step in _forms(s).items():
-        eng, T, I = s.engine(world_size=1), s.table(), s.intrinsics()
-        step(eng, T, I)
-        torch.cuda.synchronize()
-        lib.profile_reserve(256)
-        lib.profile_enable(1)
-        try:
-            step(eng, T, I)
-            torch.cuda.synchronize()
-        finally:
-            lib.profile_enable(0)
-        buf = ctypes.create_string_buffer(1 << 16)
-        lib.profile_report(buf, len(buf))
-        counts = {}
-        for ln in buf.value.decode().splitlines():   # "kernel_name launches total_ms"
-            parts = ln.rsplit(None, 2)
-            if len(parts) == 3:
-                counts[parts[0]] = counts.get(parts[0], 0) + int(parts[1])
-        out[form] = counts
-    return out
+    s = ES.Scene()
+    return ES.form_launches(s, _forms(s), lambda: (s.engine(world_size=1), s.table(), s.intrinsics()))
 
 
 def test_every_step_form_launches_what_the_fixture_recorded():

@@ -6,13 +6,11 @@ import numpy as np
 import pytest
 import torch
 
+import engine_scenes as ES
 import pose_vjp as P
 import views_cases as VC
-from conftest import gold
 
 pytestmark = pytest.mark.gpu
-
-CFG = dict(num_layers=4, hidden_size=128, skip_connect_every=4, num_encoding_fn_xyz=10, num_encoding_fn_dir=4)
 
 
 # ---- the kernels ----------------------------------------------------------------------------------------------------------------
@@ -68,72 +66,24 @@ def test_views_entry_points_reject_bad_arguments(gpu):
     VC.case_refusals(gpu)
 
 
-# ---- fixtures of the layers above -------------------------------------------------------------------------------------------------
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU visible")
-    return torch.device("cuda", 0)
-
-
-def _lego(dev, precision="fp32"):
-    import nerf_pytorch_amd as N
-    w, r = gold("lego_lowres_weights.npz"), gold("lego_lowres_render.npz")
-    mc, mf = N.FlexibleNeRFModel(**CFG), N.FlexibleNeRFModel(**CFG)
-    mc.load_state_dict({k[2:]: torch.from_numpy(w[k]) for k in w.files if k.startswith("c_")})
-    mf.load_state_dict({k[2:]: torch.from_numpy(w[k]) for k in w.files if k.startswith("f_")})
-    mc, mf = mc.to(dev), mf.to(dev)
-    if precision != "fp32":
-        mc.set_training_precision(precision), mf.set_training_precision(precision)
-    return mc, mf, int(r["H"]), int(r["W"]), float(np.float32(r["focal"])), r["pose"].astype(np.float32)
-
-
-def _se3(xi):
-    """4 x 4 transform of a twist-like 6-vector (rotation by Rodrigues' formula, translation as given)."""
-    T = torch.zeros(4, 4, dtype=xi.dtype, device=xi.device)
-    T = T + torch.nn.functional.pad(P.rodrigues(xi[:3]), (0, 1, 0, 1))
-    T = T + torch.nn.functional.pad(xi[3:, None], (3, 0, 0, 1))
-    T = T + torch.nn.functional.pad(torch.ones(1, 1, dtype=xi.dtype, device=xi.device), (3, 0, 3, 0))
-    return T
-
-
-def _ex_ed():
-    import nerf_pytorch_amd as N
-    return N.get_embedding_function(10, True, True), N.get_embedding_function(4, True, True)
-
-
-def _views(pose0, dev, V, scale=0.05, seed=2):
-    """V poses: the fixture pose times small se(3) offsets."""
-    g = torch.Generator().manual_seed(seed)
-    base = torch.from_numpy(pose0)
-    return torch.stack([base @ _se3(torch.randn(6, generator=g) * scale) for _ in range(V)]).to(dev).contiguous()
-
-
-def _queue_draws(draws):
-    queue = list(draws)
-    real = torch.rand, torch.randn
-    torch.rand = lambda *a, **k: queue.pop(0)
-    torch.randn = lambda *a, **k: queue.pop(0)
-    return real
-
-
 # ---- drop-in autograd ---------------------------------------------------------------------------------------------------------------
 def test_dropin_views_pose_gradients_equal_the_single_view_path():
     """select_training_rays_views -> predict_and_render_radiance -> MSE -> backward(): poses.grad[v] is, bit for bit, the gradient
     the same rays of view v give through select_training_rays(select_inds=...) with the same draws.  (The render is per ray, and
     the loss is written as sum / (3 n) with the full batch's n in both routes, so each ray's cotangent is the same.)"""
     import nerf_pytorch_amd as N
-    dev = _dev()
-    mc, mf, H, W, focal, pose0 = _lego(dev)
-    ex, ed = _ex_ed()
+    dev = ES.dev()
+    mc, mf, H, W, focal, pose0 = ES.lego(dev)
+    ex, ed = ES.ex_ed()
     opts = N.make_options(64, 64, perturb=True, white_background=True, radiance_field_noise_std=0.0)
     V, n = 3, 768
     g = torch.Generator().manual_seed(6)
     imgs = torch.rand(V, H, W, 3, generator=g).to(dev)
     t_rand, u = torch.rand(n, 64, generator=g).to(dev), torch.rand(n, 64, generator=g).to(dev)
-    poses = _views(pose0, dev, V).requires_grad_(True)
+    poses = ES.views(pose0, dev, V).requires_grad_(True)
 
     def loss_of(rays, tgt, tr, uu):
-        real = _queue_draws([tr, uu])
+        real = ES.queue_draws([tr, uu])
         try:
             out = N.predict_and_render_radiance(rays, mc, mf, opts, encode_position_fn=ex, encode_direction_fn=ed)
         finally:
@@ -174,10 +124,10 @@ def test_dropin_views_pose_gradients_equal_the_single_view_path():
 @pytest.mark.parametrize("backward", [None, "auto"])
 def test_step_on_views_of_one_view_equals_step_on_image(precision, backward):
     import nerf_pytorch_amd as N
-    dev = _dev()
+    dev = ES.dev()
     outs = []
     for views in (False, True):
-        mc, mf, H, W, focal, pose0 = _lego(dev, precision)
+        mc, mf, H, W, focal, pose0 = ES.lego(dev, precision)
         eng = N.TrainEngine(mc, mf, 32, 32, perturb=True, white_background=True, noise_std=0.2, seed=3, world_size=1, rank=0,
                             backward=backward)
         img = torch.rand(H, W, 3, generator=torch.Generator().manual_seed(1)).to(dev)
@@ -204,16 +154,16 @@ def test_step_on_views_equals_its_parts_and_two_streams_equal_one():
     """step_on_views(V = 3, pose_grads) against select_training_rays_views -> step(ray_grad=...) -> select_training_rays_views_bwd
     on ray_grad and ray_grad_coarse; and the two-stream step against the one-stream step."""
     import nerf_pytorch_amd as N
-    dev = _dev()
+    dev = ES.dev()
     V, n = 3, 640
     opts = N.make_options(32, 32)
     res = {}
     for arm in ("views", "parts", "views_one_stream"):
-        mc, mf, H, W, focal, pose0 = _lego(dev)
+        mc, mf, H, W, focal, pose0 = ES.lego(dev)
         eng = N.TrainEngine(mc, mf, 32, 32, perturb=True, white_background=True, noise_std=0.2, seed=3, world_size=1, rank=0,
                             overlap=(arm != "views_one_stream"))
         imgs = torch.rand(V, H, W, 3, generator=torch.Generator().manual_seed(1)).to(dev)
-        poses = _views(pose0, dev, V)
+        poses = ES.views(pose0, dev, V)
         grads, losses = [], []
         for it in range(2):
             pg = torch.full((V, 3, 4), float("nan"), device=dev)
@@ -237,10 +187,10 @@ def test_step_on_views_equals_its_parts_and_two_streams_equal_one():
 
 def test_step_on_views_data_parallel_slices_and_refusal():
     import nerf_pytorch_amd as N
-    dev = _dev()
+    dev = ES.dev()
     V, n = 3, 256
-    mc, mf, H, W, focal, pose0 = _lego(dev)
-    poses = _views(pose0, dev, V)
+    mc, mf, H, W, focal, pose0 = ES.lego(dev)
+    poses = ES.views(pose0, dev, V)
     # every pixel of every view carries its own (view, row, col)
     vv, rr, cc = torch.meshgrid(torch.arange(V), torch.arange(H), torch.arange(W), indexing="ij")
     imgs = torch.stack([vv, rr, cc], -1).float().to(dev)
@@ -272,11 +222,11 @@ def test_two_perturbed_poses_are_recovered_jointly_on_frozen_nets():
     the single-view one: the arms see different ray draws, and two equivalent single-view routes already differ by up to 2.2x in final
     translation error (profiles/r07_pose_grad.json: 0.0058 against 0.0027)."""
     import nerf_pytorch_amd as N
-    dev = _dev()
-    mc, mf, H, W, focal, pose0 = _lego(dev)
+    dev = ES.dev()
+    mc, mf, H, W, focal, pose0 = ES.lego(dev)
     for p in list(mc.parameters()) + list(mf.parameters()):
         p.requires_grad_(False)
-    ex, ed = _ex_ed()
+    ex, ed = ES.ex_ed()
     opts = N.make_options(64, 64, perturb=False, white_background=True, radiance_field_noise_std=0.0)
     gt0 = torch.from_numpy(pose0).to(dev)
     # the second view: the first one turned by 20 degrees about the world's z axis (the lego turntable)
@@ -294,7 +244,7 @@ def test_two_perturbed_poses_are_recovered_jointly_on_frozen_nets():
     for axis, shift in (([0.3, -0.8, 0.5], [0.03, -0.03, 0.0277]), ([-0.6, 0.2, 0.7], [-0.0277, 0.03, 0.03])):
         axis = torch.tensor(axis)
         deltas.append(torch.cat([axis / axis.norm() * np.deg2rad(2.0), torch.tensor(shift)]).float().to(dev))
-    starts = torch.stack([(gts[v] @ _se3(deltas[v])).detach() for v in range(2)])
+    starts = torch.stack([(gts[v] @ ES.se3(deltas[v])).detach() for v in range(2)])
     gts64 = gts.cpu().numpy().astype(np.float64)
 
     def errors(est, v):
@@ -310,7 +260,7 @@ def test_two_perturbed_poses_are_recovered_jointly_on_frozen_nets():
         opt = torch.optim.Adam([xi], lr=LR)
         eng = engine()
         pg = torch.empty(len(views), 3, 4, device=dev)
-        poses_of = lambda: torch.stack([starts[v] @ _se3(xi[j]) for j, v in enumerate(views)])  # noqa: E731
+        poses_of = lambda: torch.stack([starts[v] @ ES.se3(xi[j]) for j, v in enumerate(views)])  # noqa: E731
         curve = {v: [(-1,) + errors(starts[v], v)] for v in views}
         for it in range(STEPS):
             opt.zero_grad()

@@ -4,9 +4,9 @@ import numpy as np
 import pytest
 import torch
 
+import engine_scenes as ES
 import nerf_oracle as O
 import parity_cases as PC
-import test_gpu_views as TV
 import window_cases as WC
 
 pytestmark = pytest.mark.gpu
@@ -64,7 +64,7 @@ def _nets(dev, seeds=(2, 4)):
 
 
 def _scene():
-    r = TV.gold("lego_lowres_render.npz")
+    r = ES.gold("lego_lowres_render.npz")
     return int(r["H"]), int(r["W"]), float(np.float32(r["focal"])), r["pose"].astype(np.float32)
 
 
@@ -74,7 +74,7 @@ def test_dropin_loop_returns_the_windowed_gradients_of_the_engine_step():
     same torch graph -- both to the 1e-4 of the norm tests/test_gpu_pose.py::test_engine_pose_gradient_equals_dropin holds the two
     paths to (same kernels, another buffer layout).  The node pins its forward's window; closed bands get exact zeros."""
     import nerf_pytorch_amd as N
-    dev = TV._dev()
+    dev = ES.dev()
     H, W, focal, pose0 = _scene()
     mc, mf = _nets(dev)
     ax, ad = WC.FRACTIONAL["fern4x64"]
@@ -93,7 +93,7 @@ def test_dropin_loop_returns_the_windowed_gradients_of_the_engine_step():
 
     def dropin(leaf):
         ro, rd = bundle(leaf)
-        real = TV._queue_draws([draws[0], draws[2]])
+        real = ES.queue_draws([draws[0], draws[2]])
         try:
             out = N.run_one_iter_of_nerf(H, W, focal, mc, mf, ro, rd, opts, encode_position_fn=ex, encode_direction_fn=ed)
         finally:
@@ -163,7 +163,7 @@ def TV_rays(n, dev, seed=3):
 
 
 def test_engine_with_an_open_window_equals_the_engine_without():
-    dev = TV._dev()
+    dev = ES.dev()
     _, mc0, mf0, _, _, l0 = _run(dev, 20)
     eng, mc1, mf1, _, _, l1 = _run(dev, 20, window=(-2.0, -1.0), total_steps=STEPS)
     assert eng.window_alphas(0)[0] >= CFG["num_encoding_fn_xyz"] and mc1.encoding_window is not None
@@ -175,7 +175,7 @@ def test_engine_with_an_open_window_equals_the_engine_without():
 def test_engine_schedule_keeps_closed_bands_at_their_initial_values():
     """window=(0.1, 0.6) over 40 steps: a band's weight columns are torch.equal to their initial values after every step up to the
     last one it was closed in, and have moved by the end of the run once it has opened; the two-stream step gives the one-stream bits."""
-    dev = TV._dev()
+    dev = ES.dev()
     runs = {ov: _run(dev, STEPS, overlap=ov, record=True, window=(0.1, 0.6), total_steps=STEPS) for ov in (True, False)}
     eng, mc, mf, init, seen, losses = runs[True]
     assert torch.all(torch.isfinite(losses)) and all(bool(torch.all(torch.isfinite(m.flat_params))) for m in (mc, mf))
@@ -205,12 +205,12 @@ def test_engine_schedule_keeps_closed_bands_at_their_initial_values():
 
 def test_step_on_views_with_cameras_runs_under_a_schedule():
     import nerf_pytorch_amd as N
-    dev = TV._dev()
+    dev = ES.dev()
     H, W, focal, pose0 = _scene()
     mc, mf = _nets(dev)
     V = 3
     imgs = torch.rand(V, H, W, 3, generator=torch.Generator().manual_seed(1)).to(dev)
-    T = N.CameraTable(TV._views(pose0, dev, V), lr=2e-3)
+    T = N.CameraTable(ES.views(pose0, dev, V), lr=2e-3)
     eng = N.TrainEngine(mc, mf, 16, 16, seed=3, lr=5e-4, world_size=1, rank=0, window=(0.0, 0.5), total_steps=8)
     opts = N.make_options(16, 16)
     init = mc.flat_params.clone()
