@@ -450,6 +450,36 @@ int nerfhip_spread_loss(const float* raw, const float* z, const float* rays, int
                         const float* noise, uint64_t seed, uint32_t rng_stream, uint64_t ray_offset, float scale,
                         const float* g_loss, float* loss, float* g_weights, nerfhip_stream_t stream);
 
+/* ---- depth priors (DS-NeRF, Deng et al. 2022): supervise the ray weights from sparse per-ray depths ------------------------------
+ * One pass of one ray has s samples at depths z_0 <= ... <= z_{s-1} (the ray parameter t: for this library's pin-hole rays, whose
+ * camera-frame direction has third component -1, the camera-space z-depth of a structure-from-motion point; for NDC rays the units
+ * are the caller's), far = column 7 of its packed row, and the weights w_i = alpha_i T_i exactly as the compositing forms them (as
+ * for nerfhip_spread_loss: the same noise draws and fp64 transmittance scan).  Its prior row is (D, c, sigma): depth, confidence
+ * weight, standard deviation.  If !(c > 0) -- c = NaN included -- the ray has NO PRIOR: both losses are exactly 0, its gradient row
+ * exactly 0, D and sigma are not interpreted (NaN or garbage there is harmless), and raw is not read for it.  Otherwise, with
+ * eps = 1e-5:
+ *     d^   = sum_i w_i z_i
+ *     E    = c (d^ - D)^2                                                           the "expected-depth" term
+ *     k_i  = exp(-(z_i - D)^2 / (2 sigma^2)),  delta_i = z_{i+1} - z_i,  delta_{s-1} = max(far - z_{s-1}, 0)
+ *     Tm   = c sum_i -log(w_i + eps) k_i delta_i                                    the "termination" term (DS-NeRF eq. 10, its code's eps)
+ *     dE/dw_i = 2 c (d^ - D) z_i               dTm/dw_i = -c k_i delta_i / (w_i + eps)
+ * The depths are constants, as for the spread loss: the gradient reaches the nets (and the rays) through w alone.  NaN in raw
+ * propagates on a ray with c > 0.  A row with c > 0 and sigma <= 0 is outside the contract (no access leaves the buffers for it).
+ * raw dev [n,s,4], z dev [n,s], rays dev [n, ray_stride >= 8].  The prior row of ray r is prior + (inds ? inds[r] : r) * prior_stride
+ * (prior dev, prior_stride >= 3 floats; inds dev int64 [n] or NULL); an index outside [0, prior_rows) is a row without a prior, and
+ * nothing is read for it.  loss (optional) dev [n,2]: (E, Tm) of each ray, unscaled.  g_weights (optional) dev [n,s]:
+ *     g_weights[r,i] = scale (w_expected g_loss[r,0] dE/dw_i + w_termination g_loss[r,1] dTm/dw_i)
+ * formed in fp64 and rounded to fp32 once; g_loss dev [n,2] or NULL (= 1): the cotangents of the two losses.  A term whose weight is
+ * exactly 0 contributes nothing (not 0 * inf).  accumulate != 0: the value is ADDED to what g_weights[r,i] holds (one fp32 add), and a
+ * ray without a prior leaves its row untouched -- the term stacks on the cotangent nerfhip_spread_loss wrote; accumulate == 0: every
+ * row is written, zeros for a ray without a prior.  At least one output, and a single-output call gives the combined call's bits;
+ * 1 <= s <= 8192; n == 0 launches nothing.  O(s) per ray, fp64 sums in a fixed order (no atomics). */
+int nerfhip_depth_prior_loss(const float* raw, const float* z, const float* rays, int ray_stride, int64_t n, int s, float noise_std,
+                             const float* noise, uint64_t seed, uint32_t rng_stream, uint64_t ray_offset, const float* prior,
+                             int64_t prior_stride, const int64_t* inds, int64_t prior_rows, float w_expected, float w_termination,
+                             float scale, const float* g_loss, float* loss, float* g_weights, int accumulate,
+                             nerfhip_stream_t stream);
+
 /* d(loss)/d(rays) ALONE, for frozen nets (camera localisation against a trained field): nerfhip_render_bwd_rays' contract -- parts,
  * NERFHIP_PART_SHARED_BWD, the first pass that runs overwrites g_rays and the second accumulates, params_* = the flat vectors the
  * packed images were made from (theta_eff under an encoding window) -- without g_params: no parameter gradient is computed or

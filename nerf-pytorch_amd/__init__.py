@@ -9,6 +9,7 @@ tree and the CLI scripts of the reference are out of scope.
 from . import eval_utils, io_utils, models, occupancy  # noqa: F401
 from .cameras import CameraTable, Distortion, Exposure, Intrinsics, se3_poses  # noqa: F401
 from .cfg import AttrDict, make_options  # noqa: F401
+from .depth_prior import DepthPrior  # noqa: F401
 from .engine import TrainEngine  # noqa: F401
 from .launch_profile import LaunchProfile  # noqa: F401
 from .models import FlexibleNeRFModel  # noqa: F401

@@ -23,6 +23,11 @@ grid's density is updated from the images just packed.
 
 Ray-weight spread loss (mip-NeRF 360's L_dist; `spread=`): a net with a weight lambda > 0 gets one nerfhip_spread_loss
 launch between its loss and its backward, on the same stream, and the _w form of that backward; `spread_losses` reads the means.
+
+Depth priors (DS-NeRF; `depth_loss=` and a step's `depth_prior=`): a net with a nonzero weight gets one
+nerfhip_depth_prior_loss launch on the stream its backward runs on, behind the spread launch where there is one (then accumulating into
+the same weight cotangent), ahead of the _w form of its backward; `depth_losses` reads the means.  A step without `depth_prior=` is
+the step without the feature.
 """
 import math
 
@@ -32,6 +37,7 @@ from . import _lib as L
 from . import backward_mode as BM
 from . import train_utils as TU
 from .cameras import Distortion, Exposure, Intrinsics, check_device_vector
+from .depth_prior import DepthPrior
 from .nerf_helpers import linspace01
 from .render_call import RenderCall
 from .parallel import allreduce_gradients, shard_bounds
@@ -41,7 +47,7 @@ class TrainEngine:
     def __init__(self, model_coarse, model_fine, num_coarse, num_fine, perturb=True, lindisp=False, white_background=False,
                  noise_std=0.0, lr=5e-3, betas=(0.9, 0.999), eps=1e-8, seed=0, process_group=None, world_size=None,
                  rank=None, overlap=None, always_reduce=False, backward=None, window=None, total_steps=None, occupancy=None,
-                 occupancy_warmup=256, occupancy_every=16, spread=None):
+                 occupancy_warmup=256, occupancy_every=16, spread=None, depth_loss=None):
         self.lib = L.get_lib()
         self.mc, self.mf = model_coarse, model_fine if num_fine > 0 else None
         self.dev = model_coarse.flat_params.device
@@ -133,6 +139,13 @@ class TrainEngine:
             raise ValueError("TrainEngine: spread must be None, a finite weight >= 0 or a pair (coarse, fine) of them (got %r)" % (spread,))
         self.spread = (spread[0], spread[1] if self.mf is not None else 0.0)
         self._spread_bufs = None   # per net with lambda > 0: (weight cotangent [n, S], per-ray loss [n]), sized in _prepare
+        # depth priors (DS-NeRF): None -- no term; (a, b) -- the weights of the expected-depth and the termination term
+        # on both nets; ((a_c, b_c), (a_f, b_f)) -- per net.  A net's loss becomes mse + (1 / n) sum_rays (a E + b Tm) over ALL n rays of
+        # a step that is given prior rows (depth_prior=...); a step without them is the step without the feature
+        self.depth_loss = self._parse_depth_loss(depth_loss, self.mf is not None)
+        self._depth_bufs = None    # per net with a nonzero weight: (weight cotangent [n, S], per-ray losses [n, 2]), sized in _prepare
+        self._depth_ran = False    # whether the last step launched the depth kernel (depth_losses)
+        self._depth_keep = None    # the last step's prior table and indices (alive until the next step: the launches read them)
         self._stats = BM.StatsReader(("coarse", "fine"))
         self._zero_frac = self._stats.frac   # last known fraction of all-zero d(loss)/d(raw) rows per net (updated in place)
         # steps run dense / compacted / recomputed / fused / fused over the list / fused over the stash, per net ("auto")
@@ -152,6 +165,25 @@ class TrainEngine:
         self.t_vals = linspace01(num_coarse, self.dev)
         self.u_det = linspace01(num_fine, self.dev) if num_fine > 0 else None
         self.repack()
+
+    @staticmethod
+    def _parse_depth_loss(depth_loss, has_fine):
+        bad = ValueError("TrainEngine: depth_loss must be None, a pair (a, b) of finite weights >= 0 (expected-depth, termination) or "
+                         "a pair of such pairs (coarse, fine) (got %r)" % (depth_loss,))
+        if depth_loss is None:
+            return ((0.0, 0.0), (0.0, 0.0))
+        try:
+            d = tuple(depth_loss)
+            if len(d) != 2:
+                raise bad
+            if all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in d):
+                d = (d, d)
+            d = tuple(tuple(float(v) for v in pair) for pair in d)
+        except TypeError:
+            raise bad from None
+        if any(len(pair) != 2 or not all(v >= 0.0 and math.isfinite(v) for v in pair) for pair in d):
+            raise bad
+        return (d[0], d[1] if has_fine else (0.0, 0.0))
 
     def window_alphas(self, step):
         """(alpha_xyz, alpha_dir) of the schedule at step `step` (None without one)."""
@@ -198,6 +230,11 @@ class TrainEngine:
             S = (self.cfg.num_coarse, self.cfg.num_coarse + self.cfg.num_fine)
             self._spread_bufs = {fine: (mk(n, S[fine]), torch.zeros(n, dtype=torch.float32, device=self.dev))
                                  for fine in (0, 1) if self.spread[fine] > 0.0}
+        if any(any(w) for w in self.depth_loss):   # (what the depth kernel writes; the weight cotangent is the spread term's where it has one)
+            S = (self.cfg.num_coarse, self.cfg.num_coarse + self.cfg.num_fine)
+            self._depth_bufs = {fine: (self._spread_bufs[fine][0] if self.spread[fine] > 0.0 else mk(n, S[fine]),
+                                       torch.zeros(n, 2, dtype=torch.float32, device=self.dev))
+                                for fine in (0, 1) if any(self.depth_loss[fine])}
 
     def workspace_bytes(self):
         return 0 if self._ws is None else self._wsb
@@ -245,8 +282,34 @@ class TrainEngine:
             raise NotImplementedError("TrainEngine: %s with world size %d is not implemented (the pose / ray gradient of a "
                                       "data-parallel step would need its own all-reduce); run it with one rank" % (what, self.world))
 
+    def _check_depth_prior(self, depth_prior, n, frozen):
+        """depth_prior= of a step -> (table, row stride, indices or None, rows): `rows` (n, 3) read ray by ray, or (P, inds) -- a
+        DepthPrior and the int64 global index of every ray."""
+        if not any(any(w) for w in self.depth_loss):
+            raise ValueError("TrainEngine: depth_prior=... on an engine without depth_loss (construct it with depth_loss=(a, b))")
+        if frozen:
+            raise ValueError("TrainEngine: a frozen step (localize_*, the exposure fit) takes no depth prior: the frozen ray gradient "
+                             "takes no weight cotangent")
+        inds = None
+        if isinstance(depth_prior, (tuple, list)):
+            prior, inds = depth_prior
+            if not isinstance(prior, DepthPrior):
+                raise ValueError("TrainEngine: depth_prior=(P, inds) needs P as a DepthPrior (got %s)" % type(prior).__name__)
+            table = prior.table
+            if (not isinstance(inds, torch.Tensor) or inds.device != self.dev or inds.dtype != torch.int64 or tuple(inds.shape) != (n,)
+                    or not inds.is_contiguous()):
+                raise ValueError("TrainEngine: depth_prior=(P, inds) needs inds as a contiguous int64 (%d) tensor on %s" % (n, self.dev))
+        else:
+            table = depth_prior
+            if not isinstance(table, torch.Tensor) or tuple(table.shape) != (n, 3):
+                raise ValueError("TrainEngine: depth_prior must be a contiguous float32 (%d, 3) tensor on %s, or (DepthPrior, inds)"
+                                 % (n, self.dev))
+        if table.device != self.dev or table.dtype != torch.float32 or not table.is_contiguous():
+            raise ValueError("TrainEngine: the depth prior rows must be contiguous float32 on %s" % (self.dev,))
+        return table, table.shape[1], inds, table.shape[0]
+
     def forward_backward(self, rays, target, ray_offset=0, global_rays=None, draws=None, ray_grad=None, frozen=False, step=None,
-                         exposure=None):
+                         exposure=None, depth_prior=None):
         """rays: (n, 8|11) packed rows on the device; target: (n, >=3), row stride free (an RGBA image's [..., :3] view
         works).  Leaves the summed-over-this-rank gradient in self.grad and {coarse_mse, fine_mse, sum} in self.loss
         (device); with world > 1 the gradient all-reduces are in flight when this returns (optimizer_step waits).
@@ -271,8 +334,12 @@ class TrainEngine:
         (nerfhip_mse_loss_views_fwd_bwd in place of the plain loss launch, same streams), and after the two streams have joined
         X.backward(...) leaves d(loss)/d(table) in X.g_expo (three launches on the main stream, reading the engine's own rgb buffers).
         The exposure sits behind the render: it asks for no ray gradient.  With frozen=True and no ray_grad the step is the
-        test-time fit: the two forwards, the two losses and the table gradient, no render backward.  One rank only."""
+        test-time fit: the two forwards, the two losses and the table gradient, no render backward.  One rank only.
+        depth_prior: None, or the prior rows of the batch -- a contiguous float32 (n, 3) device tensor of (depth, weight, sigma), weight
+        0 = no prior -- or (P, inds): a depth_prior.DepthPrior and the int64 global indices of the batch (what
+        select_training_rays_views returned).  Needs TrainEngine(depth_loss=...); refused on a frozen step."""
         self._check_inputs(rays, target)
+        dp = None if depth_prior is None else self._check_depth_prior(depth_prior, rays.shape[0], frozen)
         if frozen and any(self.spread):
             raise ValueError("TrainEngine: a frozen step (localize_*, the exposure fit) with spread > 0 makes no sense: the spread loss "
                              "regularises the nets, and a frozen step updates none")
@@ -354,6 +421,13 @@ class TrainEngine:
                 # (scale: lambda / n under the loss launch's grad_scale convention -- the total is the mse terms + lambda * mean_ray(L))
                 call.spread(fine, self.spread[fine] * gscale / n, None, sl.data_ptr(), gw.data_ptr(), stream)
                 g_weights = (None, gw.data_ptr()) if fine else (gw.data_ptr(), None)
+            if dp is not None and any(self.depth_loss[fine]):
+                gw, dl = self._depth_bufs[fine]
+                a, bb = self.depth_loss[fine]
+                # (scale: 1 / n under the same convention; behind a spread launch the term is added to the cotangent it wrote)
+                call.depth_prior(fine, dp[0].data_ptr(), dp[1], None if dp[2] is None else dp[2].data_ptr(), dp[3], a, bb, gscale / n,
+                                 None, dl.data_ptr(), gw.data_ptr(), self.spread[fine] > 0.0, stream)
+                g_weights = (None, gw.data_ptr()) if fine else (gw.data_ptr(), None)
             if exposure is None:
                 lib.mse_loss_fwd_bwd(rgb.data_ptr(), None, target.data_ptr(), tstride, n, gscale, g_rgb.data_ptr(), None, loss.data_ptr(), stream)
             else:
@@ -375,6 +449,7 @@ class TrainEngine:
         coarse = (L.PART_COARSE, b["rgb_c"], b["g_c"], cot_c, self._loss_c, gc, self.mc, tmp_c, g_rays_c)
         fine = (L.PART_FINE, b["rgb_f"], b["g_f"], cot_f, self._loss_f, gf, self.mf, tmp_f, ray_grad)
         self._pending = []
+        self._depth_keep, self._depth_ran = dp, dp is not None
         with torch.cuda.device(self.dev):
             main, side = self._streams()
             st = main.cuda_stream
@@ -452,6 +527,14 @@ class TrainEngine:
         the first step."""
         b = self._spread_bufs or {}
         return tuple(b[fine][1].mean() if fine in b else None for fine in (0, 1))
+
+    @property
+    def depth_losses(self):
+        """(coarse, fine): per net a device tensor (mean E, mean Tm) over ALL rays of the last step -- the unscaled expected-depth and
+        termination losses the depth kernel wrote, formed on demand (no host synchronisation); None for a net without a weight, or
+        when the last step was given no prior."""
+        b = (self._depth_bufs or {}) if self._depth_ran else {}
+        return tuple(b[fine][1].mean(dim=0) if fine in b else None for fine in (0, 1))
 
     def _stats_words(self, name):
         """The two statistics words of net `name` in the workspace of the last step."""
@@ -542,14 +625,15 @@ class TrainEngine:
             g.update_density(((self.mc._plan, self.packed_c), (self.mf._plan if self.mf is not None else None, self.packed_f)),
                              self.step_count // self.occupancy_every)
 
-    def step(self, rays, target, ray_offset=0, lr=None, global_rays=None, draws=None, ray_grad=None):
-        """One full training iteration.  Returns the device tensor {coarse_mse, fine_mse, sum} (no host sync)."""
-        self.forward_backward(rays, target, ray_offset, global_rays, draws, ray_grad)
+    def step(self, rays, target, ray_offset=0, lr=None, global_rays=None, draws=None, ray_grad=None, depth_prior=None):
+        """One full training iteration.  Returns the device tensor {coarse_mse, fine_mse, sum} (no host sync).
+        depth_prior: see forward_backward."""
+        self.forward_backward(rays, target, ray_offset, global_rays, draws, ray_grad, depth_prior=depth_prior)
         self.optimizer_step(lr)
         return self.loss
 
     def step_on_image(self, image, pose, height, width, focal_length, options, num_random_rays, lr=None, global_rays=None,
-                      pose_grad=None, intrinsics=None, distortion=None, exposure=None):
+                      pose_grad=None, intrinsics=None, distortion=None, exposure=None, depth_prior=None, depth_rays=0):
         """One whole iteration of the reference's loop body (train_nerf.py:210-270) on a resident training image:
         on-device selection of this rank's distinct pixels (ranks take disjoint slices of one permutation keyed by
         (seed, iteration)), their rays and targets, then `step`.  No host work besides launches.
@@ -564,16 +648,17 @@ class TrainEngine:
         intrinsics: None, or a cameras.Intrinsics on the engine's device: the rays are generated from its (fx, fy, cx, cy), read on
         the device, and the step learns them -- see step_on_views.  `focal_length` must still be passed: it fixes the NDC constants.
         distortion: None, or a cameras.Distortion on the engine's device -- see step_on_views.
-        exposure: refused -- a single image has no view axis for a per-view table: use step_on_views."""
+        exposure: refused -- a single image has no view axis for a per-view table: use step_on_views.
+        depth_prior, depth_rays: a depth_prior.DepthPrior of ONE view -- see step_on_views."""
         self._no_exposure_on_image("step_on_image", exposure)
         if pose_grad is not None:
             self._no_pose_grad_across_ranks("pose_grad")
             self._check_pose_grads("pose_grad", pose_grad, (3, 4))
         return self._step_on_selection((height, width, focal_length, options), pose, image, False, num_random_rays, lr, global_rays,
-                                       pose_grad, None, intrinsics, False, distortion)
+                                       pose_grad, None, intrinsics, False, distortion, None, depth_prior, depth_rays)
 
     def step_on_views(self, images, poses, height, width, focal_length, options, num_random_rays, lr=None, global_rays=None,
-                      pose_grads=None, cameras=None, intrinsics=None, distortion=None, exposure=None):
+                      pose_grads=None, cameras=None, intrinsics=None, distortion=None, exposure=None, depth_prior=None, depth_rays=0):
         """step_on_image over a resident stack of views: this rank's rays are drawn from ALL of `images` (V, H, W, 3|4) with the
         rays of each generated from its own row of `poses` (V, >=3, 4) -- train_utils.select_training_rays_views --, then `step`.
         Same rank slicing (first = rank * n, or the shard_bounds slice of `global_rays`) over the permutation of V * H * W, same
@@ -598,9 +683,16 @@ class TrainEngine:
         exposure: None, or a cameras.Exposure of V views on the engine's device: both losses are taken under its per-view colour gain
         and offset (forward_backward(exposure=...)) and the step learns the table: X.backward() after the two streams joined,
         X.step() last (after distortion.step()).  Alone or with any of the above.  It sits behind the render and does NOT turn the
-        ray gradient on: alone, the step is selection, forward_backward, optimizer_step, X.step().  One rank only."""
+        ray gradient on: alone, the step is selection, forward_backward, optimizer_step, X.step().  One rank only.
+        depth_prior: None, or a depth_prior.DepthPrior of these V views on the engine's device (needs TrainEngine(depth_loss=...)): the
+        selection's global indices are handed to the depth kernel, which reads each ray's prior row from the resident table.
+        depth_rays: m rays of the batch drawn from the pixels that carry a prior (a sparse table gives a uniformly drawn batch almost
+        none; DS-NeRF draws keypoint rays separately): the step's indices are the first n - m positions of the usual keyed permutation
+        followed by P.pixels[j], j the positions rank * m ... rank * m + m - 1 of a second keyed permutation over len(P.pixels)
+        (nerfhip_select_indices with the seed XORed with DEPTH_RAYS_KEY); 0 <= m <= min(n, len(P.pixels)); refused with global_rays.
+        No host synchronisation."""
         return self._step_on_selection((height, width, focal_length, options), poses, images, True, num_random_rays, lr, global_rays,
-                                       pose_grads, cameras, intrinsics, False, distortion, exposure)
+                                       pose_grads, cameras, intrinsics, False, distortion, exposure, depth_prior, depth_rays)
 
     def localize_on_image(self, image, pose, height, width, focal_length, options, num_random_rays, pose_grad=None, intrinsics=None,
                           distortion=None, exposure=None):
@@ -674,8 +766,24 @@ class TrainEngine:
         if num_views is not None and exposure.num_views != num_views:
             raise RuntimeError("TrainEngine: the exposure table holds %d views, the step draws from %d" % (exposure.num_views, num_views))
 
+    # the second permutation of depth_rays= is keyed by the engine's seed XOR this constant (the 64-bit golden-ratio constant's complement)
+    DEPTH_RAYS_KEY = 0x61C8864680B583EB
+
+    def _depth_select_inds(self, prior, n, m, first, count, population):
+        """The step's indices under depth_rays=m (see step_on_views): two nerfhip_select_indices launches, a gather and a concatenation
+        on the engine's device, no host synchronisation."""
+        lib = self.lib
+        seed = int(self.seed) & 0xFFFFFFFFFFFFFFFF
+        head = torch.empty(n - m, dtype=torch.int64, device=self.dev)
+        pos = torch.empty(m, dtype=torch.int64, device=self.dev)
+        with L.launch_on(prior.pixels, head, pos) as st:
+            if n - m > 0:
+                lib.select_indices(seed, int(count), population, first, n - m, head.data_ptr(), st)
+            lib.select_indices(seed ^ self.DEPTH_RAYS_KEY, int(count), prior.pixels.numel(), self.rank * m, m, pos.data_ptr(), st)
+            return torch.cat((head, prior.pixels[pos]))
+
     def _step_on_selection(self, scene, poses, images, views, num_random_rays, lr, global_rays, pose_grads, cameras, intrinsics, frozen,
-                           distortion=None, exposure=None):
+                           distortion=None, exposure=None, depth_prior=None, depth_rays=0):
         """The step of step_on_image / step_on_views / localize_on_* behind their own argument checks.  scene: (height, width,
         focal_length, options); views: whether `poses` / `images` carry a view axis.  In launch order: the checks of intrinsics=I and
         distortion=D, then I.values() and D.values(); cameras=T checked, T.poses() (_resolve_cameras); this rank's slice of the
@@ -689,6 +797,24 @@ class TrainEngine:
         alone WITHOUT a ray gradient --, and X.step() comes last, after D.step()."""
         height, width, focal_length, options = scene
         kw, vjp_kw = {}, {}
+        depth_rays = int(depth_rays)
+        if depth_prior is None:
+            if depth_rays:
+                raise ValueError("TrainEngine: depth_rays=%d without depth_prior=..." % depth_rays)
+        else:
+            if not isinstance(depth_prior, DepthPrior):
+                raise ValueError("TrainEngine: depth_prior must be a depth_prior.DepthPrior (got %s)" % type(depth_prior).__name__)
+            self._check_depth_prior((depth_prior, torch.empty(0, dtype=torch.int64, device=self.dev)), 0, frozen)
+            nviews = images.shape[0] if views else 1
+            if (depth_prior.num_views, depth_prior.height, depth_prior.width) != (nviews, int(height), int(width)):
+                raise ValueError("TrainEngine: the depth prior holds %d views of %d x %d, the step draws from %d of %d x %d"
+                                 % (depth_prior.num_views, depth_prior.height, depth_prior.width, nviews, int(height), int(width)))
+            if depth_rays and global_rays is not None:
+                raise ValueError("TrainEngine: depth_rays=... and global_rays=... exclude each other")
+            if not 0 <= depth_rays <= min(int(num_random_rays), depth_prior.pixels.numel() // self.world):
+                raise ValueError("TrainEngine: depth_rays must lie in 0 ... min(num_random_rays, len(P.pixels)) (got %d; %d rays, %d "
+                                 "pixels with a prior over %d ranks)" % (depth_rays, int(num_random_rays), depth_prior.pixels.numel(),
+                                                                         self.world))
         if exposure is not None:
             self._no_pose_grad_across_ranks("exposure")
             self._check_exposure(exposure, images.shape[0] if isinstance(images, torch.Tensor) and images.dim() == 4 else None)
@@ -722,15 +848,19 @@ class TrainEngine:
             n = hi - first
         select = TU.select_training_rays_views if views else TU.select_training_rays
         count = self.localize_count if frozen else self.step_count
+        if depth_rays:   # (the last depth_rays rays of the batch come from the pixels that carry a prior)
+            population = int(height) * int(width) * (images.shape[0] if views else 1)
+            kw = dict(kw, select_inds=self._depth_select_inds(depth_prior, n, depth_rays, first, count, population))
         with torch.no_grad():
             rays, target, used = select(height, width, focal_length, poses, images, n, options, seed=self.seed, step=count, first=first, **kw)
         want_rays = pose_grads is not None or intrinsics is not None or distortion is not None
+        dkw = {} if depth_prior is None else dict(depth_prior=(depth_prior, used))
         if not want_rays and exposure is None:
-            return self.step(rays, target, ray_offset=first, lr=lr, global_rays=global_rays)
+            return self.step(rays, target, ray_offset=first, lr=lr, global_rays=global_rays, **dkw)
         ex = None if exposure is None else (exposure, used, int(height) * int(width))
         if want_rays:
             self._ray_grad_bufs(n, own=True)
-        self.forward_backward(rays, target, first, global_rays, None, self._ray_grad if want_rays else None, frozen, count, ex)
+        self.forward_backward(rays, target, first, global_rays, None, self._ray_grad if want_rays else None, frozen, count, ex, **dkw)
         if want_rays:
             vjp = TU.select_training_rays_views_bwd if views else TU.select_training_rays_bwd
             with torch.cuda.device(self.dev):

@@ -118,3 +118,13 @@ class RenderCall:
         return self.lib.spread_loss(self.ws + self.region("raw_" + tag)[0], self.ws + self.region("z_" + tag)[0], self.rays,
                                     self.cfg.ray_stride, self.n, S, self.cfg.noise_std, self.rand[3 if fine else 1], self.seed,
                                     3 if fine else 1, self.ray_offset, scale, g_loss, loss, g_weights, stream)
+
+    def depth_prior(self, fine, prior, prior_stride, inds, prior_rows, w_expected, w_termination, scale, g_loss, loss, g_weights,
+                    accumulate, stream):
+        """nerfhip_depth_prior_loss of one pass over the same regions and with the same noise stream as `spread`.  prior: the table
+        (rows of prior_stride floats: depth, weight, sigma); inds: None (ray r reads row r) or the int64 row index of every ray."""
+        tag, S = ("fine", self.cfg.num_coarse + self.cfg.num_fine) if fine else ("coarse", self.cfg.num_coarse)
+        return self.lib.depth_prior_loss(self.ws + self.region("raw_" + tag)[0], self.ws + self.region("z_" + tag)[0], self.rays,
+                                         self.cfg.ray_stride, self.n, S, self.cfg.noise_std, self.rand[3 if fine else 1], self.seed,
+                                         3 if fine else 1, self.ray_offset, prior, prior_stride, inds, prior_rows, w_expected,
+                                         w_termination, scale, g_loss, loss, g_weights, int(bool(accumulate)), stream)

@@ -85,12 +85,18 @@ class _FusedRender(torch.autograd.Function):
     With the `spread` flag (the seventh entry of cfg_tuple) the node has two more differentiable outputs: the per-ray spread loss of
     each pass's ray weights (nerfhip_spread_loss; None for the fine pass without a fine net).  Its forward runs the kernel for the
     losses alone; its backward runs it again with the incoming per-ray cotangents as g_loss and hands the weight cotangents to the _w
-    form of the render backward.  The flag is pinned at the forward, as the backward mode is."""
+    form of the render backward.  The flag is pinned at the forward, as the backward mode is.
+
+    With prior rows (an optional eighth entry of cfg_tuple: a contiguous float32 (n, 3) tensor of (depth, weight, sigma)) the node has
+    two more differentiable outputs behind those: the per-ray (E, Tm) of each pass, (n, 2) (nerfhip_depth_prior_loss; None for the fine
+    pass without a fine net).  Its backward runs the kernel again with the incoming cotangents as g_loss -- accumulating behind the
+    spread term where both are asked for -- and calls the _w form of the render backward."""
 
     @staticmethod
     def forward(ctx, rays, model_c, model_f, cfg_tuple, rand, training, rays_grad, *params):
         lib = L.get_lib()
-        nc, nf, perturb, lindisp, white, noise_std, spread = cfg_tuple
+        nc, nf, perturb, lindisp, white, noise_std, spread = cfg_tuple[:7]
+        prior = cfg_tuple[7] if len(cfg_tuple) > 7 else None
         n, stride = rays.shape
         dev = rays.device
         cfg = L.RenderCfg(nc, nf, int(bool(perturb)), int(bool(lindisp)), int(bool(white)), float(noise_std), stride)
@@ -138,18 +144,28 @@ class _FusedRender(torch.autograd.Function):
         ctx.n_params = len(params)
         ctx.mark_non_differentiable(bufs["disp_coarse"], bufs["disp_fine"])
         ctx.spread = bool(spread)
-        if not spread:
+        ctx.prior = prior
+        if not spread and prior is None:
             return tuple(bufs[k] for k in names)
         if ctx.frozen:
-            raise ValueError("spread=True on frozen nets (set_frozen) makes no sense: the spread loss regularises the nets")
-        sp = [torch.empty(n, dtype=torch.float32, device=dev) for _ in range(2 if nf > 0 else 1)]
-        with L.launch_on(rays, ws, *sp) as st:
-            for fine, out_sp in enumerate(sp):   # (the losses alone, over the raw rows and depths the forward left in its workspace)
-                call.spread(fine, 1.0, None, out_sp.data_ptr(), None, st)
-        return tuple(bufs[k] for k in names) + (sp[0], sp[1] if nf > 0 else None)
+            raise ValueError("spread=True or depth_prior=... on frozen nets (set_frozen) makes no sense: these losses regularise the nets")
+        tail = ()
+        if spread:
+            sp = [torch.empty(n, dtype=torch.float32, device=dev) for _ in range(2 if nf > 0 else 1)]
+            with L.launch_on(rays, ws, *sp) as st:
+                for fine, out_sp in enumerate(sp):   # (the losses alone, over the raw rows and depths the forward left in its workspace)
+                    call.spread(fine, 1.0, None, out_sp.data_ptr(), None, st)
+            tail += (sp[0], sp[1] if nf > 0 else None)
+        if prior is not None:
+            dp = [torch.empty((n, 2), dtype=torch.float32, device=dev) for _ in range(2 if nf > 0 else 1)]
+            with L.launch_on(rays, ws, prior, *dp) as st:
+                for fine, out_dp in enumerate(dp):
+                    call.depth_prior(fine, prior.data_ptr(), 3, None, n, 1.0, 1.0, 1.0, None, out_dp.data_ptr(), None, False, st)
+            tail += (dp[0], dp[1] if nf > 0 else None)
+        return tuple(bufs[k] for k in names) + tail
 
     @staticmethod
-    def backward(ctx, g_rgb_c, g_disp_c, g_acc_c, g_depth_c, g_rgb_f, g_disp_f, g_acc_f, g_depth_f, *g_spread):
+    def backward(ctx, g_rgb_c, g_disp_c, g_acc_c, g_depth_c, g_rgb_f, g_disp_f, g_acc_f, g_depth_f, *g_tail):
         call, lib = ctx.call, ctx.call.lib
         rays, model_c, model_f, ws, flats = ctx.keep
         if call.layout == 0:
@@ -161,10 +177,12 @@ class _FusedRender(torch.autograd.Function):
         keep = [None if g is None else g.contiguous().float()
                 for g in (g_rgb_c, g_acc_c, g_depth_c, g_rgb_f, g_acc_f, g_depth_f)]
         parts = 0
-        g_sp = [None if g is None else g.contiguous().float() for g in g_spread] + [None, None]
-        if any(k is not None for k in keep[:3]) or g_sp[0] is not None:
+        g_tail = [None if g is None else g.contiguous().float() for g in g_tail]
+        g_sp = (g_tail[:2] if ctx.spread else []) + [None, None]
+        g_dp = (g_tail[2:4] if ctx.spread else g_tail[:2]) + [None, None] if ctx.prior is not None else [None, None]
+        if any(k is not None for k in keep[:3]) or g_sp[0] is not None or g_dp[0] is not None:
             parts |= L.PART_COARSE
-        if nf > 0 and (any(k is not None for k in keep[3:]) or g_sp[1] is not None):
+        if nf > 0 and (any(k is not None for k in keep[3:]) or g_sp[1] is not None or g_dp[1] is not None):
             parts |= L.PART_FINE
         if ctx.frozen:
             return (_FusedRender._frozen_backward(ctx, keep, parts),) + (None,) * (6 + ctx.n_params)
@@ -173,10 +191,9 @@ class _FusedRender(torch.autograd.Function):
         g_rays = torch.zeros_like(rays) if flats is not None else None
         if parts:
             gw = [None, None]
-            if ctx.spread:   # (the weight cotangents of the passes whose spread a loss touched)
-                for fine in (0, 1):
-                    if g_sp[fine] is not None:
-                        gw[fine] = torch.empty((n, cfg.num_coarse + (nf if fine else 0)), dtype=torch.float32, device=dev)
+            for fine in (0, 1):   # (the weight cotangents of the passes whose spread or depth losses a loss touched)
+                if g_sp[fine] is not None or g_dp[fine] is not None:
+                    gw[fine] = torch.empty((n, cfg.num_coarse + (nf if fine else 0)), dtype=torch.float32, device=dev)
             g_weights = [_ptr(g) for g in gw] if (gw[0] is not None or gw[1] is not None) else None
             tmp = rays_args = None
             if g_rays is not None:
@@ -192,8 +209,11 @@ class _FusedRender(torch.autograd.Function):
                 passes = [L.PART_FINE, L.PART_COARSE]
             with _forward_modes(ctx), L.launch_on(rays, ws, gpc, gpf, tmp, *[k for k in keep if k is not None]) as st:
                 for fine in (0, 1):
-                    if gw[fine] is not None:
+                    if g_sp[fine] is not None:
                         call.spread(fine, 1.0, g_sp[fine].data_ptr(), None, gw[fine].data_ptr(), st)
+                    if g_dp[fine] is not None:   # (behind the spread term: added to the cotangent it wrote)
+                        call.depth_prior(fine, ctx.prior.data_ptr(), 3, None, n, 1.0, 1.0, 1.0, g_dp[fine].data_ptr(), None,
+                                         gw[fine].data_ptr(), g_sp[fine] is not None, st)
                 for part in passes:
                     call.backward([_ptr(k) for k in keep], (gpc.data_ptr(), _ptr(gpf)), part, st, g_weights, rays_args)
                     # (the words in the shared buffers: the coarse net's behind a pass that ran it -- it runs last --, the fine net's
@@ -243,7 +263,14 @@ def _forward_modes(ctx):
                 lib.plan_set_bwd_compaction(plan, cur)
 
 
-def _predict_fused(ray_batch, model_coarse, model_fine, opts, occupancy=None, spread=False):
+def _check_prior_rows(depth_prior, n, dev):
+    if (not isinstance(depth_prior, torch.Tensor) or depth_prior.device != dev or depth_prior.dtype != torch.float32
+            or tuple(depth_prior.shape) != (n, 3)):
+        raise ValueError("depth_prior must be a float32 (%d, 3) tensor of (depth, weight, sigma) rows on %s" % (n, dev))
+    return depth_prior.detach().contiguous()
+
+
+def _predict_fused(ray_batch, model_coarse, model_fine, opts, occupancy=None, spread=False, depth_prior=None):
     rays_grad = bool(ray_batch.requires_grad and torch.is_grad_enabled())
     rays = ray_batch.contiguous().float() if rays_grad else ray_batch.detach().contiguous().float()
     n = rays.shape[0]
@@ -271,10 +298,11 @@ def _predict_fused(ray_batch, model_coarse, model_fine, opts, occupancy=None, sp
         outs = render_fwd_occ(rays, model_coarse, model_fine if nf > 0 else None, cfg_tuple, (t_rand, noise_c, u, noise_f), occupancy)
         rgb_c, disp_c, acc_c, _, rgb_f, disp_f, acc_f, _ = outs
         return (rgb_c, disp_c, acc_c, rgb_f, disp_f, acc_f) if nf > 0 else (rgb_c, disp_c, acc_c, None, None, None)
-    outs = _FusedRender.apply(rays, model_coarse, model_fine if nf > 0 else None, cfg_tuple + (bool(spread),),
+    tail_cfg = (bool(spread),) if depth_prior is None else (bool(spread), _check_prior_rows(depth_prior, n, dev))
+    outs = _FusedRender.apply(rays, model_coarse, model_fine if nf > 0 else None, cfg_tuple + tail_cfg,
                               (t_rand, noise_c, u, noise_f), training, rays_grad, *pc, *pf)
     rgb_c, disp_c, acc_c, depth_c, rgb_f, disp_f, acc_f, depth_f = outs[:8]
-    tail = tuple(outs[8:])   # (spread=True: the two per-ray spread losses)
+    tail = tuple(outs[8:])   # (spread=True: the two per-ray spread losses; depth_prior: the two (n, 2) depth losses behind them)
     if rgb_c.requires_grad:
         # disparity re-derived from the differentiable depth / accumulation maps with the reference's own torch ops
         # (volume_rendering_utils.py:46-48: same values as the kernel's, and autograd covers a loss on it)
@@ -298,11 +326,15 @@ def _predict_culled(ray_batch, model_coarse, model_fine, opts, encode_position_f
 
 
 def predict_and_render_radiance(ray_batch, model_coarse, model_fine, options, mode="train", encode_position_fn=None,
-                                encode_direction_fn=None, occupancy=None, spread=False):
+                                encode_direction_fn=None, occupancy=None, spread=False, depth_prior=None):
     """nerf/train_utils.py:28-127.  Returns (rgb_coarse, disp_coarse, acc_coarse, rgb_fine, disp_fine, acc_fine).
     spread: True (train mode on the fused path only; anything else raises ValueError) -- the tuple gains two trailing tensors, the
     per-ray spread loss of each pass's ray weights (mip-NeRF 360's L_dist; include/nerfhip.h nerfhip_spread_loss): spread_coarse (n) and
     spread_fine (n; None without a fine net), both differentiable w.r.t. the nets.
+    depth_prior: None, or the batch's prior rows, float32 (n, 3) of (depth, weight, sigma), weight 0 = no prior (train mode on the fused
+    path only; anything else raises ValueError) -- the tuple gains two more trailing tensors, behind the spread pair when both are asked
+    for: depth_loss_coarse (n, 2) and depth_loss_fine (n, 2; None without a fine net), each ray's (E, Tm) of include/nerfhip.h
+    nerfhip_depth_prior_loss, differentiable w.r.t. the nets.
     occupancy: None, or an occupancy.OccupancyGrid -- with mode="validation" and no gradient wanted, the samples in its empty cells
     skip the MLPs (nerfhip_render_fwd_occ) and the chunk's counts are added to the grid's view_counts; in train mode it raises
     NotImplementedError."""
@@ -313,12 +345,18 @@ def predict_and_render_radiance(ray_batch, model_coarse, model_fine, options, mo
                    or not _fusable(model_coarse, model_fine, encode_position_fn, encode_direction_fn, opts.num_fine)):
         raise ValueError("spread=True needs mode=\"train\" on the fused render (FlexibleNeRFModel nets and their own embedding functions, "
                          "no occupancy grid)")
+    if depth_prior is not None and (mode != "train" or occupancy is not None
+                                    or not _fusable(model_coarse, model_fine, encode_position_fn, encode_direction_fn, opts.num_fine)):
+        raise ValueError("depth_prior=... needs mode=\"train\" on the fused render (FlexibleNeRFModel nets and their own embedding "
+                         "functions, no occupancy grid)")
     if occupancy is not None:
         if mode != "validation":
             raise NotImplementedError(_OCC_TRAIN_MSG)
         return _predict_culled(ray_batch, model_coarse, model_fine, opts, encode_position_fn, encode_direction_fn, occupancy)
     if _fusable(model_coarse, model_fine, encode_position_fn, encode_direction_fn, opts.num_fine):
-        return _predict_fused(ray_batch, model_coarse, model_fine, opts, spread=spread)
+        if depth_prior is None:
+            return _predict_fused(ray_batch, model_coarse, model_fine, opts, spread=spread)
+        return _predict_fused(ray_batch, model_coarse, model_fine, opts, spread=spread, depth_prior=depth_prior)
 
     # generic composition (arbitrary networks / encoders), mirroring the reference step by step
     lib = L.get_lib()
@@ -761,14 +799,18 @@ def select_cached_training_rays(cache_dict, num_random_rays, options, select_ind
 
 
 def run_one_iter_of_nerf(height, width, focal_length, model_coarse, model_fine, ray_origins, ray_directions, options,
-                         mode="train", encode_position_fn=None, encode_direction_fn=None, occupancy=None, spread=False):
+                         mode="train", encode_position_fn=None, encode_direction_fn=None, occupancy=None, spread=False, depth_prior=None):
     """nerf/train_utils.py:130-202.  occupancy: see predict_and_render_radiance (mode="validation" only); the grid's view_counts
     are zeroed first, so that after the call they are the sums over every ray chunk of this call.
-    spread: see predict_and_render_radiance (mode="train" only): two trailing per-ray tensors, spread_coarse and spread_fine."""
+    spread: see predict_and_render_radiance (mode="train" only): two trailing per-ray tensors, spread_coarse and spread_fine.
+    depth_prior: see predict_and_render_radiance (mode="train" only): one (depth, weight, sigma) row per ray, chunked with the rays; two
+    more trailing tensors, depth_loss_coarse and depth_loss_fine (n, 2), behind the spread pair."""
     if not ray_directions.is_cuda:
         raise RuntimeError("run_one_iter_of_nerf needs CUDA (HIP) tensors: nerf_pytorch_amd has no CPU path")
     if spread and mode != "train":
         raise ValueError("spread=True needs mode=\"train\"")
+    if depth_prior is not None and mode != "train":
+        raise ValueError("depth_prior=... needs mode=\"train\"")
     restore_shapes = [ray_directions.shape, ray_directions.shape[:-1], ray_directions.shape[:-1]]
     if model_fine:
         restore_shapes += restore_shapes
@@ -782,9 +824,15 @@ def run_one_iter_of_nerf(height, width, focal_length, model_coarse, model_fine, 
         pred = [_predict_culled(batch, model_coarse, model_fine, options.nerf.train, encode_position_fn, encode_direction_fn, occupancy)
                 for batch in batches]
     else:
+        extra = [{"spread": True} if spread else {} for _ in batches]
+        if depth_prior is not None:
+            if depth_prior.shape[0] != rays.shape[0]:
+                raise ValueError("depth_prior must hold one row per ray (%d rays, %d rows)" % (rays.shape[0], depth_prior.shape[0]))
+            for kw, rows in zip(extra, get_minibatches(depth_prior, chunksize=getattr(options.nerf, mode).chunksize)):
+                kw["depth_prior"] = rows
         pred = [predict_and_render_radiance(batch, model_coarse, model_fine, options,
                                             encode_position_fn=encode_position_fn,
-                                            encode_direction_fn=encode_direction_fn, **({"spread": True} if spread else {})) for batch in batches]
+                                            encode_direction_fn=encode_direction_fn, **kw) for batch, kw in zip(batches, extra)]
     synthesized_images = list(zip(*pred))
     synthesized_images = [torch.cat(image, dim=0) if image[0] is not None else None for image in synthesized_images]
     if mode == "validation":
