@@ -480,6 +480,42 @@ int nerfhip_depth_prior_loss(const float* raw, const float* z, const float* rays
                              float scale, const float* g_loss, float* loss, float* g_weights, int accumulate,
                              nerfhip_stream_t stream);
 
+/* ---- interlevel proposal loss (mip-NeRF 360's L_prop, Barron et al. 2022, eq. 13): train the coarse net from the fine weights ----
+ * One ray has a coarse pass and a fine pass:
+ * - The coarse pass has Sc samples at depths z^_0 <= ... <= z^_{Sc-1} with weights w^_j.
+ * - The fine pass has Sf samples at depths z_0 <= ... <= z_{Sf-1} with weights w_i.
+ * - Both sets of weights are formed exactly as the compositing forms them. That means nerfhip_volume_render_fwd's weights bit for
+ *   bit: the same noise draws (streams 1 and 3) and the same fp64 transmittance scan, as in spread.hip.
+ * - far is column 7 of the packed row.
+ * Edges follow the spread loss's convention. Sample k owns [z_k, z_{k+1}], and the last sample owns [z_last, max(far, z_last)]:
+ *     e^_0..e^_Sc :  e^_j = z^_j (j < Sc),  e^_Sc = max(far, z^_{Sc-1})        e_0..e_Sf likewise from z
+ *     lo_i = min( #{k in 1..Sc   : e^_k <= e_i     },  Sc-1 )              (searchsorted right on e^[1:])
+ *     hi_i = max( #{k in 0..Sc-1 : e^_k <  e_{i+1} } - 1,  lo_i )          (searchsorted left on e^[:-1])
+ *     B_i  = sum_{j=lo_i..hi_i} w^_j                                       (the bound: coarse intervals overlapping fine interval i)
+ *     L    = sum_i max(0, w_i - B_i)^2 / (w_i + eps),   eps = 2^-23        (multinerf's eps)
+ *     dL/dw^_j = sum_{i : lo_i <= j <= hi_i}  -2 max(0, w_i - B_i) / (w_i + eps)
+ *     dL/dw_i == 0                                                         (stop-gradient on the fine weights)
+ * - The comparisons are on the fp32 depths, which is exact.
+ * - Every fine interval overlaps at least one coarse interval. This covers zero-width intervals, the deterministic case
+ *   z_last == far, and fine samples outside the coarse range.
+ * - Exactly touching intervals do not overlap.
+ * - lo and hi are non-decreasing in i. Hence the set of i that reaches a given j is a contiguous range.
+ * - Depths are constants, as for the sibling losses. NaN in either raw propagates.
+ * raw_coarse dev [n,Sc,4], z_coarse dev [n,Sc], raw_fine dev [n,Sf,4], z_fine dev [n,Sf], rays dev [n, ray_stride >= 8];
+ * noise_coarse dev [n,Sc] / noise_fine dev [n,Sf] or NULL (in-kernel draws of streams 1 / 3 keyed by seed and ray_offset), read
+ * when noise_std > 0.  loss (optional) dev [n]: the unscaled L of each ray.  g_weights_coarse (optional) dev [n,Sc] =
+ * scale * (g_loss ? g_loss[r] : 1) * dL/dw^_j, g_loss dev [n] or NULL: the coarse pass's cotangent that nerfhip_volume_render_bwd and
+ * the _w entry points take.  accumulate != 0: the value is ADDED to what g_weights_coarse[r,j] holds (one fp32 add) -- the term
+ * stacks behind the spread and depth terms; accumulate == 0: every entry is written.  At least one output, and a single-output call
+ * gives the combined call's bits.  Sc >= 1, Sf >= 1, and THE CAP: Sc + Sf <= 4096 (the ray's prefix sums and index ranges live in
+ * 20 / 12 bytes of LDS per coarse / fine sample, 80 KiB at most); anything above is refused, never launched.  n == 0 launches nothing.
+ * O((Sc + Sf) log) per ray: fp64 prefix sums in a fixed order (no atomics; the coarse prefix in two doubles, so that B_i behind an
+ * opaque sample keeps its own relative precision), bounded binary searches, each output rounded to fp32 once. */
+int nerfhip_proposal_loss(const float* raw_coarse, const float* z_coarse, int s_coarse, const float* raw_fine, const float* z_fine,
+                          int s_fine, const float* rays, int ray_stride, int64_t n, float noise_std, const float* noise_coarse,
+                          const float* noise_fine, uint64_t seed, uint64_t ray_offset, float scale, const float* g_loss, float* loss,
+                          float* g_weights_coarse, int accumulate, nerfhip_stream_t stream);
+
 /* d(loss)/d(rays) ALONE, for frozen nets (camera localisation against a trained field): nerfhip_render_bwd_rays' contract -- parts,
  * NERFHIP_PART_SHARED_BWD, the first pass that runs overwrites g_rays and the second accumulates, params_* = the flat vectors the
  * packed images were made from (theta_eff under an encoding window) -- without g_params: no parameter gradient is computed or

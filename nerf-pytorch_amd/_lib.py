@@ -152,6 +152,8 @@ _PROTOS = {
                                        c_f, c_f, c_f, c_f]),
     "nerfhip_depth_prior_loss": (C.c_int, [c_f, c_f, c_f, C.c_int, c_i64, C.c_int, C.c_float, c_f, c_u64, c_u32, c_u64, c_f, c_i64,
                                             c_f, c_i64, C.c_float, C.c_float, C.c_float, c_f, c_f, c_f, C.c_int, c_f]),
+    "nerfhip_proposal_loss": (C.c_int, [c_f, c_f, C.c_int, c_f, c_f, C.c_int, c_f, C.c_int, c_i64, C.c_float, c_f, c_f, c_u64, c_u64,
+                                         C.c_float, c_f, c_f, c_f, C.c_int, c_f]),
     "nerfhip_render_grad_rays_tmp_bytes": (c_i64, [C.c_void_p, C.c_void_p, C.POINTER(RenderCfg), c_i64]),
     "nerfhip_render_grad_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RenderCfg), c_f, c_i64, c_f, c_f,
                                             C.POINTER(RenderRand), c_u64, c_u64, C.POINTER(RenderCotangents), c_f, c_i64,

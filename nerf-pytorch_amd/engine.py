@@ -28,6 +28,12 @@ Depth priors (DS-NeRF; `depth_loss=` and a step's `depth_prior=`
 nerfhip_depth_prior_loss launch on the stream its backward runs on, behind the spread launch where there is one (then accumulating into
 the same weight cotangent), ahead of the _w form of its backward; `depth_losses` reads the means.  A step without `depth_prior=` is
 the step without the feature.
+
+Interlevel proposal loss (mip-NeRF 360's L_prop; `proposal=` and `coarse_photometric=`): the coarse net's loss gains
+lambda * mean_ray(L) -- one nerfhip_proposal_loss launch in the coarse net's pass, behind the spread and depth launches (accumulating
+into their cotangent where either ran), ahead of the _w form of its backward.  The kernel reads the FINE pass's raw rows and depths:
+on two streams the coarse net's pass starts behind the fine forward, and overlaps the fine backward only.  coarse_photometric=False
+withholds the colour cotangent from the coarse backward: the coarse net learns from its weight losses alone.
 """
 import math
 
@@ -47,7 +53,7 @@ class TrainEngine:
     def __init__(self, model_coarse, model_fine, num_coarse, num_fine, perturb=True, lindisp=False, white_background=False,
                  noise_std=0.0, lr=5e-3, betas=(0.9, 0.999), eps=1e-8, seed=0, process_group=None, world_size=None,
                  rank=None, overlap=None, always_reduce=False, backward=None, window=None, total_steps=None, occupancy=None,
-                 occupancy_warmup=256, occupancy_every=16, spread=None, depth_loss=None):
+                 occupancy_warmup=256, occupancy_every=16, spread=None, depth_loss=None, proposal=None, coarse_photometric=True):
         self.lib = L.get_lib()
         self.mc, self.mf = model_coarse, model_fine if num_fine > 0 else None
         self.dev = model_coarse.flat_params.device
@@ -146,6 +152,23 @@ class TrainEngine:
         self._depth_bufs = None    # per net with a nonzero weight: (weight cotangent [n, S], per-ray losses [n, 2]), sized in _prepare
         self._depth_ran = False    # whether the last step launched the depth kernel (depth_losses)
         self._depth_keep = None    # the last step's prior table and indices (alive until the next step: the launches read them)
+        # interlevel proposal loss (mip-NeRF 360's L_prop): None / 0 -- the step as it always was, launch for launch; a
+        # weight lambda > 0 -- the coarse net's loss gains lambda * mean_ray(L) of its weight histogram against the fine pass's weights
+        # (a constant of the term: the fine net's gradient does not move)
+        if proposal is None:
+            proposal = 0.0
+        if isinstance(proposal, bool) or not isinstance(proposal, (int, float)) or not (proposal >= 0.0 and math.isfinite(proposal)):
+            raise ValueError("TrainEngine: proposal must be None or a finite weight >= 0 (got %r)" % (proposal,))
+        if proposal > 0.0 and self.mf is None:
+            raise ValueError("TrainEngine: proposal > 0 needs a fine net (num_fine > 0): the loss bounds the fine pass's weights")
+        self.proposal = float(proposal)
+        self._proposal_bufs = None   # (coarse weight cotangent [n, num_coarse], per-ray loss [n]), sized in _prepare
+        # coarse_photometric=False: the coarse backward is given no colour cotangent (its MSE is still launched and reported); it needs
+        # a weight loss on the coarse net, or that net would learn nothing
+        self.coarse_photometric = bool(coarse_photometric)
+        if not self.coarse_photometric and not (self.proposal > 0.0 or self.spread[0] > 0.0 or any(self.depth_loss[0])):
+            raise ValueError("TrainEngine: coarse_photometric=False leaves the coarse net without any loss: give it proposal > 0 (or a "
+                             "spread or depth weight on the coarse net)")
         self._stats = BM.StatsReader(("coarse", "fine"))
         self._zero_frac = self._stats.frac   # last known fraction of all-zero d(loss)/d(raw) rows per net (updated in place)
         # steps run dense / compacted / recomputed / fused / fused over the list / fused over the stash, per net ("auto")
@@ -235,6 +258,9 @@ class TrainEngine:
             self._depth_bufs = {fine: (self._spread_bufs[fine][0] if self.spread[fine] > 0.0 else mk(n, S[fine]),
                                        torch.zeros(n, 2, dtype=torch.float32, device=self.dev))
                                 for fine in (0, 1) if any(self.depth_loss[fine])}
+        if self.proposal > 0.0:   # (what the proposal kernel writes; the coarse weight cotangent is the spread / depth terms' where they have one)
+            shared = (self._spread_bufs or {}).get(0) or (self._depth_bufs or {}).get(0)
+            self._proposal_bufs = (shared[0] if shared else mk(n, self.cfg.num_coarse), torch.zeros(n, dtype=torch.float32, device=self.dev))
 
     def workspace_bytes(self):
         return 0 if self._ws is None else self._wsb
@@ -343,6 +369,13 @@ class TrainEngine:
         if frozen and any(self.spread):
             raise ValueError("TrainEngine: a frozen step (localize_*, the exposure fit) with spread > 0 makes no sense: the spread loss "
                              "regularises the nets, and a frozen step updates none")
+        if frozen and self.proposal > 0.0:
+            raise ValueError("TrainEngine: a frozen step (localize_*, the exposure fit) with proposal > 0 makes no sense: the proposal "
+                             "loss trains the coarse net, and a frozen step updates none")
+        if not self.coarse_photometric and not frozen and not (self.proposal > 0.0 or self.spread[0] > 0.0
+                                                               or (dp is not None and any(self.depth_loss[0]))):
+            raise ValueError("TrainEngine: coarse_photometric=False and a step without depth_prior=...: the coarse net's only loss is "
+                             "its depth term, and this step has none")
         if self.occupancy is not None and (ray_grad is not None or frozen):
             raise NotImplementedError("TrainEngine: a step with a ray gradient (pose, camera, intrinsics or distortion gradients) or a "
                                       "frozen step (localize_*) is not implemented with occupancy=...: the ray gradient of the culled "
@@ -385,7 +418,8 @@ class TrainEngine:
         gc = self.grad[:self.nc_params]
         gf = self.grad[self.nc_params:] if nf > 0 else None
         tstride = target.stride(0)
-        cot_c = (b["g_c"].data_ptr(), None, None, None, None, None)
+        # (coarse_photometric=False: the coarse backward gets no colour cotangent -- a frozen step's ray gradient keeps it)
+        cot_c = (b["g_c"].data_ptr() if self.coarse_photometric or frozen else None, None, None, None, None, None)
         cot_f = (None, None, None, b["g_f"].data_ptr() if nf > 0 else None, None, None)
         rand = None
         if draws is not None:
@@ -428,6 +462,12 @@ class TrainEngine:
                 call.depth_prior(fine, dp[0].data_ptr(), dp[1], None if dp[2] is None else dp[2].data_ptr(), dp[3], a, bb, gscale / n,
                                  None, dl.data_ptr(), gw.data_ptr(), self.spread[fine] > 0.0, stream)
                 g_weights = (None, gw.data_ptr()) if fine else (gw.data_ptr(), None)
+            if not fine and self.proposal > 0.0:
+                gw, pl = self._proposal_bufs
+                # (scale: lambda / n as for the spread term; behind a spread or depth launch the term is added to the cotangent it wrote.
+                # Reads the fine pass's raw rows and depths: `stream` is behind the fine forward, and the fine backward only reads them)
+                call.proposal(self.proposal * gscale / n, None, pl.data_ptr(), gw.data_ptr(), g_weights is not None, stream)
+                g_weights = (gw.data_ptr(), None)
             if exposure is None:
                 lib.mse_loss_fwd_bwd(rgb.data_ptr(), None, target.data_ptr(), tstride, n, gscale, g_rgb.data_ptr(), None, loss.data_ptr(), stream)
             else:
@@ -454,16 +494,24 @@ class TrainEngine:
             main, side = self._streams()
             st = main.cuda_stream
             two = self.overlap and nf > 0
+            late = two and self.proposal > 0.0   # (the coarse net's pass reads the fine forward's rows: it overlaps the fine backward only)
             fwd(L.PART_COARSE, st)
-            if two:   # the coarse net's pass next to the fine forward and backward
+            if two:
                 e1, e2 = self._ev
+            if two and not late:   # the coarse net's pass next to the fine forward and backward
                 e1.record(main)
                 side.wait_event(e1)
                 net_pass(*coarse, side.cuda_stream)
                 e2.record(side)
             if nf > 0:
                 fwd(L.PART_FINE, st)
+                if late:
+                    e1.record(main)
                 net_pass(*fine, st)
+                if late:   # the coarse net's pass next to the fine backward
+                    side.wait_event(e1)
+                    net_pass(*coarse, side.cuda_stream)
+                    e2.record(side)
                 if self._reduce and not frozen:  # in flight while the coarse backward computes
                     self._pending.append(allreduce_gradients(gf, self.pg, async_op=True, single_rank=True))
             if two:
@@ -527,6 +575,12 @@ class TrainEngine:
         the first step."""
         b = self._spread_bufs or {}
         return tuple(b[fine][1].mean() if fine in b else None for fine in (0, 1))
+
+    @property
+    def proposal_loss(self):
+        """The mean over the last step's rays of the unscaled interlevel loss L, as a device scalar formed on demand from the per-ray
+        buffer the proposal kernel wrote (no host synchronisation); None without a proposal weight or before the first step."""
+        return None if self._proposal_bufs is None else self._proposal_bufs[1].mean()
 
     @property
     def depth_losses(self):

@@ -128,3 +128,15 @@ class RenderCall:
                                          self.cfg.ray_stride, self.n, S, self.cfg.noise_std, self.rand[3 if fine else 1], self.seed,
                                          3 if fine else 1, self.ray_offset, prior, prior_stride, inds, prior_rows, w_expected,
                                          w_termination, scale, g_loss, loss, g_weights, int(bool(accumulate)), stream)
+
+    def proposal(self, scale, g_loss, loss, g_weights, accumulate, stream):
+        """nerfhip_proposal_loss over the raw rows and depths BOTH passes' forwards left in the workspace, each with its pass's noise:
+        the per-ray interlevel loss and its gradient w.r.t. the coarse pass's weights (g_weights: [n, num_coarse])."""
+        cfg = self.cfg
+        if cfg.num_fine <= 0:
+            raise ValueError("RenderCall.proposal: the interlevel loss needs a fine pass (num_fine > 0)")
+        reg = lambda name: self.ws + self.region(name)[0]  # noqa: E731
+        return self.lib.proposal_loss(reg("raw_coarse"), reg("z_coarse"), cfg.num_coarse, reg("raw_fine"), reg("z_fine"),
+                                      cfg.num_coarse + cfg.num_fine, self.rays, cfg.ray_stride, self.n, cfg.noise_std, self.rand[1],
+                                      self.rand[3], self.seed, self.ray_offset, scale, g_loss, loss, g_weights, int(bool(accumulate)),
+                                      stream)

@@ -90,13 +90,21 @@ class _FusedRender(torch.autograd.Function):
     With prior rows (an optional eighth entry of cfg_tuple: a contiguous float32 (n, 3) tensor of (depth, weight, sigma)) the node has
     two more differentiable outputs behind those: the per-ray (E, Tm) of each pass, (n, 2) (nerfhip_depth_prior_loss; None for the fine
     pass without a fine net).  Its backward runs the kernel again with the incoming cotangents as g_loss -- accumulating behind the
-    spread term where both are asked for -- and calls the _w form of the render backward."""
+    spread term where both are asked for -- and calls the _w form of the render backward.
+
+    With the `proposal` flag (an optional ninth entry of cfg_tuple; needs a fine net) the node has one more differentiable output behind
+    those: the per-ray interlevel loss (n) (nerfhip_proposal_loss), differentiable w.r.t. the COARSE net only.  Its backward runs the
+    kernel again with the incoming cotangent as g_loss -- accumulating behind the coarse pass's spread and depth terms -- for the
+    coarse weight cotangent of the _w render backward."""
 
     @staticmethod
     def forward(ctx, rays, model_c, model_f, cfg_tuple, rand, training, rays_grad, *params):
         lib = L.get_lib()
         nc, nf, perturb, lindisp, white, noise_std, spread = cfg_tuple[:7]
         prior = cfg_tuple[7] if len(cfg_tuple) > 7 else None
+        proposal = bool(cfg_tuple[8]) if len(cfg_tuple) > 8 else False
+        if proposal and nf <= 0:
+            raise ValueError("proposal=True needs a fine net (num_fine > 0): the loss bounds the fine pass's weights")
         n, stride = rays.shape
         dev = rays.device
         cfg = L.RenderCfg(nc, nf, int(bool(perturb)), int(bool(lindisp)), int(bool(white)), float(noise_std), stride)
@@ -145,10 +153,11 @@ class _FusedRender(torch.autograd.Function):
         ctx.mark_non_differentiable(bufs["disp_coarse"], bufs["disp_fine"])
         ctx.spread = bool(spread)
         ctx.prior = prior
-        if not spread and prior is None:
+        ctx.proposal = proposal
+        if not spread and prior is None and not proposal:
             return tuple(bufs[k] for k in names)
         if ctx.frozen:
-            raise ValueError("spread=True or depth_prior=... on frozen nets (set_frozen) makes no sense: these losses regularise the nets")
+            raise ValueError("spread=True, depth_prior=... or proposal=True on frozen nets (set_frozen) makes no sense: these losses regularise the nets")
         tail = ()
         if spread:
             sp = [torch.empty(n, dtype=torch.float32, device=dev) for _ in range(2 if nf > 0 else 1)]
@@ -162,6 +171,11 @@ class _FusedRender(torch.autograd.Function):
                 for fine, out_dp in enumerate(dp):
                     call.depth_prior(fine, prior.data_ptr(), 3, None, n, 1.0, 1.0, 1.0, None, out_dp.data_ptr(), None, False, st)
             tail += (dp[0], dp[1] if nf > 0 else None)
+        if proposal:
+            pl = torch.empty(n, dtype=torch.float32, device=dev)
+            with L.launch_on(rays, ws, pl) as st:   # (the loss alone, over both passes' raw rows and depths)
+                call.proposal(1.0, None, pl.data_ptr(), None, False, st)
+            tail += (pl,)
         return tuple(bufs[k] for k in names) + tail
 
     @staticmethod
@@ -180,7 +194,8 @@ class _FusedRender(torch.autograd.Function):
         g_tail = [None if g is None else g.contiguous().float() for g in g_tail]
         g_sp = (g_tail[:2] if ctx.spread else []) + [None, None]
         g_dp = (g_tail[2:4] if ctx.spread else g_tail[:2]) + [None, None] if ctx.prior is not None else [None, None]
-        if any(k is not None for k in keep[:3]) or g_sp[0] is not None or g_dp[0] is not None:
+        g_pp = g_tail[2 * (int(ctx.spread) + int(ctx.prior is not None))] if ctx.proposal else None
+        if any(k is not None for k in keep[:3]) or g_sp[0] is not None or g_dp[0] is not None or g_pp is not None:
             parts |= L.PART_COARSE
         if nf > 0 and (any(k is not None for k in keep[3:]) or g_sp[1] is not None or g_dp[1] is not None):
             parts |= L.PART_FINE
@@ -192,7 +207,7 @@ class _FusedRender(torch.autograd.Function):
         if parts:
             gw = [None, None]
             for fine in (0, 1):   # (the weight cotangents of the passes whose spread or depth losses a loss touched)
-                if g_sp[fine] is not None or g_dp[fine] is not None:
+                if g_sp[fine] is not None or g_dp[fine] is not None or (not fine and g_pp is not None):
                     gw[fine] = torch.empty((n, cfg.num_coarse + (nf if fine else 0)), dtype=torch.float32, device=dev)
             g_weights = [_ptr(g) for g in gw] if (gw[0] is not None or gw[1] is not None) else None
             tmp = rays_args = None
@@ -214,6 +229,8 @@ class _FusedRender(torch.autograd.Function):
                     if g_dp[fine] is not None:   # (behind the spread term: added to the cotangent it wrote)
                         call.depth_prior(fine, ctx.prior.data_ptr(), 3, None, n, 1.0, 1.0, 1.0, g_dp[fine].data_ptr(), None,
                                          gw[fine].data_ptr(), g_sp[fine] is not None, st)
+                if g_pp is not None:   # (behind the coarse pass's spread and depth terms: added to the cotangent they wrote)
+                    call.proposal(1.0, g_pp.data_ptr(), None, gw[0].data_ptr(), g_sp[0] is not None or g_dp[0] is not None, st)
                 for part in passes:
                     call.backward([_ptr(k) for k in keep], (gpc.data_ptr(), _ptr(gpf)), part, st, g_weights, rays_args)
                     # (the words in the shared buffers: the coarse net's behind a pass that ran it -- it runs last --, the fine net's
@@ -270,7 +287,7 @@ def _check_prior_rows(depth_prior, n, dev):
     return depth_prior.detach().contiguous()
 
 
-def _predict_fused(ray_batch, model_coarse, model_fine, opts, occupancy=None, spread=False, depth_prior=None):
+def _predict_fused(ray_batch, model_coarse, model_fine, opts, occupancy=None, spread=False, depth_prior=None, proposal=False):
     rays_grad = bool(ray_batch.requires_grad and torch.is_grad_enabled())
     rays = ray_batch.contiguous().float() if rays_grad else ray_batch.detach().contiguous().float()
     n = rays.shape[0]
@@ -299,10 +316,14 @@ def _predict_fused(ray_batch, model_coarse, model_fine, opts, occupancy=None, sp
         rgb_c, disp_c, acc_c, _, rgb_f, disp_f, acc_f, _ = outs
         return (rgb_c, disp_c, acc_c, rgb_f, disp_f, acc_f) if nf > 0 else (rgb_c, disp_c, acc_c, None, None, None)
     tail_cfg = (bool(spread),) if depth_prior is None else (bool(spread), _check_prior_rows(depth_prior, n, dev))
+    if proposal:   # (the ninth entry; without it the tuple is what it always was)
+        tail_cfg = (tail_cfg + (None,))[:2] + (True,)
     outs = _FusedRender.apply(rays, model_coarse, model_fine if nf > 0 else None, cfg_tuple + tail_cfg,
                               (t_rand, noise_c, u, noise_f), training, rays_grad, *pc, *pf)
     rgb_c, disp_c, acc_c, depth_c, rgb_f, disp_f, acc_f, depth_f = outs[:8]
-    tail = tuple(outs[8:])   # (spread=True: the two per-ray spread losses; depth_prior: the two (n, 2) depth losses behind them)
+    # (spread=True: the two per-ray spread losses; depth_prior: the two (n, 2) depth losses behind them; proposal=True: the per-ray
+    # interlevel loss last)
+    tail = tuple(outs[8:])
     if rgb_c.requires_grad:
         # disparity re-derived from the differentiable depth / accumulation maps with the reference's own torch ops
         # (volume_rendering_utils.py:46-48: same values as the kernel's, and autograd covers a loss on it)
@@ -326,7 +347,7 @@ def _predict_culled(ray_batch, model_coarse, model_fine, opts, encode_position_f
 
 
 def predict_and_render_radiance(ray_batch, model_coarse, model_fine, options, mode="train", encode_position_fn=None,
-                                encode_direction_fn=None, occupancy=None, spread=False, depth_prior=None):
+                                encode_direction_fn=None, occupancy=None, spread=False, depth_prior=None, proposal=False):
     """nerf/train_utils.py:28-127.  Returns (rgb_coarse, disp_coarse, acc_coarse, rgb_fine, disp_fine, acc_fine).
     spread: True (train mode on the fused path only; anything else raises ValueError) -- the tuple gains two trailing tensors, the
     per-ray spread loss of each pass's ray weights (mip-NeRF 360's L_dist; include/nerfhip.h nerfhip_spread_loss): spread_coarse (n) and
@@ -335,6 +356,9 @@ def predict_and_render_radiance(ray_batch, model_coarse, model_fine, options, mo
     path only; anything else raises ValueError) -- the tuple gains two more trailing tensors, behind the spread pair when both are asked
     for: depth_loss_coarse (n, 2) and depth_loss_fine (n, 2; None without a fine net), each ray's (E, Tm) of include/nerfhip.h
     nerfhip_depth_prior_loss, differentiable w.r.t. the nets.
+    proposal: True (train mode on the fused path with a fine net only; anything else raises ValueError) -- the tuple gains one more
+    trailing tensor, behind the spread and depth tensors when those are asked for: proposal_loss (n), each ray's interlevel loss of
+    include/nerfhip.h nerfhip_proposal_loss (mip-NeRF 360's L_prop), differentiable w.r.t. the COARSE net only.
     occupancy: None, or an occupancy.OccupancyGrid -- with mode="validation" and no gradient wanted, the samples in its empty cells
     skip the MLPs (nerfhip_render_fwd_occ) and the chunk's counts are added to the grid's view_counts; in train mode it raises
     NotImplementedError."""
@@ -349,14 +373,19 @@ def predict_and_render_radiance(ray_batch, model_coarse, model_fine, options, mo
                                     or not _fusable(model_coarse, model_fine, encode_position_fn, encode_direction_fn, opts.num_fine)):
         raise ValueError("depth_prior=... needs mode=\"train\" on the fused render (FlexibleNeRFModel nets and their own embedding "
                          "functions, no occupancy grid)")
+    if proposal and (mode != "train" or occupancy is not None or opts.num_fine <= 0
+                     or not _fusable(model_coarse, model_fine, encode_position_fn, encode_direction_fn, opts.num_fine)):
+        raise ValueError("proposal=True needs mode=\"train\" on the fused render with a fine net (FlexibleNeRFModel nets and their own "
+                         "embedding functions, num_fine > 0, no occupancy grid)")
     if occupancy is not None:
         if mode != "validation":
             raise NotImplementedError(_OCC_TRAIN_MSG)
         return _predict_culled(ray_batch, model_coarse, model_fine, opts, encode_position_fn, encode_direction_fn, occupancy)
     if _fusable(model_coarse, model_fine, encode_position_fn, encode_direction_fn, opts.num_fine):
+        kw = {"proposal": True} if proposal else {}
         if depth_prior is None:
-            return _predict_fused(ray_batch, model_coarse, model_fine, opts, spread=spread)
-        return _predict_fused(ray_batch, model_coarse, model_fine, opts, spread=spread, depth_prior=depth_prior)
+            return _predict_fused(ray_batch, model_coarse, model_fine, opts, spread=spread, **kw)
+        return _predict_fused(ray_batch, model_coarse, model_fine, opts, spread=spread, depth_prior=depth_prior, **kw)
 
     # generic composition (arbitrary networks / encoders), mirroring the reference step by step
     lib = L.get_lib()
@@ -799,18 +828,22 @@ def select_cached_training_rays(cache_dict, num_random_rays, options, select_ind
 
 
 def run_one_iter_of_nerf(height, width, focal_length, model_coarse, model_fine, ray_origins, ray_directions, options,
-                         mode="train", encode_position_fn=None, encode_direction_fn=None, occupancy=None, spread=False, depth_prior=None):
+                         mode="train", encode_position_fn=None, encode_direction_fn=None, occupancy=None, spread=False, depth_prior=None,
+                         proposal=False):
     """nerf/train_utils.py:130-202.  occupancy: see predict_and_render_radiance (mode="validation" only); the grid's view_counts
     are zeroed first, so that after the call they are the sums over every ray chunk of this call.
     spread: see predict_and_render_radiance (mode="train" only): two trailing per-ray tensors, spread_coarse and spread_fine.
     depth_prior: see predict_and_render_radiance (mode="train" only): one (depth, weight, sigma) row per ray, chunked with the rays; two
-    more trailing tensors, depth_loss_coarse and depth_loss_fine (n, 2), behind the spread pair."""
+    more trailing tensors, depth_loss_coarse and depth_loss_fine (n, 2), behind the spread pair.
+    proposal: see predict_and_render_radiance (mode="train" only): one more trailing per-ray tensor, proposal_loss, last."""
     if not ray_directions.is_cuda:
         raise RuntimeError("run_one_iter_of_nerf needs CUDA (HIP) tensors: nerf_pytorch_amd has no CPU path")
     if spread and mode != "train":
         raise ValueError("spread=True needs mode=\"train\"")
     if depth_prior is not None and mode != "train":
         raise ValueError("depth_prior=... needs mode=\"train\"")
+    if proposal and mode != "train":
+        raise ValueError("proposal=True needs mode=\"train\"")
     restore_shapes = [ray_directions.shape, ray_directions.shape[:-1], ray_directions.shape[:-1]]
     if model_fine:
         restore_shapes += restore_shapes
@@ -825,6 +858,9 @@ def run_one_iter_of_nerf(height, width, focal_length, model_coarse, model_fine, 
                 for batch in batches]
     else:
         extra = [{"spread": True} if spread else {} for _ in batches]
+        if proposal:
+            for kw in extra:
+                kw["proposal"] = True
         if depth_prior is not None:
             if depth_prior.shape[0] != rays.shape[0]:
                 raise ValueError("depth_prior must hold one row per ray (%d rays, %d rows)" % (rays.shape[0], depth_prior.shape[0]))
