@@ -18,7 +18,7 @@
  * Random draws: wherever the reference calls torch.rand / torch.randn the caller may pass the draws in
  * (parity mode: identical results for identical draws) or pass NULL and a (seed, ray_offset) pair, in
  * which case a counter-based Philox4x32-10 generator is evaluated in-kernel (production mode).  Stream
- * ids: 0 = stratified t_rand, 1 = coarse sigma noise, 2 = inverse-CDF u, 3 = fine sigma noise.
+ * ids: 0 = stratified t_rand, 1 = coarse sigma noise, 2 = inverse-CDF u, 3 = fine sigma noise, 4 = background colour.
  * nerfhip_rng_fill() writes exactly the numbers the kernels would draw.
  */
 #ifndef NERFHIP_H_
@@ -641,6 +641,31 @@ int nerfhip_occ_density_bits(const float* dens, const int* res, float tau, uint3
 int nerfhip_mse_loss_fwd_bwd(const float* rgb_coarse, const float* rgb_fine, const float* target, int target_stride,
                              int64_t n, float grad_scale, float* g_rgb_coarse, float* g_rgb_fine, float* loss_out,
                              nerfhip_stream_t stream);
+/* The loss of ONE compositing pass against RGBA targets (one call per net), with its cotangents g_rgb and g_acc for the fused backward
+ * (nerfhip_render_cotangents: g_rgb_* / g_acc_*).  rgb: dev [n,3]; acc: dev [n]; target: dev rows of target_stride >= 4 floats
+ * (C_r, C_g, C_b, a), alpha straight (un-premultiplied); a is clamped to [0, 1] on read, a NaN propagates.  loss_out: dev float[3] =
+ * {photometric, alpha, entropy}, unscaled means.  g_rgb: dev [n,3], g_acc: dev [n]; either may be NULL.
+ * Background b_r of ray r: row r of bg (dev [n,3]) if bg != NULL; else, if bg_random, three uniform draws of Philox stream 4, element
+ * 3 (ray_offset + r) + c under `seed` -- what nerfhip_rng_fill(NERFHIP_RNG_UNIFORM, seed, 4, 3 ray_offset, 3 n) writes; else the
+ * constant (bg_r, bg_g, bg_b).
+ * mode 0 (matte): t_c = a C_c + (1 - a) b_c and p_c = rgb_c + (1 - acc) b_c, both in fp64 from the fp32 inputs; d_c = (float)(p_c - t_c);
+ *   photometric = sum d_c^2 / (3 n); g_rgb_c = d_c k with k = 2 / (3 n) * grad_scale formed as nerfhip_mse_loss_fwd_bwd forms it;
+ *   alpha = sum (acc - a)^2 / n.
+ * mode 1 (weight): a is a per-pixel loss weight (a mask of transient objects or sky: 0 = ignore).  d_c = rgb_c - C_c in fp32;
+ *   photometric = sum a d_c^2 / (3 n) (the divisor is 3 n, not the sum of the weights: the ranks of a data-parallel step agree on the
+ *   scale); g_rgb_c = (d_c k) a; the background is not read; alpha = 0 and lam_alpha must be 0 (alpha is no opacity here).
+ * Both modes: entropy = mean of H(x) = -(x log x + (1 - x) log(1 - x)), x = min(max(acc, 1e-6), 1 - 1e-6); dH/dacc = log((1 - x) / x)
+ *   inside the clamp and exactly 0 where the clamp acted.
+ * g_acc[r] = -sum_c g_rgb_c b_c (matte only) + (2 lam_alpha / n) grad_scale (acc - a) + (lam_entropy / n) grad_scale dH/dacc, formed in
+ *   fp64 and rounded once; a term whose weight is exactly 0 contributes nothing (not 0 * inf).
+ * One workgroup, fp64 sums in a fixed order, no atomics; the photometric sum walks nerfhip_mse_loss_fwd_bwd's elements in its order, so
+ * that in weight mode with a == 1 everywhere loss_out[0] and g_rgb are that entry point's bits.
+ * Refused (NERFHIP_ERR_ARG, nothing launched): n <= 0; target_stride < 4; a NULL rgb, acc, target or loss_out; mode not 0 or 1; a
+ * negative or non-finite lam_alpha or lam_entropy; lam_alpha != 0 in weight mode. */
+int nerfhip_matte_loss_fwd_bwd(const float* rgb, const float* acc, const float* target, int target_stride, int64_t n,
+                               int mode, const float* bg, int bg_random, float bg_r, float bg_g, float bg_b,
+                               uint64_t seed, uint64_t ray_offset, float lam_alpha, float lam_entropy, float grad_scale,
+                               float* g_rgb, float* g_acc, float* loss_out, nerfhip_stream_t stream);
 /* torch.optim.Adam single-tensor step (no amsgrad, no weight decay) on a flat vector; step counts from 1. */
 int nerfhip_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
                       float beta1, float beta2, float eps, int64_t step, float grad_scale, nerfhip_stream_t stream);

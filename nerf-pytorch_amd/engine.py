@@ -34,6 +34,11 @@ lambda * mean_ray(L) -- one nerfhip_proposal_loss launch in the coarse net's pas
 into their cotangent where either ran), ahead of the _w form of its backward.  The kernel reads the FINE pass's raw rows and depths:
 on two streams the coarse net's pass starts behind the fine forward, and overlaps the fine backward only.  coarse_photometric=False
 withholds the colour cotangent from the coarse backward: the coarse net learns from its weight losses alone.
+
+RGBA targets (`alpha=`, `background=`, `alpha_loss=`, `opacity_entropy=`): with alpha="matte" or "weight" each net's
+loss launch is nerfhip_matte_loss_fwd_bwd in place of nerfhip_mse_loss_fwd_bwd, on the same stream, and the g_acc it writes enters the
+net's backward as the cotangent of the accumulated opacity, next to g_rgb (withheld with it under coarse_photometric=False);
+`matte_losses` reads each net's {photometric, alpha, entropy}.  Without `alpha=` the fourth column of a target is ignored, as ever.
 """
 import math
 
@@ -53,7 +58,8 @@ class TrainEngine:
     def __init__(self, model_coarse, model_fine, num_coarse, num_fine, perturb=True, lindisp=False, white_background=False,
                  noise_std=0.0, lr=5e-3, betas=(0.9, 0.999), eps=1e-8, seed=0, process_group=None, world_size=None,
                  rank=None, overlap=None, always_reduce=False, backward=None, window=None, total_steps=None, occupancy=None,
-                 occupancy_warmup=256, occupancy_every=16, spread=None, depth_loss=None, proposal=None, coarse_photometric=True):
+                 occupancy_warmup=256, occupancy_every=16, spread=None, depth_loss=None, proposal=None, coarse_photometric=True,
+                 alpha=None, background=None, alpha_loss=None, opacity_entropy=None):
         self.lib = L.get_lib()
         self.mc, self.mf = model_coarse, model_fine if num_fine > 0 else None
         self.dev = model_coarse.flat_params.device
@@ -169,6 +175,13 @@ class TrainEngine:
         if not self.coarse_photometric and not (self.proposal > 0.0 or self.spread[0] > 0.0 or any(self.depth_loss[0])):
             raise ValueError("TrainEngine: coarse_photometric=False leaves the coarse net without any loss: give it proposal > 0 (or a "
                              "spread or depth weight on the coarse net)")
+        # RGBA targets: None -- the fourth column of a target is ignored, the step as it always was; "matte" -- each
+        # net's loss is taken over a per-ray background (`background`: "random", the default -- uniform draws keyed by the step's seed
+        # and the global ray index --, or a constant (r, g, b)), with alpha_loss * mean (acc - a)^2 on top; "weight" -- alpha weights
+        # every pixel's squared error.  Both: opacity_entropy * mean H(acc).  One nerfhip_matte_loss_fwd_bwd per net in place of
+        # nerfhip_mse_loss_fwd_bwd; its g_acc enters the net's backward as the cotangent of the accumulated opacity
+        self.alpha, self.background, self.alpha_loss, self.opacity_entropy = self._parse_alpha(
+            alpha, background, alpha_loss, opacity_entropy, bool(white_background), self.mf is not None)
         self._stats = BM.StatsReader(("coarse", "fine"))
         self._zero_frac = self._stats.frac   # last known fraction of all-zero d(loss)/d(raw) rows per net (updated in place)
         # steps run dense / compacted / recomputed / fused / fused over the list / fused over the stash, per net ("auto")
@@ -207,6 +220,56 @@ class TrainEngine:
         if any(len(pair) != 2 or not all(v >= 0.0 and math.isfinite(v) for v in pair) for pair in d):
             raise bad
         return (d[0], d[1] if has_fine else (0.0, 0.0))
+
+    @staticmethod
+    def _parse_alpha(alpha, background, alpha_loss, opacity_entropy, white_background, has_fine):
+        """-> (mode or None, None / "random" / (r, g, b), (alpha_loss coarse, fine), (opacity_entropy coarse, fine))."""
+        if alpha not in (None, "matte", "weight"):
+            raise ValueError("TrainEngine: alpha must be None, 'matte' or 'weight' (got %r)" % (alpha,))
+
+        def pair(name, v):
+            if v is None:
+                return (0.0, 0.0)
+            bad = ValueError("TrainEngine: %s must be a finite weight >= 0 or a pair (coarse, fine) of them (got %r)" % (name, v))
+            if isinstance(v, bool):
+                raise bad
+            try:
+                v = (float(v), float(v)) if isinstance(v, (int, float)) else tuple(float(x) for x in v)
+            except (TypeError, ValueError):
+                raise bad from None
+            if len(v) != 2 or not all(x >= 0.0 and math.isfinite(x) for x in v):
+                raise bad
+            return v
+
+        lam_a, lam_h = pair("alpha_loss", alpha_loss), pair("opacity_entropy", opacity_entropy)
+        if alpha is None:   # (the parsed weights decide: 0, 0.0, (0, 0) and [0.0, 0.0] all ask for nothing)
+            for name, given, asks in (("alpha_loss", alpha_loss, any(lam_a)), ("opacity_entropy", opacity_entropy, any(lam_h)),
+                                      ("background", background, background is not None)):
+                if asks:
+                    raise ValueError("TrainEngine: %s=%r needs alpha='matte' or alpha='weight'" % (name, given))
+            return None, None, (0.0, 0.0), (0.0, 0.0)
+        if not has_fine:
+            lam_a, lam_h = (lam_a[0], 0.0), (lam_h[0], 0.0)
+        if alpha == "weight":
+            if any(lam_a):
+                raise ValueError("TrainEngine: alpha_loss=%r with alpha='weight': alpha is a per-pixel loss weight there, not an "
+                                 "opacity (alpha_loss belongs to alpha='matte')" % (alpha_loss,))
+            if background is not None:
+                raise ValueError("TrainEngine: background=%r with alpha='weight': the weighted loss reads no background" % (background,))
+            return alpha, None, lam_a, lam_h
+        if white_background:
+            raise ValueError("TrainEngine: alpha='matte' with white_background=True would composite twice (the render onto white, the "
+                             "loss onto its background): use white_background=False and background=(1, 1, 1)")
+        if background is None:
+            background = "random"
+        if not (isinstance(background, str) and background == "random"):
+            try:
+                background = tuple(float(x) for x in background)
+            except (TypeError, ValueError):
+                background = ()
+            if len(background) != 3 or not all(math.isfinite(x) for x in background):
+                raise ValueError("TrainEngine: background must be 'random' or three finite floats (r, g, b)")
+        return alpha, background, lam_a, lam_h
 
     def window_alphas(self, step):
         """(alpha_xyz, alpha_dir) of the schedule at step `step` (None without one)."""
@@ -249,6 +312,8 @@ class TrainEngine:
             self._occ_tmp = torch.zeros(self._occ_tb // 4 + 64, dtype=torch.int32, device=self.dev)
         self._bufs = dict(rgb_c=mk(n, 3), rgb_f=mk(n, 3), g_c=mk(n, 3), g_f=mk(n, 3), disp_c=mk(n), acc_c=mk(n),
                           disp_f=mk(n), acc_f=mk(n))
+        if self.alpha is not None:   # (the cotangents of the accumulated opacity: what the matte kernel writes)
+            self._bufs.update(ga_c=mk(n), ga_f=mk(n))
         if any(self.spread):   # (what the spread kernel writes)
             S = (self.cfg.num_coarse, self.cfg.num_coarse + self.cfg.num_fine)
             self._spread_bufs = {fine: (mk(n, S[fine]), torch.zeros(n, dtype=torch.float32, device=self.dev))
@@ -366,6 +431,13 @@ class TrainEngine:
         select_training_rays_views returned).  Needs TrainEngine(depth_loss=...); refused on a frozen step."""
         self._check_inputs(rays, target)
         dp = None if depth_prior is None else self._check_depth_prior(depth_prior, rays.shape[0], frozen)
+        if self.alpha is not None:
+            if target.shape[1] < 4:
+                raise ValueError("TrainEngine: alpha=%r needs targets of 4 columns (r, g, b, alpha); got shape %s"
+                                 % (self.alpha, tuple(target.shape)))
+            if exposure is not None:
+                raise ValueError("TrainEngine: exposure=... on an engine with alpha=%r is not covered: the loss under the exposure "
+                                 "table reads no alpha" % (self.alpha,))
         if frozen and any(self.spread):
             raise ValueError("TrainEngine: a frozen step (localize_*, the exposure fit) with spread > 0 makes no sense: the spread loss "
                              "regularises the nets, and a frozen step updates none")
@@ -419,8 +491,13 @@ class TrainEngine:
         gf = self.grad[self.nc_params:] if nf > 0 else None
         tstride = target.stride(0)
         # (coarse_photometric=False: the coarse backward gets no colour cotangent -- a frozen step's ray gradient keeps it)
-        cot_c = (b["g_c"].data_ptr() if self.coarse_photometric or frozen else None, None, None, None, None, None)
-        cot_f = (None, None, None, b["g_f"].data_ptr() if nf > 0 else None, None, None)
+        matte = self.alpha is not None   # (then g_acc of the matte loss rides in the slot next to g_rgb, and is withheld with it)
+        with_c = self.coarse_photometric or frozen
+        cot_c = (b["g_c"].data_ptr() if with_c else None, b["ga_c"].data_ptr() if matte and with_c else None, None, None, None, None)
+        cot_f = (None, None, None, b["g_f"].data_ptr() if nf > 0 else None, b["ga_f"].data_ptr() if matte and nf > 0 else None, None)
+        if matte:
+            bg = self.background
+            matte_args = (int(self.alpha == "weight"), None, int(bg == "random")) + (bg if isinstance(bg, tuple) else (0.0, 0.0, 0.0))
         rand = None
         if draws is not None:
             shapes = ((n, self.cfg.num_coarse), (n, self.cfg.num_coarse), (n, nf), (n, self.cfg.num_coarse + nf))
@@ -444,7 +521,7 @@ class TrainEngine:
             pc_flat = self.mc._theta_eff(refresh=False).data_ptr()
             pf_flat = self.mf._theta_eff(refresh=False).data_ptr() if nf > 0 else None
 
-        def net_pass(part, rgb, g_rgb, cot, loss, grad, model, tmp, g_rays, stream):
+        def net_pass(part, rgb, acc, g_rgb, g_acc, cot, loss, grad, model, tmp, g_rays, stream):
             """One net's loss, then its backward in the step's form, then its window gradients (behind its backward, ahead of its
             all-reduce), on `stream`.  With a spread weight: the spread kernel between the loss and the backward, and the backward's
             _w form."""
@@ -468,7 +545,11 @@ class TrainEngine:
                 # Reads the fine pass's raw rows and depths: `stream` is behind the fine forward, and the fine backward only reads them)
                 call.proposal(self.proposal * gscale / n, None, pl.data_ptr(), gw.data_ptr(), g_weights is not None, stream)
                 g_weights = (gw.data_ptr(), None)
-            if exposure is None:
+            if matte:   # (loss = {photometric, alpha, entropy} of this net; the background draws are the step's: seed, global ray index)
+                lib.matte_loss_fwd_bwd(rgb.data_ptr(), acc.data_ptr(), target.data_ptr(), tstride, n, *matte_args, seed, ray_offset,
+                                       self.alpha_loss[fine], self.opacity_entropy[fine], gscale, g_rgb.data_ptr(), g_acc.data_ptr(),
+                                       loss.data_ptr(), stream)
+            elif exposure is None:
                 lib.mse_loss_fwd_bwd(rgb.data_ptr(), None, target.data_ptr(), tstride, n, gscale, g_rgb.data_ptr(), None, loss.data_ptr(), stream)
             else:
                 lib.mse_loss_views_fwd_bwd(rgb.data_ptr(), None, target.data_ptr(), tstride, n, gscale, ex_inds.data_ptr(), ex_hw,
@@ -486,8 +567,8 @@ class TrainEngine:
             grid = self.occupancy._struct()
             occ = (grid, grid, self._occ_tmp.data_ptr(), self._occ_tb)
         fwd = lambda part, stream: call.forward(out, part, stream, occ)  # noqa: E731
-        coarse = (L.PART_COARSE, b["rgb_c"], b["g_c"], cot_c, self._loss_c, gc, self.mc, tmp_c, g_rays_c)
-        fine = (L.PART_FINE, b["rgb_f"], b["g_f"], cot_f, self._loss_f, gf, self.mf, tmp_f, ray_grad)
+        coarse = (L.PART_COARSE, b["rgb_c"], b["acc_c"], b["g_c"], b.get("ga_c"), cot_c, self._loss_c, gc, self.mc, tmp_c, g_rays_c)
+        fine = (L.PART_FINE, b["rgb_f"], b["acc_f"], b["g_f"], b.get("ga_f"), cot_f, self._loss_f, gf, self.mf, tmp_f, ray_grad)
         self._pending = []
         self._depth_keep, self._depth_ran = dp, dp is not None
         with torch.cuda.device(self.dev):
@@ -522,6 +603,9 @@ class TrainEngine:
                 self._pending.append(allreduce_gradients(gc, self.pg, async_op=True, single_rank=True))
             if nf > 0:
                 torch.stack((self._loss_c[0], self._loss_f[0], self._loss_c[0] + self._loss_f[0]), out=self.loss)
+            elif matte:   # (the coarse net's words are {photometric, alpha, entropy})
+                self.loss.zero_()
+                self.loss[0::2] = self._loss_c[0]   # ({photometric_c, 0, sum}: no fine net, as the plain loss launch writes it)
             else:
                 self.loss.copy_(self._loss_c)
             if self.backward == "auto" and not frozen:   # ({kept, total} of every net that ran over a list in the step just issued)
@@ -575,6 +659,14 @@ class TrainEngine:
         the first step."""
         b = self._spread_bufs or {}
         return tuple(b[fine][1].mean() if fine in b else None for fine in (0, 1))
+
+    @property
+    def matte_losses(self):
+        """(coarse, fine): each net's device tensor [3] = {photometric, alpha, entropy} of the last step (unscaled means, as
+        nerfhip_matte_loss_fwd_bwd wrote them; no host synchronisation); fine is None without a fine net.  None without alpha=..."""
+        if self.alpha is None:
+            return None
+        return (self._loss_c, self._loss_f if self.mf is not None else None)
 
     @property
     def proposal_loss(self):

@@ -805,6 +805,75 @@ def exposure_mse_loss(rgb_coarse, rgb_fine, target, inds, hw, table):
     return _ExposureLoss.apply(rgb_coarse, rgb_fine, target, inds, hw, table)
 
 
+class _MatteLoss(torch.autograd.Function):
+    """matte_mse_loss as ONE node: the forward is the launch of nerfhip_matte_loss_fwd_bwd (which also leaves g_rgb and g_acc of the
+    weighted total), the backward hands those out scaled by the incoming cotangent."""
+
+    @staticmethod
+    def forward(ctx, rgb, acc, target, mode, bg, lam_alpha, lam_entropy, seed, ray_offset):
+        lib = L.get_lib()
+        n = rgb.shape[0]
+        r = rgb.detach().float().contiguous()
+        a = acc.detach().float().reshape(n).contiguous()
+        tgt = target.detach().float()
+        if tgt.dim() != 2 or tgt.shape[1] < 4 or tgt.stride(1) != 1:
+            tgt = tgt.reshape(n, -1).contiguous()
+        if tgt.shape[1] < 4:
+            raise ValueError("matte_mse_loss: target_rgba must hold rows of 4 floats (r, g, b, alpha) (got shape %s)" % (tuple(target.shape),))
+        rows = None   # (a per-ray background)
+        if isinstance(bg, torch.Tensor):
+            rows = bg.detach().float().reshape(n, 3).contiguous()
+        const = bg if isinstance(bg, tuple) else (0.0, 0.0, 0.0)
+        mk = lambda *shape: torch.empty(shape, dtype=torch.float32, device=r.device)  # noqa: E731
+        g_rgb, g_acc, loss = mk(n, 3), mk(n), mk(3)
+        with L.launch_on(r, a, tgt, rows, g_rgb, g_acc, loss) as st:
+            lib.matte_loss_fwd_bwd(r.data_ptr(), a.data_ptr(), tgt.data_ptr(), tgt.stride(0), n, mode, None if rows is None else rows.data_ptr(),
+                                   int(isinstance(bg, str)), *const, int(seed) & 0xFFFFFFFFFFFFFFFF, int(ray_offset), lam_alpha, lam_entropy,
+                                   1.0, g_rgb.data_ptr(), g_acc.data_ptr(), loss.data_ptr(), st)
+        ctx.keep = (g_rgb, g_acc)
+        ctx.meta = (rgb.dtype, acc.dtype, tuple(acc.shape))
+        total = loss[0].clone()   # (no view of `parts`: an output of its own)
+        if lam_alpha != 0.0:
+            total = total + lam_alpha * loss[1]
+        if lam_entropy != 0.0:
+            total = total + lam_entropy * loss[2]
+        ctx.mark_non_differentiable(loss)
+        return total, loss
+
+    @staticmethod
+    def backward(ctx, g_total, _g_parts):
+        g_rgb, g_acc = ctx.keep
+        dt_r, dt_a, acc_shape = ctx.meta
+        need = ctx.needs_input_grad
+        return ((g_rgb * g_total).to(dt_r) if need[0] else None, (g_acc * g_total).reshape(acc_shape).to(dt_a) if need[1] else None,
+                None, None, None, None, None, None, None)
+
+
+def matte_mse_loss(rgb, acc, target_rgba, mode="matte", background="random", alpha_loss=0.0, opacity_entropy=0.0, seed=0, ray_offset=0):
+    """(total, parts): the loss of ONE net's rgb (n, 3) and accumulated opacity acc (n) -- the rgb_* / acc_* outputs of
+    run_one_iter_of_nerf -- against RGBA targets (n, >= 4; straight alpha), in place of one mse_loss line of the reference's loop
+    (train_nerf.py:244-258); one call per net.  mode "matte": the squared error of rgb + (1 - acc) * b against a * C + (1 - a) * b
+    over a per-ray background b -- background="random" (uniform draws keyed by seed and ray_offset + ray index), a constant
+    (r, g, b), or an (n, 3) tensor -- plus alpha_loss * mean (acc - a)^2; mode "weight": alpha weights every pixel's squared error
+    (a mask: 0 = ignore; background and alpha_loss do not apply).  Both: plus opacity_entropy * mean H(acc), the binary entropy.
+    total is differentiable w.r.t. rgb and acc: one autograd node, one launch (nerfhip_matte_loss_fwd_bwd) in the forward, whose
+    cotangents the backward hands out times the incoming cotangent; parts is the detached device tensor [3] = {photometric, alpha,
+    entropy}, unscaled means."""
+    if mode not in ("matte", "weight"):
+        raise ValueError("matte_mse_loss: mode must be 'matte' or 'weight' (got %r)" % (mode,))
+    if mode == "weight":
+        if alpha_loss != 0.0:
+            raise ValueError("matte_mse_loss: alpha_loss=%r with mode='weight': alpha is a per-pixel loss weight there, not an opacity"
+                             % (alpha_loss,))
+        background = (0.0, 0.0, 0.0)   # (not read)
+    elif not isinstance(background, torch.Tensor) and background != "random":
+        background = tuple(float(v) for v in background)
+        if len(background) != 3:
+            raise ValueError("matte_mse_loss: background must be 'random', three floats (r, g, b) or an (n, 3) tensor")
+    return _MatteLoss.apply(rgb, acc, target_rgba, int(mode == "weight"), background, float(alpha_loss), float(opacity_entropy), seed,
+                            ray_offset)
+
+
 def select_cached_training_rays(cache_dict, num_random_rays, options, select_inds=None, seed=0, step=0, first=0):
     """The cached branch (train_nerf.py:175-194): rows of cache_dict["ray_bundle"] (2, ., 3) and of
     cache_dict["target"][..., :3], both already on the device."""
