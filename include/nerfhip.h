@@ -666,6 +666,37 @@ int nerfhip_matte_loss_fwd_bwd(const float* rgb, const float* acc, const float* 
                                int mode, const float* bg, int bg_random, float bg_r, float bg_g, float bg_b,
                                uint64_t seed, uint64_t ray_offset, float lam_alpha, float lam_entropy, float grad_scale,
                                float* g_rgb, float* g_acc, float* loss_out, nerfhip_stream_t stream);
+/* The photometric loss of ONE compositing pass under a robust kind, with an optional trim of the call's largest per-ray residuals
+ * (one call per net), and its cotangent g_rgb for the fused backward.  rgb: dev [n,3]; target: dev rows of target_stride >= 3 floats.
+ * d = rgb_c - t_c, formed in fp32 as nerfhip_mse_loss_fwd_bwd forms it.  rho is formed in fp64 from the fp32 d.  h = psi / 2 is rounded
+ * to fp32 once.
+ *   kind 0, l2:          rho = d^2;                                                    h = d;                          param ignored
+ *   kind 1, l1:          rho = |d|;                                                    h = 0.5 sign(d) (0 at 0);       param ignored
+ *   kind 2, huber:       rho = d^2 if |d| <= delta, else delta (2 |d| - delta);        h = d, else delta sign(d);      param = delta > 0
+ *   kind 3, charbonnier: rho = sqrt(d^2 + eps^2) - eps;                                h = 0.5 d / sqrt(d^2 + eps^2);  param = eps > 0
+ *   kind 4, relative:    rho = d^2 / (p + eps)^2, p = rgb_c held constant (RawNeRF);   h = d / (p + eps)^2;            param = eps > 0
+ * The Huber form continues l2 beyond delta, so that delta -> inf recovers the plain loss and a learning rate carries over.
+ * Cotangent and loss: k = 2 / (3 n) * grad_scale, formed as nerfhip_mse_loss_fwd_bwd forms it; g_rgb_c = (h k) m_r;
+ *   loss = sum_r m_r sum_c rho / (3 n).  The divisor stays 3 n whatever is trimmed (as the matte loss's weight mode: the ranks of a
+ *   data-parallel step agree on the scale).
+ * Trimming (keep < 1): e_r = (float) sum_c rho(d_c) is the per-ray residual, non-negative.  kk = min(n, max(1, ceil((double)keep * n))).
+ *   tau is the kk-th smallest e_r of the call.  m_r = !(e_r > tau): ties at tau are all kept.  A NaN residual is never trimmed (it
+ *   sorts behind +inf): its ray stays, and the loss becomes NaN, so divergence remains visible.  tau and the mask are constants of the
+ *   step: no gradient flows through them; a trimmed ray's g_rgb row is +0.  keep == 1 runs no selection, reports tau = +inf and
+ *   kept = 1, and needs no tmp.
+ * loss_out: dev float[3] = {loss, kept fraction = (float)(sum_r m_r / n), tau}.  g_rgb: dev [n,3]; resid_out: dev [n] floats (e_r);
+ * mask_out: dev [n] bytes (m_r); each of the three may be NULL.  tmp: dev, nerfhip_robust_loss_tmp_bytes(n) bytes, aligned to 4.
+ * One workgroup, fp64 sums in a fixed order, integer counts, no atomics: the results do not depend on scheduling.  Kind 0 with
+ * keep == 1 gives nerfhip_mse_loss_fwd_bwd(rgb, NULL, ...)'s loss_out[0] and g_rgb bit for bit (the same element-to-thread
+ * assignment, wave sums, block sums and final division), and so does kind 2 with a delta beyond every |d|.
+ * Refused (NERFHIP_ERR_ARG, nothing launched): n <= 0 or n >= 2^31; target_stride < 3; a NULL rgb, target or loss_out; a kind outside
+ * 0..4; a non-positive or non-finite param where the kind reads it; keep outside (0, 1] or NaN; keep < 1 with tmp NULL, misaligned or
+ * smaller than nerfhip_robust_loss_tmp_bytes(n). */
+int64_t nerfhip_robust_loss_tmp_bytes(int64_t n);
+int nerfhip_robust_loss_fwd_bwd(const float* rgb, const float* target, int target_stride, int64_t n,
+                                int kind, float param, float keep, float grad_scale,
+                                float* g_rgb, float* resid_out, unsigned char* mask_out, float* loss_out,
+                                void* tmp, int64_t tmp_bytes, nerfhip_stream_t stream);
 /* torch.optim.Adam single-tensor step (no amsgrad, no weight decay) on a flat vector; step counts from 1. */
 int nerfhip_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
                       float beta1, float beta2, float eps, int64_t step, float grad_scale, nerfhip_stream_t stream);

@@ -20,7 +20,7 @@ from .nerf_helpers import (cumprod_exclusive, get_embedding_function, get_miniba
 from .eval_utils import ImageWriter, cast_to_disparity_image, cast_to_image, render_pose_rows  # noqa: F401
 from .io_utils import load_cached_example, load_checkpoint, save_cached_example, save_checkpoint  # noqa: F401
 from .train_utils import (exposure_mse_loss, matte_mse_loss, pack_rays, predict_and_render_radiance, run_network, run_one_iter_of_nerf,  # noqa: F401
-                          select_cached_training_rays, select_training_rays, select_training_rays_views,
+                          robust_mse_loss, select_cached_training_rays, select_training_rays, select_training_rays_views,
                           select_training_rays_views_bwd)
 from .volume_rendering_utils import volume_render_radiance_field  # noqa: F401
 

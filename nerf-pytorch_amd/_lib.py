@@ -176,6 +176,9 @@ _PROTOS = {
     "nerfhip_mse_loss_fwd_bwd": (C.c_int, [c_f, c_f, c_f, C.c_int, c_i64, C.c_float, c_f, c_f, c_f, c_f]),
     "nerfhip_matte_loss_fwd_bwd": (C.c_int, [c_f, c_f, c_f, C.c_int, c_i64, C.c_int, c_f, C.c_int, C.c_float, C.c_float, C.c_float, c_u64,
                                              c_u64, C.c_float, C.c_float, C.c_float, c_f, c_f, c_f, c_f]),
+    "nerfhip_robust_loss_tmp_bytes": (c_i64, [c_i64]),
+    "nerfhip_robust_loss_fwd_bwd": (C.c_int, [c_f, c_f, C.c_int, c_i64, C.c_int, C.c_float, C.c_float, C.c_float, c_f, c_f, c_f, c_f, c_f,
+                                              c_i64, c_f]),
     "nerfhip_adam_step": (C.c_int, [c_f, c_f, c_f, c_f, c_i64, C.c_float, C.c_float, C.c_float, C.c_float, c_i64,
                                      C.c_float, c_f]),
     "nerfhip_select_indices": (C.c_int, [c_u64, c_u64, c_i64, c_i64, c_i64, c_f, c_f]),

@@ -39,6 +39,12 @@ RGBA targets (`alpha=`, `background=`, `alpha_loss=`, `opacity_e
 loss launch is nerfhip_matte_loss_fwd_bwd in place of nerfhip_mse_loss_fwd_bwd, on the same stream, and the g_acc it writes enters the
 net's backward as the cotangent of the accumulated opacity, next to g_rgb (withheld with it under coarse_photometric=False);
 `matte_losses` reads each net's {photometric, alpha, entropy}.  Without `alpha=` the fourth column of a target is ignored, as ever.
+
+Robust photometric losses (`photometric=`, `trim=`): with either set each net's loss launch is
+nerfhip_robust_loss_fwd_bwd in place of nerfhip_mse_loss_fwd_bwd, on the same stream, with the same grad_scale, into the same g_rgb
+buffer and loss words; everything behind the launch is untouched.  Each net trims on its own residuals (no new wait between the
+streams), and in a data-parallel step each rank trims its own shard: tau is a quantile of the rank's rays, not of the global batch.
+`loss` holds the robust means, `robust_stats` each net's {kept fraction, tau}.  Without the keywords: the same launches, the same bits.
 """
 import math
 
@@ -59,7 +65,7 @@ class TrainEngine:
                  noise_std=0.0, lr=5e-3, betas=(0.9, 0.999), eps=1e-8, seed=0, process_group=None, world_size=None,
                  rank=None, overlap=None, always_reduce=False, backward=None, window=None, total_steps=None, occupancy=None,
                  occupancy_warmup=256, occupancy_every=16, spread=None, depth_loss=None, proposal=None, coarse_photometric=True,
-                 alpha=None, background=None, alpha_loss=None, opacity_entropy=None):
+                 alpha=None, background=None, alpha_loss=None, opacity_entropy=None, photometric=None, trim=None):
         self.lib = L.get_lib()
         self.mc, self.mf = model_coarse, model_fine if num_fine > 0 else None
         self.dev = model_coarse.flat_params.device
@@ -182,6 +188,15 @@ class TrainEngine:
         # nerfhip_mse_loss_fwd_bwd; its g_acc enters the net's backward as the cotangent of the accumulated opacity
         self.alpha, self.background, self.alpha_loss, self.opacity_entropy = self._parse_alpha(
             alpha, background, alpha_loss, opacity_entropy, bool(white_background), self.mf is not None)
+        # robust photometric losses: None -- the plain squared error, the step as it always was; `photometric`: "l1",
+        # ("huber", delta), ("charbonnier", eps) or ("relative", eps); `trim`: the fraction of the batch's rays that is kept, by per-ray
+        # residual (the others get a zero cotangent row); each may be a pair (coarse, fine).  When either is set, each net's loss launch
+        # is nerfhip_robust_loss_fwd_bwd in place of nerfhip_mse_loss_fwd_bwd, on the same stream, into the same g_rgb and loss words;
+        # each net trims on its own residuals, and in a data-parallel step each rank trims its own shard
+        self.robust = self._parse_robust(photometric, trim, self.mf is not None)
+        if self.robust is not None and self.alpha is not None:
+            raise ValueError("TrainEngine: %s=... together with alpha=%r is not covered: the matte loss carries its own kernel"
+                             % ("photometric" if photometric is not None else "trim", self.alpha))
         self._stats = BM.StatsReader(("coarse", "fine"))
         self._zero_frac = self._stats.frac   # last known fraction of all-zero d(loss)/d(raw) rows per net (updated in place)
         # steps run dense / compacted / recomputed / fused / fused over the list / fused over the stash, per net ("auto")
@@ -271,6 +286,56 @@ class TrainEngine:
                 raise ValueError("TrainEngine: background must be 'random' or three finite floats (r, g, b)")
         return alpha, background, lam_a, lam_h
 
+    ROBUST_KINDS = {"l2": 0, "l1": 1, "huber": 2, "charbonnier": 3, "relative": 4}
+
+    @classmethod
+    def _parse_robust(cls, photometric, trim, has_fine):
+        """-> None (neither keyword asks for anything), or ((kind, param, keep) of the coarse net, of the fine net)."""
+        def number(v):
+            return isinstance(v, (int, float)) and not isinstance(v, bool)
+
+        def spec(v):
+            """One net's `photometric` -> (kind, param)."""
+            bad = ValueError("TrainEngine: photometric must be None, 'l1', ('huber', delta), ('charbonnier', eps) or ('relative', eps) "
+                             "with a finite parameter > 0, or a pair (coarse, fine) of those (got %r)" % (photometric,))
+            if v is None:
+                return (0, 0.0)
+            name, param = (v, None) if isinstance(v, str) else (tuple(v) if isinstance(v, (tuple, list)) and len(v) == 2 else (None, None))
+            if not isinstance(name, str):
+                raise bad
+            if name not in cls.ROBUST_KINDS:
+                raise ValueError("TrainEngine: photometric: unknown kind %r (one of %s)" % (name, ", ".join(sorted(cls.ROBUST_KINDS))))
+            kind = cls.ROBUST_KINDS[name]
+            if kind < 2:
+                if param is not None:
+                    raise bad
+                return (kind, 0.0)
+            if not number(param) or not (param > 0.0 and math.isfinite(param)):
+                raise ValueError("TrainEngine: photometric=(%r, %r): the parameter must be a finite number > 0" % (name, param))
+            return (kind, float(param))
+
+        def keep_of(v):
+            if v is None:
+                return 1.0
+            if not number(v) or not (0.0 < v <= 1.0):
+                raise ValueError("TrainEngine: trim must be None, a kept fraction in (0, 1] or a pair (coarse, fine) of those (got %r)"
+                                 % (trim,))
+            return float(v)
+
+        one = photometric is None or isinstance(photometric, str) or (
+            isinstance(photometric, (tuple, list)) and len(photometric) == 2 and isinstance(photometric[0], str) and number(photometric[1]))
+        if not one and not (isinstance(photometric, (tuple, list)) and len(photometric) == 2):
+            spec(photometric)   # (raises)
+        kinds = (spec(photometric),) * 2 if one else tuple(spec(v) for v in photometric)
+        if trim is not None and not number(trim) and not (isinstance(trim, (tuple, list)) and len(trim) == 2):
+            keep_of(trim)   # (raises)
+        keeps = (keep_of(trim),) * 2 if trim is None or number(trim) else tuple(keep_of(v) for v in trim)
+        if not has_fine:
+            kinds, keeps = (kinds[0], (0, 0.0)), (keeps[0], 1.0)
+        if all(k == (0, 0.0) for k in kinds) and all(k == 1.0 for k in keeps):
+            return None
+        return tuple(k + (kp,) for k, kp in zip(kinds, keeps))
+
     def window_alphas(self, step):
         """(alpha_xyz, alpha_dir) of the schedule at step `step` (None without one)."""
         if self.window is None:
@@ -314,6 +379,9 @@ class TrainEngine:
                           disp_f=mk(n), acc_f=mk(n))
         if self.alpha is not None:   # (the cotangents of the accumulated opacity: what the matte kernel writes)
             self._bufs.update(ga_c=mk(n), ga_f=mk(n))
+        if self.robust is not None:   # (a trimming net's per-ray residuals: the selection's keys; one per net -- two streams)
+            words = self.lib.robust_loss_tmp_bytes(n) // 4
+            self._bufs.update({"rt_" + tag: mk(words) for tag, (_, _, keep) in zip("cf", self.robust) if keep < 1.0})
         if any(self.spread):   # (what the spread kernel writes)
             S = (self.cfg.num_coarse, self.cfg.num_coarse + self.cfg.num_fine)
             self._spread_bufs = {fine: (mk(n, S[fine]), torch.zeros(n, dtype=torch.float32, device=self.dev))
@@ -438,6 +506,9 @@ class TrainEngine:
             if exposure is not None:
                 raise ValueError("TrainEngine: exposure=... on an engine with alpha=%r is not covered: the loss under the exposure "
                                  "table reads no alpha" % (self.alpha,))
+        if self.robust is not None and exposure is not None:
+            raise ValueError("TrainEngine: exposure=... on an engine with photometric=... or trim=... is not covered: the loss under the "
+                             "exposure table carries its own kernel")
         if frozen and any(self.spread):
             raise ValueError("TrainEngine: a frozen step (localize_*, the exposure fit) with spread > 0 makes no sense: the spread loss "
                              "regularises the nets, and a frozen step updates none")
@@ -492,6 +563,7 @@ class TrainEngine:
         tstride = target.stride(0)
         # (coarse_photometric=False: the coarse backward gets no colour cotangent -- a frozen step's ray gradient keeps it)
         matte = self.alpha is not None   # (then g_acc of the matte loss rides in the slot next to g_rgb, and is withheld with it)
+        robust = self.robust is not None
         with_c = self.coarse_photometric or frozen
         cot_c = (b["g_c"].data_ptr() if with_c else None, b["ga_c"].data_ptr() if matte and with_c else None, None, None, None, None)
         cot_f = (None, None, None, b["g_f"].data_ptr() if nf > 0 else None, b["ga_f"].data_ptr() if matte and nf > 0 else None, None)
@@ -549,6 +621,12 @@ class TrainEngine:
                 lib.matte_loss_fwd_bwd(rgb.data_ptr(), acc.data_ptr(), target.data_ptr(), tstride, n, *matte_args, seed, ray_offset,
                                        self.alpha_loss[fine], self.opacity_entropy[fine], gscale, g_rgb.data_ptr(), g_acc.data_ptr(),
                                        loss.data_ptr(), stream)
+            elif robust:   # (loss = {robust mean, kept fraction, tau} of this net; the net trims on its own residuals)
+                kind, param, keep = self.robust[fine]
+                rt = b.get("rt_f" if fine else "rt_c")
+                lib.robust_loss_fwd_bwd(rgb.data_ptr(), target.data_ptr(), tstride, n, kind, param, keep, gscale, g_rgb.data_ptr(), None,
+                                        None, loss.data_ptr(), None if rt is None else rt.data_ptr(), 0 if rt is None else 4 * rt.numel(),
+                                        stream)
             elif exposure is None:
                 lib.mse_loss_fwd_bwd(rgb.data_ptr(), None, target.data_ptr(), tstride, n, gscale, g_rgb.data_ptr(), None, loss.data_ptr(), stream)
             else:
@@ -603,7 +681,7 @@ class TrainEngine:
                 self._pending.append(allreduce_gradients(gc, self.pg, async_op=True, single_rank=True))
             if nf > 0:
                 torch.stack((self._loss_c[0], self._loss_f[0], self._loss_c[0] + self._loss_f[0]), out=self.loss)
-            elif matte:   # (the coarse net's words are {photometric, alpha, entropy})
+            elif matte or robust:   # (the coarse net's words are {photometric, alpha, entropy} / {loss, kept fraction, tau})
                 self.loss.zero_()
                 self.loss[0::2] = self._loss_c[0]   # ({photometric_c, 0, sum}: no fine net, as the plain loss launch writes it)
             else:
@@ -667,6 +745,15 @@ class TrainEngine:
         if self.alpha is None:
             return None
         return (self._loss_c, self._loss_f if self.mf is not None else None)
+
+    @property
+    def robust_stats(self):
+        """(coarse, fine): each net's device tensor [2] = {kept fraction, tau} of the last step's robust loss launch (views of the words
+        nerfhip_robust_loss_fwd_bwd wrote; no host synchronisation; a net that does not trim reports {1, +inf}); fine is None without a
+        fine net.  None without photometric= / trim=."""
+        if self.robust is None:
+            return None
+        return (self._loss_c[1:3], self._loss_f[1:3] if self.mf is not None else None)
 
     @property
     def proposal_loss(self):

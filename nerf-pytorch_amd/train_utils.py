@@ -15,6 +15,7 @@ reshape honour `mode`.
 """
 import contextlib
 import ctypes as C
+import math
 
 import torch
 
@@ -872,6 +873,59 @@ def matte_mse_loss(rgb, acc, target_rgba, mode="matte", background="random", alp
             raise ValueError("matte_mse_loss: background must be 'random', three floats (r, g, b) or an (n, 3) tensor")
     return _MatteLoss.apply(rgb, acc, target_rgba, int(mode == "weight"), background, float(alpha_loss), float(opacity_entropy), seed,
                             ray_offset)
+
+
+ROBUST_KINDS = {"l2": 0, "l1": 1, "huber": 2, "charbonnier": 3, "relative": 4}
+
+
+class _RobustLoss(torch.autograd.Function):
+    """robust_mse_loss as ONE node: the forward is the launch of nerfhip_robust_loss_fwd_bwd (which also leaves g_rgb), the backward
+    hands that out scaled by the incoming cotangent."""
+
+    @staticmethod
+    def forward(ctx, rgb, target, kind, param, keep):
+        lib = L.get_lib()
+        n = rgb.shape[0]
+        r = rgb.detach().float().contiguous()
+        tgt = target.detach().float()
+        if tgt.dim() != 2 or tgt.shape[1] < 3 or tgt.stride(1) != 1:
+            tgt = tgt.reshape(n, -1).contiguous()
+        if tgt.shape[1] < 3:
+            raise ValueError("robust_mse_loss: target must hold rows of at least 3 floats (got shape %s)" % (tuple(target.shape),))
+        mk = lambda *shape: torch.empty(shape, dtype=torch.float32, device=r.device)  # noqa: E731
+        g_rgb, words = mk(n, 3), mk(3)
+        tmp = mk(lib.robust_loss_tmp_bytes(n) // 4) if keep < 1.0 else None
+        with L.launch_on(r, tgt, g_rgb, words, tmp) as st:
+            lib.robust_loss_fwd_bwd(r.data_ptr(), tgt.data_ptr(), tgt.stride(0), n, kind, param, keep, 1.0, g_rgb.data_ptr(), None, None,
+                                    words.data_ptr(), None if tmp is None else tmp.data_ptr(), 0 if tmp is None else 4 * tmp.numel(), st)
+        ctx.keep = g_rgb
+        ctx.meta = rgb.dtype
+        loss, kept, tau = words[0].clone(), words[1].clone(), words[2].clone()   # (no views of `words`: outputs of their own)
+        ctx.mark_non_differentiable(kept, tau)
+        return loss, kept, tau
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_kept, _g_tau):
+        return (ctx.keep * g_loss).to(ctx.meta) if ctx.needs_input_grad[0] else None, None, None, None, None
+
+
+def robust_mse_loss(rgb, target, kind="huber", param=0.1, trim=None):
+    """(loss, (kept, tau)): the robust photometric loss of ONE net's rgb (n, 3) against target (n, >= 3), in place of one mse_loss line
+    of the reference's loop (train_nerf.py:244-258); one call per net.  kind: "l2", "l1", "huber" (param = delta), "charbonnier"
+    (param = eps) or "relative" (RawNeRF's (p - t) / (sg(p) + eps), param = eps) -- the definition is nerfhip_robust_loss_fwd_bwd's
+    (include/nerfhip.h); trim: None, or the fraction of the rays that is kept by per-ray residual (the others get a zero gradient row;
+    the divisor stays 3 n).  loss is differentiable w.r.t. rgb: one autograd node, one launch in the forward, whose cotangent the
+    backward hands out times the incoming cotangent; kept (the kept fraction) and tau (the residual at the cut; +inf without a trim) are
+    detached device scalars."""
+    if kind not in ROBUST_KINDS:
+        raise ValueError("robust_mse_loss: unknown kind %r (one of %s)" % (kind, ", ".join(sorted(ROBUST_KINDS))))
+    k = ROBUST_KINDS[kind]
+    if k >= 2 and not (isinstance(param, (int, float)) and not isinstance(param, bool) and param > 0.0 and math.isfinite(param)):
+        raise ValueError("robust_mse_loss: param=%r: kind %r needs a finite parameter > 0" % (param, kind))
+    if trim is not None and not (isinstance(trim, (int, float)) and not isinstance(trim, bool) and 0.0 < trim <= 1.0):
+        raise ValueError("robust_mse_loss: trim must be None or a kept fraction in (0, 1] (got %r)" % (trim,))
+    loss, kept, tau = _RobustLoss.apply(rgb, target, k, float(param) if k >= 2 else 0.0, 1.0 if trim is None else float(trim))
+    return loss, (kept, tau)
 
 
 def select_cached_training_rays(cache_dict, num_random_rays, options, select_inds=None, seed=0, step=0, first=0):
