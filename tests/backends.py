@@ -40,6 +40,7 @@ def model_cfg(num_layers=4, hidden_size=128, skip_connect_every=4, num_encoding_
 
 class Backend:
     name = "?"
+    compute_units = 0   # (overridden) what nh_compute_units() returns: the grid of the persistent kernels is min(groups, this)
 
     # -- device array plumbing (overridden) --
     def dev(self, a):
@@ -358,6 +359,7 @@ class Backend:
 
 class EmuBackend(Backend):
     name = "emu"
+    compute_units = 3   # the constant nh_compute_units() returns under NERFHIP_EMU (csrc/nh_host.h), so that the CPU suite walks the persistent loops
 
     def __init__(self):
         self.lib = L.bind(build_emu())
@@ -384,6 +386,8 @@ class GpuBackend(Backend):
         self.torch = torch
         self.lib = L.get_lib()
         assert self.lib.is_emulated() == 0
+        # (hipDeviceAttributeMultiprocessorCount of the current device: what nh_compute_units() reads, csrc/nh_host.h)
+        self.compute_units = int(torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count)
 
     def dev(self, a):
         return self.torch.from_numpy(np.ascontiguousarray(a)).cuda()

@@ -322,15 +322,28 @@ MLP_GEOMETRIES = {
 EXT_GEOMETRIES = ("L12_4x128", "L16_Ld6_8x256", "L11_novw3x64_skip1", "L12_Ld10_2x512", "Ld5_4x128_skip2")
 
 
-def case_mlp_forward(b, names=None, m=70):
+def exact_rows(params, cfg, rows, gen, margin):
+    """EXACTLY `rows` input rows for a gradient comparison: a pool of 1.3 x rows + 64 draws, `unit.mlp_bwd`'s margin filter
+    (O.mlp_relu_margin: rows whose ReLU branches round-off cannot decide), the first `rows` survivors.  The filter is per row, so a
+    prefix of the result is what a smaller request over the same pool would have kept.  The pool must suffice: never a skip."""
+    dx, dd = O.model_dims(cfg)
+    x = torch.randn(int(1.3 * rows) + 64, dx + dd, generator=gen)
+    x = x[O.mlp_relu_margin(params, x, cfg) > margin]
+    assert x.shape[0] >= rows, "the pool left %d of the %d rows asked for" % (x.shape[0], rows)
+    return x[:rows].contiguous()
+
+
+def case_mlp_forward(b, names=None, m=70, precision=0):
+    """precision: 0 (the fp32 kernels) or an fp16-piece plan, at the same bound (the stash-free forward of a training plan is its
+    inference forward)."""
     for name in names or MLP_GEOMETRIES:
         cfg = MLP_GEOMETRIES[name]
-        plan, params, flat, packed = mlp_setup(b, cfg, seed=31)
+        plan, params, flat, packed = mlp_setup(b, cfg, seed=31, precision=precision)
         dx, dd = O.model_dims(cfg)
         x = torch.randn(m, dx + dd, generator=rng(32))
         want = O.mlp_forward(params, x, cfg).numpy()
         got, _ = b.mlp_fwd(plan, packed, x.numpy())
-        close(got, want, *TL.bound("unit.mlp_fwd"), what="mlp fwd " + name)
+        close(got, want, *TL.bound("unit.mlp_fwd", ARITH_NAME[precision]), what="mlp fwd %s m=%d" % (name, m))
         b.lib.plan_destroy(plan)
 
 
@@ -386,10 +399,11 @@ def case_mlp_golden(b):
         b.lib.plan_destroy(plan)
 
 
-def case_mlp_backward(b, names=None, m=150, precision=0, g_scale=1.0, w_gain=1.0):
+def case_mlp_backward(b, names=None, m=150, precision=0, g_scale=1.0, w_gain=1.0, rows=None):
     """Teacher-forced MLP backward against the oracle's autograd, every parameter tensor.  precision: 0 (the fp32 kernels) or an
     fp16-piece training plan (F16X3_FWD: the training forward on fp16 pieces -- its stash: slots in ITS order, fp32 rows as it
-    computed them, ReLU masks in the data-gradient kernel's lane layout --, _FWD_DGRAD, _TRAIN) under the SAME margin and bound."""
+    computed them, ReLU masks in the data-gradient kernel's lane layout --, _FWD_DGRAD, _TRAIN) under the SAME margin and bound.
+    rows: the kernels see EXACTLY that many rows (exact_rows) instead of whatever the filter leaves of m."""
     mb = TL.bound("unit.mlp_bwd", ARITH_NAME[precision])
     margin, tol = mb["margin"], mb["tol"]
     for name in names or ("default4x128", "deep8x128_skip4", "fern8x128_skip3_L6", "novw4x128"):
@@ -397,19 +411,26 @@ def case_mlp_backward(b, names=None, m=150, precision=0, g_scale=1.0, w_gain=1.0
         plan, params, flat, packed = mlp_setup(b, cfg, seed=41, precision=precision, w_gain=w_gain)
         dx, dd = O.model_dims(cfg)
         gen = rng(42)
-        x = torch.randn(m, dx + dd, generator=gen)
-        go = torch.randn(m, 4, generator=gen) * g_scale  # (g_scale: cotangents as small as a 4096-ray mean's -- the fp16 chain's scaling)
-        # rows with a ReLU input within 1e-6 (relative) of zero are dropped: their branch is decided by fp32 round-off, the
-        # kernel's k-ordered sums and torch's GEMM may disagree, and ONE such unit moves the gradient by 1e-2 of max|g|
-        # (seen on MI355X and on the emulator alike: sample 136 of seed 42 for the 3x512 net, pre-activation 3.7e-9)
-        keep = O.mlp_relu_margin(params, x, cfg) > margin
-        x, go = x[keep].contiguous(), go[keep].contiguous()
-        assert x.shape[0] >= 0.9 * m, (x.shape[0], m)   # (8x256: 2,300 units per row)
+        if rows is not None:
+            x = exact_rows(params, cfg, rows, gen, margin)
+            go = torch.randn(rows, 4, generator=gen) * g_scale
+        else:
+            x = torch.randn(m, dx + dd, generator=gen)
+            go = torch.randn(m, 4, generator=gen) * g_scale  # (g_scale: cotangents as small as a 4096-ray mean's -- the fp16 chain's scaling)
+            # rows with a ReLU input within 1e-6 (relative) of zero are dropped: their branch is decided by fp32 round-off, the
+            # kernel's k-ordered sums and torch's GEMM may disagree, and ONE such unit moves the gradient by 1e-2 of max|g|
+            # (seen on MI355X and on the emulator alike: sample 136 of seed 42 for the 3x512 net, pre-activation 3.7e-9)
+            keep = O.mlp_relu_margin(params, x, cfg) > margin
+            x, go = x[keep].contiguous(), go[keep].contiguous()
+            assert x.shape[0] >= 0.9 * m, (x.shape[0], m)   # (8x256: 2,300 units per row)
         p = {k: v.clone().requires_grad_(True) for k, v in params.items()}
         (O.mlp_forward(p, x, cfg) * go).sum().backward()
         got_y, stash = b.mlp_fwd(plan, packed, x.numpy(), want_stash=True)
         gflat = b.mlp_bwd(plan, packed, go.numpy(), stash)
         grads = b.unflatten(plan, gflat)
+        if rows is not None:  # (on record: the largest error of the launch, of max|g| per tensor)
+            note("mlp_bwd_exact_rows_%s_%s" % (ARITH_NAME[precision], b.name), **{"%s rows=%d" % (name, rows): max(
+                float(np.abs(grads[k] - v.grad.numpy()).max()) / (float(np.abs(v.grad.numpy()).max()) + 1e-12) for k, v in p.items())})
         for k, v in p.items():
             ref = v.grad.numpy()
             scale = float(np.abs(ref).max()) + 1e-12
@@ -417,13 +438,34 @@ def case_mlp_backward(b, names=None, m=150, precision=0, g_scale=1.0, w_gain=1.0
         b.lib.plan_destroy(plan)
 
 
-def case_mlp_backward_compacted(b, names=None, m=300, precision=0, fractions=(0.0, 0.45, 0.85, 1.0), g_scale=1.0):
+def kept_count_patterns(rows, kept_counts, strided=(33, 129)):
+    """Masks of `rows` cotangent rows with EXACTLY k non-zero rows, for every k: the first k rows, the last k rows and, for the k in
+    `strided`, every (rows // k)-th row -- the kept count of a compacted backward on, one below and one above its 32-row tiles
+    (ceil(kept / 32)) and 128-row groups ((slots + 127) >> 7), dense at either end of the batch and gathered from all over it."""
+    out = []
+    for k in kept_counts:
+        assert 0 < k <= rows, (k, rows)
+        first, last, every = (torch.zeros(rows, dtype=torch.bool) for _ in range(3))
+        first[:k] = True
+        last[rows - k:] = True
+        out += [("kept %d, the first rows" % k, first), ("kept %d, the last rows" % k, last)]
+        if k in strided:
+            every[torch.arange(k) * (rows // k)] = True
+            out.append(("kept %d, every %d-th row" % (k, rows // k), every))
+    assert all(int(on.sum()) == int(what.split()[1].rstrip(",")) for what, on in out)
+    return out
+
+
+def case_mlp_backward_compacted(b, names=None, m=300, precision=0, fractions=(0.0, 0.45, 0.85, 1.0), g_scale=1.0, rows=None,
+                                kept_counts=()):
     """The compacted backward (nerfhip_plan_set_bwd_compaction; csrc/compact.hip) against the dense one of the same plan and against the
     oracle's autograd.  d(raw output) rows are zeroed at random at the given fractions -- what relu(sigma + noise)
     (nerf/volume_rendering_utils.py:38) does to the cotangents of a training batch: 0 (nothing to drop), in between (ragged last tile,
     gathered rows), 1 (every row zero: the gradient is exactly zero) --; also a batch whose ONLY non-zero row is the last sample.
     Compacted == dense up to the rounding of another split-K partition (`unit.compact_vs_dense`, of max|g| per tensor); the count the
-    library reports is the number of non-zero rows; d(loss)/d(x) comes out the same with zero rows for the dropped samples."""
+    library reports is the number of non-zero rows; d(loss)/d(x) comes out the same with zero rows for the dropped samples.
+    rows: EXACTLY that many rows (exact_rows) instead of what the filter leaves of m; kept_counts: besides, patterns with exactly k
+    non-zero rows for each k (kept_count_patterns) under the same assertions."""
     mb = TL.bound("unit.mlp_bwd", ARITH_NAME[precision])
     margin, tol = mb["margin"], mb["tol"]
     ctol = TL.bound("unit.compact_vs_dense", ARITH_NAME[precision])
@@ -432,11 +474,15 @@ def case_mlp_backward_compacted(b, names=None, m=300, precision=0, fractions=(0.
         plan, params, flat, packed = mlp_setup(b, cfg, seed=47, precision=precision)
         dx, dd = O.model_dims(cfg)
         gen = rng(48)
-        x = torch.randn(m, dx + dd, generator=gen)
-        keep = O.mlp_relu_margin(params, x, cfg) > margin
-        x = x[keep].contiguous()
-        mm = x.shape[0]
-        assert mm >= 0.9 * m
+        if rows is not None:
+            x = exact_rows(params, cfg, rows, gen, margin)
+            mm = rows
+        else:
+            x = torch.randn(m, dx + dd, generator=gen)
+            keep = O.mlp_relu_margin(params, x, cfg) > margin
+            x = x[keep].contiguous()
+            mm = x.shape[0]
+            assert mm >= 0.9 * m
         go_full = torch.randn(mm, 4, generator=gen) * g_scale
         patterns = []
         for fr in fractions:
@@ -445,6 +491,7 @@ def case_mlp_backward_compacted(b, names=None, m=300, precision=0, fractions=(0.
         last = torch.zeros(mm, dtype=torch.bool)
         last[-1] = True
         patterns.append(("only the last sample", last))
+        patterns += kept_count_patterns(mm, kept_counts)
         _, stash = b.mlp_fwd(plan, packed, x.numpy(), want_stash=True)
         for what, on in patterns:
             go = go_full * on[:, None].float()
@@ -746,14 +793,19 @@ def case_f16x3_dead_layers(b, m=120):
             b.lib.plan_destroy(plan)
 
 
-def case_mlp_input_grad(b, names=None, m=150, precision=0):
-    """d(loss)/d(x) of FlexibleNeRFModel.forward vs the oracle's autograd (x enters layer1, the skip layers, layers_dir)."""
+def case_mlp_input_grad(b, names=None, m=150, precision=0, rows=None):
+    """d(loss)/d(x) of FlexibleNeRFModel.forward vs the oracle's autograd (x enters layer1, the skip layers, layers_dir).
+    rows: EXACTLY that many rows, margin-filtered (exact_rows), instead of m unfiltered draws."""
     for name in names or ("default4x128", "fern8x128_skip3_L6", "novw4x128", "odd5x99_skip2"):
         cfg = MLP_GEOMETRIES[name]
         plan, params, flat, packed = mlp_setup(b, cfg, seed=43, precision=precision)
         dx, dd = O.model_dims(cfg)
         gen = rng(44)
-        x = torch.randn(m, dx + dd, generator=gen)
+        if rows is not None:
+            x = exact_rows(params, cfg, rows, gen, TL.bound("unit.mlp_bwd", ARITH_NAME[precision])["margin"])
+            m = rows
+        else:
+            x = torch.randn(m, dx + dd, generator=gen)
         go = torch.randn(m, 4, generator=gen)
         x = x.requires_grad_(True)
         (O.mlp_forward(params, x, cfg) * go).sum().backward()
@@ -763,6 +815,130 @@ def case_mlp_input_grad(b, names=None, m=150, precision=0):
         tol = TL.bound("unit.mlp_input_grad", ARITH_NAME[precision])
         close(gx, ref, tol * float(np.abs(ref).max()) + 1e-7, 10 * tol, what="mlp input grad " + name)
         b.lib.plan_destroy(plan)
+
+
+# One below, on and one above every granularity of the MLP kernels, read from their code: 16 samples per wave (one MFMA tile), the
+# 32-sample stash / gradient tiles k_wgrad reads, 48, the 64-sample workgroups of the 4-wave shapes (64-, 128-, 512-wide nets: for
+# m <= 64 the second workgroup of a group has no rows) and mlp64r's 64-sample rounds, the 128-sample groups, 256.
+ROW_EDGES = (1, 2, 15, 16, 17, 31, 32, 33, 47, 48, 49, 63, 64, 65, 127, 128, 129, 255, 256, 257)
+
+
+def has_resident_image(b, plan):
+    """True for the fp32 plans of 64-wide nets whose stash-free forward is the persistent k_fwd64r (csrc/mlp.hip mlp_forward_any:
+    r64_off >= 0) -- exactly the plans that accept the fused backward modes."""
+    try:
+        b.set_compaction(plan, "fused")
+    except L.NerfHipError:
+        return False
+    b.set_compaction(plan, False)
+    return True
+
+
+def case_mlp_row_edges(b, name, precision, rows_list=ROW_EDGES):
+    """ONE plan at EXACT row counts (ROW_EDGES): the rows are prefixes of one margin-filtered pool (exact_rows), so every launch is
+    a prefix of the next.  Per row count:
+      forward    -- against the oracle's fp32 forward (`unit.mlp_fwd`) and its fp64 forward (`unit.mlp_fwd.vs_fp64_over_scale`, of the
+                    launch's output scale); on training plans the stash-writing forward's outputs equal the stash-free forward's bit
+                    for bit (the same kernel without its stores).  The exception is documented too: an fp32 plan
+                    with an LDS-resident image (64-wide nets, has_resident_image) runs its stash-free forward on ANOTHER kernel
+                    (k_fwd64r, csrc/mlp64r.hip), so there the two forwards are held to `unit.mlp_fwd` of each other instead;
+      backward   -- (training plans) every parameter tensor against the oracle's fp64 autograd at `unit.mlp_bwd`'s tol of max|g| per
+                    tensor, d(loss)/d(x) against it at `unit.mlp_input_grad`;
+      reference  -- the oracle's OWN fp32 autograd is within tol / 4 of its fp64 autograd on these rows for every tensor, else the row
+                    set is ill-conditioned and the case fails (it says nothing about the kernels then; it never skips);
+      prefix     -- the first r output rows of the next larger launch equal the r-row launch's bit for bit (row i sits in the same
+                    lane either way), and so do the first r rows of d(loss)/d(x) on plans whose data gradient runs in fp32; the
+                    fp16-piece data gradient is scaled from the whole batch's cotangents: within 1e-6 of max|g|, the number
+                    case_mlp_backward_compacted holds gx_comp to gx_dense with.  A tail that leaks into, or is fed by, rows that do
+                    not exist shows here.
+    The worst figures per row count go on record."""
+    arith = ARITH_NAME[precision]
+    cfg = MLP_GEOMETRIES[name]
+    train = precision != F16X3                                   # (F16X3: inference-only, forward assertions alone)
+    f16_dgrad = precision in (F16X3_FWD_DGRAD, F16X3_TRAIN)
+    mb = TL.bound("unit.mlp_bwd", arith)
+    margin, tol = mb["margin"], mb["tol"]
+    xtol = TL.bound("unit.mlp_input_grad", arith)
+    plan, params, flat, packed = mlp_setup(b, cfg, seed=71, precision=precision)
+    resident = train and has_resident_image(b, plan)
+    rows_list = sorted(rows_list)
+    gen = rng(72)
+    x_all = exact_rows(params, cfg, rows_list[-1], gen, margin)
+    go_all = torch.randn(rows_list[-1], 4, generator=gen)
+    p64 = {k: v.double() for k, v in params.items()}
+    case = "mlp_row_edges_%s_%s_%s" % (name, arith, b.name)
+    prev = None
+    for r in rows_list:
+        x, go = x_all[:r].contiguous(), go_all[:r].contiguous()
+        what = "%s %s rows=%d" % (name, arith, r)
+        rec = {}
+        # -- forward
+        want = O.mlp_forward(params, x, cfg).numpy()
+        want64 = O.mlp_forward(p64, x.double(), cfg).numpy()
+        got, _ = b.mlp_fwd(plan, packed, x.numpy())
+        rec["fwd_vs_fp64_over_scale"] = float(np.abs(got - want64).max()) / float(np.abs(want64).max())
+        note(case, **{"rows=%03d %s" % (r, k): v for k, v in rec.items()})
+        close(got, want, *TL.bound("unit.mlp_fwd", arith), what="row edges fwd " + what)
+        assert rec["fwd_vs_fp64_over_scale"] < TL.bound("unit.mlp_fwd.vs_fp64_over_scale", arith), (what, rec)
+        gx = None
+        if train:
+            got_s, stash = b.mlp_fwd(plan, packed, x.numpy(), want_stash=True)
+            if resident:
+                close(got_s, got, *TL.bound("unit.mlp_fwd", arith), what="row edges stash-writing vs stash-free fwd " + what)
+                close(got_s, want, *TL.bound("unit.mlp_fwd", arith), what="row edges stash-writing fwd " + what)
+            else:
+                assert np.array_equal(got_s, got), ("stash-writing vs stash-free forward", what, float(np.abs(got_s - got).max()))
+            # -- the references: fp64 autograd, and the oracle's own fp32 autograd as the condition on the row set
+            ref = {}
+            for dt in (torch.float32, torch.float64):
+                p = {k: v.to(dt).clone().requires_grad_(True) for k, v in params.items()}
+                xr = x.to(dt).clone().requires_grad_(True)
+                (O.mlp_forward(p, xr, cfg) * go.to(dt)).sum().backward()
+                ref[dt] = dict({k: v.grad.double().numpy() for k, v in p.items()}, x=xr.grad.double().numpy())
+            r64 = ref[torch.float64]
+            scale = {k: float(np.abs(v).max()) + 1e-12 for k, v in r64.items()}
+            cond = {k: float(np.abs(ref[torch.float32][k] - v).max()) / scale[k] for k, v in r64.items()}
+            rec["oracle_fp32_vs_fp64"] = max(cond.values())
+            assert rec["oracle_fp32_vs_fp64"] <= tol / 4, ("ill-conditioned rows: the oracle's fp32 autograd is that far from its fp64 autograd",
+                                                          what, max(cond, key=cond.get), rec["oracle_fp32_vs_fp64"], tol / 4)
+            # -- backward
+            gflat, gx = b.mlp_bwd(plan, packed, go.numpy(), stash, flat_for_input_grad=flat)
+            grads = b.unflatten(plan, gflat)
+            rec["param_grad_vs_fp64"] = max(float(np.abs(grads[k] - r64[k]).max()) / scale[k] for k in grads)
+            rec["input_grad_vs_fp64"] = float(np.abs(gx - r64["x"]).max()) / scale["x"]
+            note(case, **{"rows=%03d %s" % (r, k): v for k, v in rec.items()})
+            for k in grads:
+                close(grads[k], r64[k], tol * scale[k] + 1e-7, 10 * tol, what="row edges bwd %s %s" % (what, k))
+            close(gx, r64["x"], xtol * scale["x"] + 1e-7, 10 * xtol, what="row edges input grad " + what)
+        # -- prefix invariance against the next smaller launch
+        if prev is not None:
+            pr, pgot, pgx = prev
+            assert np.array_equal(got[:pr], pgot), ("forward rows 0..%d differ between the %d- and the %d-row launch" % (pr - 1, pr, r), what,
+                                                    float(np.abs(got[:pr] - pgot).max()))
+            if train and f16_dgrad:
+                d = float(np.abs(gx[:pr] - pgx).max())
+                assert d <= 1e-6 * (float(np.abs(gx).max()) + 1e-30), ("d(loss)/d(x) rows 0..%d, %d- vs %d-row launch" % (pr - 1, pr, r), what, d)
+            elif train:
+                assert np.array_equal(gx[:pr], pgx), ("d(loss)/d(x) rows 0..%d differ between the %d- and the %d-row launch" % (pr - 1, pr, r),
+                                                      what, float(np.abs(gx[:pr] - pgx).max()))
+        prev = (r, got, gx)
+    b.lib.plan_destroy(plan)
+
+
+def case_persistent_round_edges(b, name, precision, which=(0, 1, 2)):
+    """The fp16-piece forward and data-gradient kernels are persistent: grid = min(groups of 128 rows, compute units).  With C compute
+    units (b.compute_units): 128 C rows -- exactly one round --, 128 C + 1 -- one workgroup runs a second round of ONE row --,
+    128 (C + 1) + 17 -- two second rounds, the last one ragged --, dense, at EXACT row counts: case_mlp_forward and (training plans)
+    case_mlp_backward at their present bounds.  The fp32 plans run the same counts (their grids are not persistent)."""
+    C_ = b.compute_units
+    assert C_ > 0
+    counts = (128 * C_, 128 * C_ + 1, 128 * (C_ + 1) + 17)
+    for i in which:
+        if precision == F16X3:
+            case_mlp_forward_f16x3(b, names=(name,), m=counts[i], precision=F16X3)
+        else:
+            case_mlp_forward(b, names=(name,), m=counts[i], precision=precision)
+            case_mlp_backward(b, names=(name,), precision=precision, rows=counts[i])
 
 
 # ---- the whole path ----------------------------------------------------------------------------------------------------

@@ -3,7 +3,10 @@
 This checks kernel index algebra, weight packing, LDS addressing and barrier placement without a GPU.  It says nothing
 about the hardware; `tests/test_gpu_parity.py` (-m gpu) runs the same cases through the product library on an MI355X.
 """
+import pytest
+
 import parity_cases as P
+import tolerances as TL
 
 
 def test_rays(emu):
@@ -212,6 +215,44 @@ def test_mlp_golden(emu):
 
 def test_mlp_backward(emu):
     P.case_mlp_backward(emu, names=("default4x128", "fern8x128_skip3_L6", "novw4x128"), m=70)
+
+
+# ---- exact row counts at the kernels' tile edges (the GPU suite runs ROW_EDGES whole, on more plans) -----------------------------
+EMU_ROW_EDGES = (1, 15, 16, 17, 31, 32, 33, 63, 64, 65, 129)
+
+
+@pytest.mark.parametrize("name,precision,rows", [
+    ("default4x128", 0, EMU_ROW_EDGES), ("default4x128", P.F16X3_TRAIN, EMU_ROW_EDGES), ("llff4x64_skip3_L6", 0, EMU_ROW_EDGES),
+    ("northstar8x256", 0, (1, 17, 33, 65, 129)), ("wide2x320", 0, (1, 17, 33, 65, 129))],
+    ids=lambda v: P.ARITH_NAME[v] if isinstance(v, int) else (v if isinstance(v, str) else "rows"))
+def test_mlp_row_edges(emu, name, precision, rows):
+    P.case_mlp_row_edges(emu, name, precision, rows)
+
+
+@pytest.mark.parametrize("precision", [0, P.F16X3_TRAIN, P.F16X3], ids=lambda v: P.ARITH_NAME[v])
+def test_mlp_persistent_round_edges(emu, precision):
+    """3 "compute units": 384, 385 and 529 rows."""
+    P.case_persistent_round_edges(emu, "default4x128", precision)
+
+
+def test_compacted_backward_kept_count_edges(emu):
+    P.case_mlp_backward_compacted(emu, names=("default4x128",), rows=290, fractions=(), kept_counts=(1, 32, 33, 128, 129))
+
+
+def test_render_samples_per_ray_not_a_multiple_of_16(emu):
+    """19 + 13 and 43 + 22 samples per ray: a wave's 16 samples straddle two rays in both passes (the GPU suite's other renders of
+    128- and 256-wide nets and of the fp16-piece kernels all use multiples of 16).
+    n starts at 12 for the 8x256 nets: on THREE rays of this geometry the end-to-end fine-net gradient is ill-conditioned by the
+    reference's own account -- the oracle's fp32 autograd is 7.1e-2 of max|g| from its fp64 autograd on the fine net's
+    layers_xyz.0.weight (max|g| 1.5e-5; the kernels: 6.1e-2 fp32, 4.0e-2 fp16 pieces, against the fp32 oracle), beyond
+    `unit.render_grad.fine_sanity` whatever computes it."""
+    bounds = (TL.bound("unit.render_grad.coarse_fp64_yardstick"), TL.bound("unit.render_grad.fine_sanity"))
+    d, ns = P.MLP_GEOMETRIES["default4x128"], P.MLP_GEOMETRIES["northstar8x256"]
+    for prec in (0, P.F16X3_TRAIN):
+        tag = "ragged19+13_%s_emu" % P.ARITH_NAME[prec]
+        P.case_render_vs_oracle(emu, d, n=7, nc=19, nf=13, with_grads=True, tag=tag, grad_tol=bounds, precision=prec)
+        P.case_render_compacted(emu, d, n=7, nc=19, nf=13, precision=prec, tag=tag)
+    P.case_render_vs_oracle(emu, ns, n=12, nc=43, nf=22, with_grads=True, tag="ragged43+22_fp32_emu", grad_tol=bounds)
 
 
 def test_e2e_golden_a(emu):

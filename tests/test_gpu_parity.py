@@ -177,6 +177,59 @@ def test_mlp_backward(gpu):
                                     "northstar8x256"), m=1500)
 
 
+# ---- exact row counts at every tile edge (parity_cases.ROW_EDGES): one plan per test ------------------------------------------------
+_ROW_EDGE_PLANS = [(n, 0) for n in ("default4x128", "novw4x128", "northstar8x256", "llff4x64_skip3_L6", "wide2x320", "odd5x99_skip2",
+                                    "L12_4x128")] \
+    + [(n, P.F16X3_TRAIN) for n in ("default4x128", "northstar8x256", "llff4x64_skip3_L6")] \
+    + [("novw4x128", P.F16X3_FWD_DGRAD)] + [(n, P.F16X3) for n in ("default4x128", "northstar8x256")]
+
+
+@pytest.mark.parametrize("name,precision", _ROW_EDGE_PLANS, ids=["%s-%s" % (n, P.ARITH_NAME[p]) for n, p in _ROW_EDGE_PLANS])
+def test_mlp_row_edges(gpu, name, precision):
+    """Forward, backward, the reference's own conditioning and prefix invariance at 1 ... 257 rows: one below, on and one above 16, 32,
+    48, 64, 128 and 256 (wide2x320: the 512-wide instances; odd5x99_skip2: zero-padded; L12_4x128: the extended slots; F16X3:
+    inference-only, the forward assertions)."""
+    P.case_mlp_row_edges(gpu, name, precision)
+
+
+_PERSISTENT_PLANS = [("default4x128", P.F16X3_TRAIN, (0, 1, 2)), ("default4x128", 0, (0, 1, 2)), ("default4x128", P.F16X3, (0, 1, 2))] \
+    + [("northstar8x256", P.F16X3_TRAIN, (i,)) for i in (0, 1, 2)]
+
+
+@pytest.mark.parametrize("name,precision,which", _PERSISTENT_PLANS,
+                         ids=["%s-%s-%s" % (n, P.ARITH_NAME[p], "".join("abc"[i] for i in w)) for n, p, w in _PERSISTENT_PLANS])
+def test_mlp_persistent_round_edges(gpu, name, precision, which):
+    """Dense batches of 128 C (a), 128 C + 1 (b) and 128 (C + 1) + 17 (c) rows on the device's C compute units: exactly one round of the
+    persistent fp16-piece kernels, a second round of one row, two second rounds with a ragged last one (8x256: one count per test,
+    the reference's autograd over 33,000 rows takes seconds)."""
+    P.case_persistent_round_edges(gpu, name, precision, which)
+
+
+@pytest.mark.parametrize("name,precision", [("default4x128", 0), ("default4x128", P.F16X3_TRAIN), ("northstar8x256", 0), ("llff4x64_skip3_L6", 0)],
+                         ids=lambda v: P.ARITH_NAME[v] if isinstance(v, int) else v)
+def test_compacted_backward_kept_count_edges(gpu, name, precision):
+    """Exactly 290 rows, of which exactly k carry a cotangent -- k on, one below and one above the list path's 32-row tiles and 128-row
+    groups, as the first rows, as the last rows, and (33, 129) strided over the batch."""
+    P.case_mlp_backward_compacted(gpu, names=(name,), precision=precision, rows=290, fractions=(), kept_counts=(1, 31, 32, 33, 127, 128, 129, 289))
+
+
+_RAGGED_RENDERS = [("default4x128", 96, 19, 13), ("northstar8x256", 48, 43, 22)]
+
+
+@pytest.mark.parametrize("arith", ["fp32", "f16x3_train"])
+@pytest.mark.parametrize("name,n,nc,nf", _RAGGED_RENDERS, ids=[r[0] for r in _RAGGED_RENDERS])
+def test_render_samples_per_ray_not_a_multiple_of_16(gpu, name, n, nc, nf, arith):
+    """19 + 13 and 43 + 22 samples per ray: a wave's 16 samples straddle two rays in both passes of the 128- / 256-wide and fp16-piece
+    kernels (every other render of theirs here uses multiples of 16).  Render with gradients at test_northstar_render_and_gradients_vs_oracle's
+    bounds, and the backward's dense / compacted / recomputed modes.  (Not fewer rays: on three rays of 8x256 the end-to-end fine-net
+    gradient is ill-conditioned by the reference's own account, see tests/test_emu_parity.py's case of the same name.)"""
+    prec = {"fp32": 0, "f16x3_train": P.F16X3_TRAIN}[arith]
+    tag = "ragged%d+%d_%s_%d_%s" % (nc, nf, name, n, arith)
+    P.case_render_vs_oracle(gpu, P.MLP_GEOMETRIES[name], n=n, nc=nc, nf=nf, with_grads=True, tag=tag, precision=prec,
+                            grad_tol=(T.bound("unit.render_grad.coarse_fp64_yardstick", arith), T.bound("unit.render_grad.fine_sanity", arith)))
+    P.case_render_compacted(gpu, P.MLP_GEOMETRIES[name], n=n, nc=nc, nf=nf, precision=prec, tag=tag)
+
+
 @pytest.mark.parametrize("arith", ["fp32", "f16x3_fwd_dgrad", "f16x3_train"])
 def test_compacted_backward_equals_dense(gpu, arith):
     """nerfhip_plan_set_bwd_compaction (round 6): the backward over the samples whose d(raw output) row is not all zero == the dense
